@@ -17,6 +17,9 @@ device counter after the timed region) per second -- the extra no-grad density e
 work the step does on top and is not counted.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full    (+ every other block of the line: sustained loop, kernel tables,
+                                                             roofline, PSNR episode, config 4 / 5, render, CPU baseline, ...)
+  python bench.py ... --dump-outputs DIR  (the last timed step's results as DIR/<name>.npy)
   python bench.py --gpus N ...            (spawns its own N ranks through torch.distributed.run on 127.0.0.1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -98,6 +101,14 @@ def parse():
     ap.add_argument('--psnr-app-iters', type=int, default=1500, help='configs/nerf.yaml:26 raw_phase_iter_app')
     ap.add_argument('--comm-dtype', default='fp32', choices=['fp32', 'bf16'], help='payload of the gradient all-reduce (N > 1)')
     ap.add_argument('--sustain-seconds', type=float, default=1.0, help='length of the second, longer measurement (0 = off)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: sustained loop, per-kernel tables and roofline, the other reuse setting, train_app, '
+                         'the other scaling mode and exchange comparisons (N > 1), PSNR episode, faithful / config4 / render / config5 blocks, '
+                         'CPU baseline (the --no-* options and their parameters apply inside it).  Default: set up, warm up, time the K steps, '
+                         'print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (the trained parameters, its sample counts and '
+                         'losses; render mode: the batch\'s colours and distances) as DIR/<name>.npy, float32 / float64')
     return ap.parse_args()
 
 
@@ -455,6 +466,7 @@ def main():
         scene.sample_counters.zero_()
         use_graph = graph and (not args.no_graph) and mode != 'render' and scene.dp_graph_ok()
         graphed = None
+        last_render = {}                                                  # (render mode: the last step's result, for --dump-outputs)
         if mode in ('train_geo', 'train_app'):
             kind = 'geo' if mode == 'train_geo' else 'app'
             net = scene.nerf.geo_mlp if kind == 'geo' else scene.nerf.app_mlp
@@ -487,9 +499,10 @@ def main():
                     res = scene.render_once(Rays(flat_o[bb * 32768:(bb + 1) * 32768], flat_d[bb * 32768:(bb + 1) * 32768]),
                                             ['rgb', 'distance', 'n_marched_dev', 'n_samples_dev'])
                     ops.step_bookkeeping(None, None, scene.sample_counters, res['n_marched_dev'], res['n_samples_dev'])
+                last_render['res'] = res
             eager_step = step
         return {'scene': scene, 'step': step, 'eager_step': eager_step, 'rays_per_step': rays_per_step, 'graphed': graphed,
-                'scaling': scaling}
+                'scaling': scaling, 'mode': mode, 'last_render': last_render}
 
     def timed(run, n_steps, first):
         """n_steps steps bracketed by barrier + synchronize on both sides; -> (seconds = max over ranks, marched, kept)."""
@@ -595,6 +608,25 @@ def main():
         run, head = measure(reuse_default, args.scaling)
     scene, step, eager_step = run['scene'], run['step'], run['eager_step']
     tc, r = scene.train_conf, scene.renderer
+
+    def emit(line):
+        # The JSON line is the LAST thing on stdout: RCCL prints a version banner through C stdio, which a pipe buffers until the
+        # process exits -- every rank flushes it out first, then rank 0 prints.
+        _flush_native_stdout()
+        if world > 1:
+            dist.barrier()
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1 or single_rank_dp:
+            dist.destroy_process_group()
+
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, run)           # before anything below runs more steps on this scene
+    if not args.full:
+        if watchdog is not None:
+            watchdog.cancel()
+        emit(_line(args, world, head, run, None, None, None, None, None, None, notes=notes) if rank == 0 else None)
+        return
 
     # a second, longer measurement of the same loop (the K-step region above is only tens of milliseconds long)
     sustained = None
@@ -758,15 +790,54 @@ def main():
             cpu = cpu_baseline(args.spp, args.cpu_rays)
         line = _line(args, world, head, run, sustained, kern, ev_counts, reuse_block, other_block, psnr_block, cpu=cpu, notes=notes,
                      late=(kern_late, ev_late), blocks={'train_app': app_block, 'faithful': faithful_block, 'render': render_blk, 'config4': config4_blk, 'config5': config5_blk, 'comm': comm_block})
-    # The JSON line is the LAST thing on stdout: RCCL prints a version banner through C stdio, which a pipe buffers until the
-    # process exits -- every rank flushes it out first, then rank 0 prints.
-    _flush_native_stdout()
-    if world > 1:
-        dist.barrier()
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if world > 1 or single_rank_dp:
-        dist.destroy_process_group()
+    emit(line)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(out_dir, run):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy (float32, counts and losses float64).
+    Training modes: the fp32 parameters of the network the step trains (after its Adam update), the step's marched / kept sample
+    counts, its loss values and, where the step renders one, its colour render; render mode: the batch's colours, distances and
+    counts.  An array that would take the total past 64 MB is replaced by a fixed, seeded sample of its entries (<name>.npy, with
+    the flat indices in <name>_index.npy)."""
+    import numpy as np
+    torch.cuda.synchronize()
+    scene = run['scene']
+    arrays = {}
+    if run['mode'] == 'render':
+        res = run['last_render']['res']
+        arrays.update(rgb=res['rgb'], distance=res['distance'], n_marched=res['n_marched_dev'], n_kept=res['n_samples_dev'])
+    else:
+        kind = 'geo' if run['mode'] == 'train_geo' else 'app'
+        arrays[f'{kind}_params'] = getattr(scene.nerf, f'{kind}_mlp').params.detach()
+        counts = getattr(scene, '_last_counts', None)
+        if counts is not None:
+            arrays.update(n_marched=counts[0], n_kept=counts[1])
+        for k, v in scene.last_losses.items():
+            arrays[k] = v
+        if getattr(scene, 'last_colors', None) is not None:
+            arrays['colors'] = scene.last_colors
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        if v is not None:
+            t = v.detach().cpu() if torch.is_tensor(v) else torch.as_tensor(v)
+            exact = not t.is_floating_point() or t.dtype == torch.float64 or t.numel() == 1
+            host[name] = t.double().numpy() if exact else t.float().numpy()
+    used = 0
+    for name, a in sorted(host.items(), key=lambda kv: kv[1].nbytes):          # (smallest first: only the largest get sampled)
+        if used + a.nbytes > DUMP_LIMIT_BYTES:
+            n = (DUMP_LIMIT_BYTES - used) // (a.itemsize + 8)                   # (each kept entry + its float64 index)
+            if n < 1:
+                continue
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+            np.save(os.path.join(out_dir, f'{name}_index.npy'), idx.astype(np.float64))
+            used += idx.size * 8
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+        used += a.nbytes
 
 
 def _kernel_table(args, kern, ev_counts, prepass, only_priced=False):

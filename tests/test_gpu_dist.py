@@ -179,7 +179,7 @@ def test_bench_launches_its_own_ranks(tmp_path, n_ranks):
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', PYTHONPATH=ROOT, PERF_BENCH_ONE_DEVICE='1', PERF_BENCH_BACKEND='gloo')
     env.pop('WORLD_SIZE', None); env.pop('RANK', None)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n_ranks), '--steps', '3', '--warmup', '1', '--rays-per-gpu', '1024',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', str(n_ranks), '--steps', '3', '--warmup', '1', '--rays-per-gpu', '1024',
            '--sustain-seconds', '0', '--psnr-geo-iters', '40', '--psnr-app-iters', '30', '--height', '128', '--width', '256']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

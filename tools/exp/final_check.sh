@@ -6,12 +6,12 @@ cd $R
 O=gpurun_out/final; rm -rf $O; mkdir -p $O
 python -m pytest tests -m gpu -q --maxfail=20 > $O/tests.log 2>&1
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-python bench.py > $O/bench_line.json 2> $O/bench.err
+python bench.py --full > $O/bench_line.json 2> $O/bench.err
 python tools/render_dense.py > $O/render_dense_16.json 2> $O/rd.err
 python tools/render_dense.py --batch 524288 > $O/render_dense_frame.json 2>> $O/rd.err
 python tools/train_episode.py > $O/train_episode.json 2> $O/ep.err
 python tools/exp/fwd_v2.py --out $O/fwd_v2.json > $O/fwd_v2.log 2>&1
-bash tools/exp/dp_single.sh > $O/dp_single.log 2>&1
+bash tools/exp/dp_single.sh $O/dp1 > $O/dp_single.log 2>&1
 bash tools/exp/ep_prof.sh > $O/ep_prof.log 2>&1
 bash tools/exp/r03_profile.sh > $O/r03_profile.log 2>&1
 grep -E "passed|failed" $O/tests.log | tail -2; tail -1 $O/smoke.log; python - <<'P'

@@ -7,9 +7,9 @@ cd $R
 ( time timeout 1800 python -m pytest tests -m gpu -q --maxfail=8 --durations=10 ) > $O/pytest.log 2>&1
 echo "pytest rc=$?" >> $O/pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-( time timeout 600 python bench.py ) > $O/bench.log 2> $O/bench.err
+( time timeout 600 python bench.py --full ) > $O/bench.log 2> $O/bench.err
 tail -1 $O/bench.log > $O/bench_line.json
-PERF_DP_SINGLE_RANK=1 timeout 600 python bench.py --no-cpu-baseline --no-psnr --no-render-block --no-config4 --no-config5 --no-train-app > $O/bench_dp1.log 2> $O/bench_dp1.err
+PERF_DP_SINGLE_RANK=1 timeout 600 python bench.py --full --no-cpu-baseline --no-psnr --no-render-block --no-config4 --no-config5 --no-train-app > $O/bench_dp1.log 2> $O/bench_dp1.err
 tail -1 $O/bench_dp1.log > $O/bench_dp1_line.json
 for S in room doorway pillars; do
   timeout 600 python tools/soak_episodes.py --episodes 5 --scene $S > $O/soak_$S.log 2>&1

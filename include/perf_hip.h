@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PERF_ABI_VERSION 13
+#define PERF_ABI_VERSION 14
 
 #define PERF_OK 0
 #define PERF_E_INVALID (-1)   /* bad argument */
@@ -65,9 +65,10 @@ extern "C" {
 #define PERF_MAX_LEVELS 24
 
 /* Table layout of a grid.  TCNN: tiny-cuda-nn's -- what every grid of the reference uses (modules/fields/ngp_nerf.py:96-134), the
- * only layout the gradient / second-order / fused entry points accept.  LINE_LOCAL: opt-in, inference only (perf_hashgrid_fwd,
- * perf_hashgrid_corners, perf_field_infer), for grids the reference never defines (BASELINE.json configs[4]: L = 20 tables sized to
- * HBM): a level with local[l] != 0 stores the vertices of a 4 x 4 x 2 block as one 128-byte line (entry x%4 + 4 (y%4) + 16 (z%2)),
+ * only layout perf_hashgrid_bwd, the input-gradient / second-order entry points and the fused encode + MLP kernel accept.  LINE_LOCAL:
+ * opt-in, for grids the reference never defines (BASELINE.json configs[4]: L = 20 tables sized to HBM); forward through
+ * perf_hashgrid_fwd, perf_hashgrid_corners and perf_field_infer, parameter gradient through perf_hashgrid_bwd_lines and perf_field_bwd
+ * (ABI 14; no input gradient, no second order, no data-parallel integer exchange): a level with local[l] != 0 stores the vertices of a 4 x 4 x 2 block as one 128-byte line (entry x%4 + 4 (y%4) + 16 (z%2)),
  * the blocks of a super-block of 2^sb_shift[0] x 2^sb_shift[1] x 2^sb_shift[2] vertices contiguously (x-major), and addresses the
  * SUPER-BLOCK densely (sx + sy*nsx[l] + sz*nsxy[l], hashed[l] == 0) or by the prime-XOR hash of its coordinates modulo
  * size[l] >> (sb_shift[0] + sb_shift[1] + sb_shift[2]).  offset[l] of such a level is a multiple of 32 entries (its blocks ARE cache
@@ -265,6 +266,23 @@ int perf_hashgrid_bwd(const perf_grid_desc* grid, const float* x01, const float*
                       int32_t* overflow_flag, int32_t* headroom_state, const int32_t* shifts_dev, int raw_fields,
                       const int32_t* redo_flag, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* perf_hashgrid_bwd for PERF_LAYOUT_LINE_LOCAL / _OVERLAP grids (ABI 14; a TCNN grid is refused: use perf_hashgrid_bwd).  Same
+ * parameters and semantics -- accumulate, level_absmax (fixed-point units of perf_hashgrid_bwd), overflow_flag, headroom_state, n_dev,
+ * redo_flag (the predicated fp32 repair; PERF_E_UNSUPPORTED when a line-local level has more than 255 tiles), workspace -- except that
+ * shifts_dev and raw_fields (the data-parallel integer exchange) are refused.  The line-local levels must be a suffix of the grid (res
+ * grows with the level); the levels in front of them go through perf_hashgrid_bwd's kernels.  A line-local level of <= 255 tiles of
+ * 16,384 entries (tile = entry >> 14) is owned by LDS workgroups; larger ones -- and all of them when the workspace is smaller than
+ * perf_hashgrid_bwd_lines_workspace_bytes(grid, 0) -- take a global-atomics scatter.  In fixed-point mode both paths add the same
+ * integers (bit-identical tables).  LINE_OVERLAP: both storage copies of a shared vertex (position 3 of a run, position 0 of the next
+ * run of the row) receive the sum of their contributions -- with accumulate, the sum of this call's contributions is added -- and a
+ * row's never-read last entry receives 0, so an elementwise optimizer keeps the copies equal; needs 2^(sb_shift[0] - 2) <= 512.  An
+ * overwriting call also writes 0 into the padding in front of a line-local level (the level starts on a super-block boundary). */
+int64_t perf_hashgrid_bwd_lines_workspace_bytes(const perf_grid_desc* grid, int64_t n);
+int perf_hashgrid_bwd_lines(const perf_grid_desc* grid, const float* x01, const float* dfeat,
+                            float* grad_table, int64_t n, const int64_t* n_dev, int accumulate, const float* level_absmax,
+                            int32_t* overflow_flag, int32_t* headroom_state, const int32_t* shifts_dev, int raw_fields,
+                            const int32_t* redo_flag, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- job-wide fixed-point units of a data-parallel step (no counterpart in the reference, which is single-GPU;
  *      rays shard over the GPUs, one gradient exchange per step) ------------------------------------------
  * Between the MLP backward and the grid backward every rank packs PERF_DP_STATS int32 words -- the float bits of its
@@ -347,7 +365,8 @@ int perf_field_infer(const perf_grid_desc* grid, const perf_mlp_desc* mlp, const
                      void* scratch, int64_t scratch_bytes, void* feat_out, int dtype, void* stream);
 
 /* The whole backward of one field as ONE boundary call (the backward of a tcnn.NetworkWithInputEncoding forward:
- * modules/fields/ngp_nerf.py:142,158 under modules/scene/nerf.py:252-253): perf_mlp_bwd -> perf_hashgrid_bwd into the table part of the
+ * modules/fields/ngp_nerf.py:142,158 under modules/scene/nerf.py:252-253): perf_mlp_bwd -> perf_hashgrid_bwd (line-local layouts:
+ * perf_hashgrid_bwd_lines) into the table part of the
  * same flat gradient -> (fixed != 0 && redo != 0) the predicated fp32 repair launch -- chained on the stream, nothing else runs.
  * grad: fp32 [n_net | 2 * table entries], overwritten.  w16_net: the network part of the 16-bit working copy.  fixed != 0: packed
  * fixed-point accumulation (overflow_flag / headroom_state as in perf_hashgrid_bwd).  workspace: perf_field_bwd_workspace_bytes(...)

@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libperf_hip.so')
 
-ABI_VERSION = 13         # PERF_ABI_VERSION of include/perf_hip.h this binding was written against
+ABI_VERSION = 14         # PERF_ABI_VERSION of include/perf_hip.h this binding was written against
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -67,6 +67,8 @@ _SIGS = {
     'perf_hashgrid_fwd_f32': (c_int, [POINTER(GridDesc), P, P, P, c_int64, P]),
     'perf_hashgrid_bwd_workspace_bytes': (c_int64, [POINTER(GridDesc), c_int64]),
     'perf_hashgrid_bwd': (c_int, [POINTER(GridDesc), P, P, P, c_int64, P, c_int, P, P, P, P, c_int, P, P, c_int64, P]),
+    'perf_hashgrid_bwd_lines_workspace_bytes': (c_int64, [POINTER(GridDesc), c_int64]),
+    'perf_hashgrid_bwd_lines': (c_int, [POINTER(GridDesc), P, P, P, c_int64, P, c_int, P, P, P, P, c_int, P, P, c_int64, P]),
     'perf_dp_stats_pack': (c_int, [P, P, P, c_int64, P, P]),
     'perf_dp_units': (c_int, [POINTER(GridDesc), P, c_int32, P, P, P, c_int32, P]),
     'perf_dp_slot_pack': (c_int, [P, P, P, c_int64, P, P, c_int64, c_int32, c_int32, P, P]),

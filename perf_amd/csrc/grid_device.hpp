@@ -25,14 +25,14 @@ struct GridLocal {
     uint32_t nsxy[PERF_MAX_LEVELS];
 };
 
-// loc == nullptr: the caller only understands tcnn's layout (gradients, second order, the fused encode + MLP kernel, the
-// 16-level forward kernel): a line-local descriptor is refused
+// loc == nullptr: the caller only understands tcnn's layout (perf_hashgrid_bwd, input gradient, second order, the fused encode + MLP
+// kernel, the 16-level forward kernel): a line-local descriptor is refused
 static int fill_params(const perf_grid_desc* g, GridParams* p, GridLocal* loc = nullptr) {
     PERF_REQUIRE(g != nullptr, "grid desc is NULL");
     PERF_REQUIRE(g->n_levels >= 1 && g->n_levels <= PERF_MAX_LEVELS, "n_levels %d out of range", g->n_levels);
     PERF_REQUIRE(g->layout == PERF_LAYOUT_TCNN || g->layout == PERF_LAYOUT_LINE_LOCAL || g->layout == PERF_LAYOUT_LINE_OVERLAP, "unknown table layout %d", (int)g->layout);
     PERF_REQUIRE(g->layout == PERF_LAYOUT_TCNN || loc != nullptr,
-                 "this entry point takes tcnn-layout grids only (PERF_LAYOUT_LINE_LOCAL / _OVERLAP are inference only: perf_hashgrid_fwd, perf_hashgrid_corners, perf_field_infer)");
+                 "this entry point takes tcnn-layout grids only (PERF_LAYOUT_LINE_LOCAL / _OVERLAP: perf_hashgrid_fwd, perf_hashgrid_corners, perf_field_infer; parameter gradient: perf_hashgrid_bwd_lines, perf_field_bwd)");
     if (loc) {
         loc->any = 0; loc->ovl = 0; loc->shx = loc->shy = 2; loc->shz = 1;
         for (int l = 0; l < PERF_MAX_LEVELS; ++l) loc->local[l] = loc->nsx[l] = loc->nsxy[l] = 0;

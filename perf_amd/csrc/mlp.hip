@@ -146,7 +146,8 @@ extern "C" int perf_field_infer(const perf_grid_desc* grid, const perf_mlp_desc*
 extern "C" int64_t perf_field_bwd_workspace_bytes(const perf_grid_desc* grid, const perf_mlp_desc* mlp, int64_t n, int64_t* mlp_ws_bytes,
                                                  int64_t* grid_ws_bytes, int64_t* dfeat_bytes) {
     if (!grid || !mlp || n < 0) return -1;
-    const int64_t a = perf_mlp_bwd_workspace_bytes(mlp, n), b = perf_hashgrid_bwd_workspace_bytes(grid, n);
+    const int64_t a = perf_mlp_bwd_workspace_bytes(mlp, n),
+                  b = grid->layout == PERF_LAYOUT_TCNN ? perf_hashgrid_bwd_workspace_bytes(grid, n) : perf_hashgrid_bwd_lines_workspace_bytes(grid, n);
     if (a < 0 || b < 0) return -1;
     const int64_t a16 = (a + 15) & ~(int64_t)15, b16 = (b + 31) & ~(int64_t)15, c = (int64_t)grid->n_levels * n * 8;
     if (mlp_ws_bytes) *mlp_ws_bytes = a16;
@@ -206,11 +207,13 @@ static int field_bwd_chain(const perf_grid_desc* grid, const perf_mlp_desc* mlp,
     rc = perf_internal_mlp_bwd(mlp, w16_net, feat16, feat_index, feat_stride, sel, dout, dfeat, grad, fixed ? amax : nullptr, mlp_ws, a16, n, n_dev, dtype,
                                stream, &job);
     if (rc) return rc;
-    rc = perf_internal_hashgrid_bwd(grid, x01, dfeat, grad + n_net, n, n_dev, 0, fixed ? amax : nullptr, fixed ? overflow_flag : nullptr,
-                                    fixed ? headroom_state : nullptr, nullptr, 0, nullptr, grid_ws, b16, stream, &job);
+    // (the grid part by table layout: the line-local layouts take perf_hashgrid_bwd_lines)
+    auto grid_bwd = grid->layout == PERF_LAYOUT_TCNN ? &perf_internal_hashgrid_bwd : &perf_internal_hashgrid_bwd_lines;
+    rc = grid_bwd(grid, x01, dfeat, grad + n_net, n, n_dev, 0, fixed ? amax : nullptr, fixed ? overflow_flag : nullptr,
+                  fixed ? headroom_state : nullptr, nullptr, 0, nullptr, grid_ws, b16, stream, &job, nullptr);
     if (rc) return rc;
     if (fixed && redo)
-        rc = perf_internal_hashgrid_bwd(grid, x01, dfeat, grad + n_net, n, n_dev, 0, nullptr, nullptr, headroom_state, nullptr, 0, overflow_flag, nullptr, 0,
-                                        stream, nullptr, book);
+        rc = grid_bwd(grid, x01, dfeat, grad + n_net, n, n_dev, 0, nullptr, nullptr, headroom_state, nullptr, 0, overflow_flag, nullptr, 0,
+                      stream, nullptr, book);
     return rc;
 }

@@ -13,15 +13,18 @@ import torch.nn as nn
 
 from . import ops
 from . import tcnn
+from .grid import LOCAL_MIN_RES
 from .tcnn import _DualFieldFn, field_apply
 
 PER_LEVEL_SCALE = 1.4472692012786865
 
 
-def _grid_cfg(n_levels=16, log2_hashmap_size=18, base_resolution=16, per_level_scale=PER_LEVEL_SCALE):
-    return {"otype": "HashGrid", "n_levels": n_levels, "n_features_per_level": 2,
-            "log2_hashmap_size": log2_hashmap_size, "base_resolution": base_resolution,
-            "per_level_scale": per_level_scale}
+def _grid_cfg(n_levels=16, log2_hashmap_size=18, base_resolution=16, per_level_scale=PER_LEVEL_SCALE, layout_kw=None):
+    cfg = {"otype": "HashGrid", "n_levels": n_levels, "n_features_per_level": 2,
+           "log2_hashmap_size": log2_hashmap_size, "base_resolution": base_resolution,
+           "per_level_scale": per_level_scale}
+    cfg.update(layout_kw or {})         # (GridConfig.from_tcnn's optional keys layout / sb_shift / local_min_res)
+    return cfg
 
 
 class _TruncExp(torch.autograd.Function):
@@ -68,7 +71,10 @@ class NGPNeRF(nn.Module):
     """Instant-NGP radiance field (ngp_nerf.py:68-198)."""
 
     def __init__(self, aabb: Union[torch.Tensor, List[float]], num_dim: int = 3, use_viewdirs: bool = False,
-                 unbounded: bool = False, n_levels: int = 16, dtype=None, log2_hashmap_size: int = 18):
+                 unbounded: bool = False, n_levels: int = 16, dtype=None, log2_hashmap_size: int = 18, layout: str = 'tcnn',
+                 sb_shift=None, local_min_res: int = LOCAL_MIN_RES):
+        """layout (not the reference's): 'tcnn' or the opt-in line-local table layouts of perf_amd.grid.GridConfig ('line_local' /
+        'line_overlap', with sb_shift / local_min_res), for both fields; trained through ops.hashgrid_bwd_lines."""
         super().__init__()
         if not isinstance(aabb, torch.Tensor):
             aabb = torch.tensor(aabb, dtype=torch.float32, device='cpu')
@@ -80,9 +86,15 @@ class NGPNeRF(nn.Module):
         self.n_levels = n_levels
         self.dtype_name = dtype
         # (n_levels / log2_hashmap_size beyond the reference's 16 / 18: BASELINE config 5's tables sized to HBM)
-        self.geo_mlp = _DensityNet(_grid_cfg(n_levels, log2_hashmap_size), dtype=dtype)
+        self._layout_kw = None
+        if layout != 'tcnn':
+            self._layout_kw = {'layout': layout, 'local_min_res': local_min_res}
+            if sb_shift is not None:
+                self._layout_kw['sb_shift'] = tuple(int(v) for v in sb_shift)
+        self._geo_cfg = (n_levels, log2_hashmap_size)
+        self.geo_mlp = _DensityNet(_grid_cfg(n_levels, log2_hashmap_size, layout_kw=self._layout_kw), dtype=dtype)
         self.app_mlp = tcnn.NetworkWithInputEncoding(
-            3, 3, _grid_cfg(n_levels, log2_hashmap_size),
+            3, 3, _grid_cfg(n_levels, log2_hashmap_size, layout_kw=self._layout_kw),
             {"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "Sigmoid", "n_neurons": 64,
              "n_hidden_layers": 2}, dtype=dtype)
 
@@ -120,6 +132,9 @@ class NGPNeRF(nn.Module):
         geo_grad / app_grad = False detach the respective parameters (nerf_renderer.py:166-179 no_grad branches)."""
         pg = self.geo_mlp.params if geo_grad else self.geo_mlp.params.detach()
         pa = self.app_mlp.params if app_grad else self.app_mlp.params.detach()
+        if self.geo_mlp.grid.layout != 'tcnn':
+            # (the shared-corner dual encode is tcnn-layout only: line-local tables encode each field on its own)
+            return field_apply(self.geo_mlp, x01, pg, sel)[:, 0], field_apply(self.app_mlp, x01, pa, sel)
         sig, rgb = _DualFieldFn.apply(x01, pg, pa, sel, self.geo_mlp, self.app_mlp)
         return sig[:, 0], rgb
 
@@ -132,7 +147,8 @@ class NGPNeRF(nn.Module):
 
     def reset_geo(self):
         """Fresh geometry network, identical initialisation every episode (ngp_nerf.py:178-197)."""
-        self.geo_mlp = _DensityNet(_grid_cfg(16), dtype=self.dtype_name)
+        # (the field's own grid: levels, table size, layout -- the defaults (16, 18, tcnn) give the reference's grid bit for bit)
+        self.geo_mlp = _DensityNet(_grid_cfg(*self._geo_cfg, layout_kw=self._layout_kw), dtype=self.dtype_name)
 
 
 class InferenceNeRF:

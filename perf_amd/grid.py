@@ -28,7 +28,8 @@ class GridConfig:
     per_level_scale: float = 1.4472692012786865
     interpolation: str = 'Linear'
     # Table layout.  'tcnn': tiny-cuda-nn's (dense x + y res + z res^2, or the prime-XOR hash of the vertex) -- the only layout of
-    # every grid the reference defines.  'line_local' (opt-in, inference only; BASELINE config 5's L = 20 tables sized to HBM, for
+    # every grid the reference defines.  'line_local' (opt-in; parameter gradient through ops.hashgrid_bwd_lines, no input gradient / second
+    # order / data-parallel exchange; BASELINE config 5's L = 20 tables sized to HBM, for
     # which no reference result exists): levels with res >= local_min_res store a 4 x 4 x 2 block of vertices as one 128-byte
     # line, the blocks of a 2^sb_shift-vertex super-block (default 32 x 64 x 256 = 2 MiB) contiguously, and hash (or densely
     # index) the SUPER-BLOCK: a sample's eight corners lie in ~2.3 lines of one page.  'line_overlap': line_local whose 16-byte x
@@ -102,12 +103,17 @@ class GridConfig:
         otype = cfg.get('otype', 'HashGrid')
         if otype not in ('HashGrid', 'Grid'):
             raise ValueError(f'unsupported encoding otype {otype!r}')
+        # (optional keys of this build, not tcnn's: the table layout -- absent, the grid is tcnn's)
+        sb = cfg.get('sb_shift')
         return cls(n_levels=int(cfg.get('n_levels', 16)),
                    n_features_per_level=int(cfg.get('n_features_per_level', 2)),
                    log2_hashmap_size=int(cfg.get('log2_hashmap_size', 19)),
                    base_resolution=int(cfg.get('base_resolution', 16)),
                    per_level_scale=float(cfg.get('per_level_scale', 2.0)),
-                   interpolation=str(cfg.get('interpolation', 'Linear')))
+                   interpolation=str(cfg.get('interpolation', 'Linear')),
+                   layout=str(cfg.get('layout', 'tcnn')),
+                   sb_shift=tuple(int(v) for v in sb) if sb is not None else None,
+                   local_min_res=int(cfg.get('local_min_res', LOCAL_MIN_RES)))
 
     @property
     def n_params(self) -> int:

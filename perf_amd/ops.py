@@ -261,20 +261,54 @@ def hashgrid_bwd(grid: GridConfig, x01, dfeat, out=None, accumulate=False, level
     return out
 
 
+def hashgrid_bwd_lines(grid: GridConfig, x01, dfeat, out=None, accumulate=False, level_absmax=None, n_dev=None, hr_state=None,
+                       use_owners=True, use_codes=True):
+    """hashgrid_bwd for the line-local table layouts ('line_local' / 'line_overlap'; perf_hashgrid_bwd_lines): dfeat [L, n, 2] f32 ->
+    gradient table [total*2] f32, overwritten or added to (accumulate=True).  level_absmax selects the fixed-point accumulation, hr_state
+    its headroom feedback.  'line_overlap': both storage copies of a shared vertex receive the vertex's gradient.  use_owners=False
+    (tests): a workspace without room for the LDS owners selects the global-atomics scatter for every line-local level; use_codes=False:
+    one without room for the tile codes, the position-streaming owners."""
+    if grid.layout == 'tcnn':
+        raise ValueError('hashgrid_bwd_lines takes line-local layouts; a tcnn-layout grid goes through hashgrid_bwd')
+    n = x01.shape[0]
+    if out is None:
+        out = torch.empty(grid.n_params, dtype=torch.float32, device=x01.device)
+        accumulate = False
+    d = grid.desc()
+    lib = _lib.load()
+    ws_bytes = lib.perf_hashgrid_bwd_lines_workspace_bytes(ctypes.byref(d), n if use_codes else 0)
+    if ws_bytes < 0:
+        _lib.check(-1, 'perf_hashgrid_bwd_lines_workspace_bytes')
+    if not use_owners:
+        # the tcnn-rule levels' own minimum only: no room for the line-local owners
+        pre = _lib.GridDesc.from_buffer_copy(d)
+        pre.n_levels = int(grid.local.argmax()) if grid.local.any() else grid.n_levels
+        pre.layout = _lib.LAYOUT_TCNN
+        ws_bytes = lib.perf_hashgrid_bwd_workspace_bytes(ctypes.byref(pre), 0) if pre.n_levels > 0 else 0
+    ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=x01.device)
+    fixed = level_absmax is not None
+    flag = overflow_flag(x01.device) if fixed else None
+    _call('perf_hashgrid_bwd_lines', ctypes.byref(d), _p(_f32(x01, 'x01')), _p(_f32(dfeat, 'dfeat')), _p(_f32(out, 'grad')),
+          n, _nd(n_dev), int(bool(accumulate)), _p(level_absmax), _p(flag), _p(hr_state if fixed else None), None, 0,
+          None, _p(ws), ws_bytes, _stream())
+    return out
+
+
 def hashgrid_bwd_redo_supported(grid: GridConfig) -> bool:
-    """Grids whose levels all fit LDS owners (<= 255 hashed / 64 dense tiles of 16,384 entries): PeRF's L16/T18 does."""
+    """Grids whose levels all fit LDS owners (<= 255 hashed / 64 dense tiles of 16,384 entries; line-local levels: <= 255 tiles):
+    PeRF's L16/T18 does."""
     for l in range(grid.n_levels):
         tiles = -(-int(grid.size[l]) // 16384)
-        if tiles > (255 if grid.hashed[l] else 64):
+        if tiles > (255 if grid.hashed[l] or grid.local[l] else 64):
             return False
     return True
 
 
 def hashgrid_bwd_redo(grid: GridConfig, x01, dfeat, out, n_dev=None, hr_state=None):
     """The repair launch of a fixed-point hashgrid_bwd into the same `out`: a no-op dispatch unless that call raised the
-    overflow flag, else the table gradient again with fp32 LDS accumulation (perf_hashgrid_bwd, redo_flag)."""
+    overflow flag, else the table gradient again with fp32 LDS accumulation (perf_hashgrid_bwd / perf_hashgrid_bwd_lines, redo_flag)."""
     d = grid.desc()
-    _call('perf_hashgrid_bwd', ctypes.byref(d), _p(_f32(x01, 'x01')), _p(_f32(dfeat, 'dfeat')), _p(_f32(out, 'grad')),
+    _call('perf_hashgrid_bwd' if grid.layout == 'tcnn' else 'perf_hashgrid_bwd_lines', ctypes.byref(d), _p(_f32(x01, 'x01')), _p(_f32(dfeat, 'dfeat')), _p(_f32(out, 'grad')),
           x01.shape[0], _nd(n_dev), 0, None, None, _p(hr_state), None, 0, _p(overflow_flag(x01.device)), None, 0, _stream(),
           label='perf_hashgrid_bwd(redo: predicated no-op)')
     return out
@@ -342,6 +376,10 @@ def field_bwd(grid: GridConfig, mlp: MlpConfig, x01, w16_net, feat16, dout, sel=
 
 
 def hashgrid_bwd_into(grid, x01, dfeat, out, level_absmax=None, n_dev=None, hr_state=None, shifts=None, raw_fields=False):
+    if grid.layout != 'tcnn':
+        if shifts is not None or raw_fields:
+            raise ValueError(f'{grid.layout}: given units / raw fields (the data-parallel integer exchange) need the tcnn table layout')
+        return hashgrid_bwd_lines(grid, x01, dfeat, out=out, accumulate=False, level_absmax=level_absmax, n_dev=n_dev, hr_state=hr_state)
     return hashgrid_bwd(grid, x01, dfeat, out=out, accumulate=False, level_absmax=level_absmax, n_dev=n_dev, hr_state=hr_state,
                         shifts=shifts, raw_fields=raw_fields)
 
@@ -451,7 +489,7 @@ def field_infer(grid: GridConfig, mlp: MlpConfig, x01, sel, w16, n_dev=None, wan
     n_net = mlp.n_params
     out = torch.empty(n, mlp.n_output_dims, dtype=torch.float32, device=x01.device)
     feat = torch.empty(grid.n_levels, n, 2, dtype=w16.dtype, device=x01.device) if want_features else None
-    fused = n <= FUSED_MAX_SAMPLES and grid.n_levels <= 16
+    fused = n <= FUSED_MAX_SAMPLES and grid.n_levels <= 16 and grid.layout == 'tcnn'      # (perf_field_infer's own choice)
     if _PROF is not None and not fused:
         # per-kernel timing (bench.py): the same two kernels the boundary call launches, issued one by one so that each gets
         # its own event pair

@@ -417,8 +417,17 @@ class _HipStepKernels:
 
 
 class NeRFScene:
+    GRID_CONF_KEYS = ('n_levels', 'log2_hashmap_size', 'layout', 'sb_shift', 'local_min_res')
+
     def __init__(self, base_exp_dir=None, train_conf=None, estimator_type='occ', renderer_conf=None, dtype=None,
-                 fused_adam=True, writer=None):
+                 fused_adam=True, writer=None, grid_conf=None):
+        """grid_conf (not the reference's): None -- the reference's grids (L16 / T18, tcnn's table layout) -- or a dict of
+        n_levels, log2_hashmap_size, layout ('tcnn' | 'line_local' | 'line_overlap'), sb_shift, local_min_res for both fields.
+        The line-local layouts train on one process only (no data-parallel integer exchange for them)."""
+        if grid_conf is not None:
+            unknown = set(grid_conf) - set(self.GRID_CONF_KEYS)
+            if unknown:
+                raise ValueError(f'grid_conf: unknown keys {sorted(unknown)} (known: {self.GRID_CONF_KEYS})')
         if estimator_type != 'occ':
             raise NotImplementedError("estimator_type 'prop' is dead code in the reference (nerf_renderer.py:73)")
         self.aabb = torch.tensor([-1.0, -1.0, -1.0, 1.0, 1.0, 1.0], device='cpu')
@@ -437,7 +446,8 @@ class NeRFScene:
         self.writer = writer
         self.writer_every = 16
         self.train_conf = train_conf or default_train_conf()
-        self.nerf = NGPNeRF(aabb=self.aabb, dtype=dtype)
+        self.grid_conf = dict(grid_conf) if grid_conf is not None else None
+        self.nerf = NGPNeRF(aabb=self.aabb, dtype=dtype, **(self.grid_conf or {}))
         self.estimator = OccGridEstimator(roi_aabb=self.aabb, resolution=256, levels=1).cuda()
         self.renderer = NeRFOCCRenderer(**(renderer_conf or {'max_radius': 2, 'bg_color': 'rand_noise'}))
         self.fused_adam = fused_adam
@@ -730,8 +740,17 @@ class NeRFScene:
                 w.add_scalar(tag, float(self.last_losses[key]), step)
         w.add_scalar('others/lr_' + kind, float(lr), step)
 
+    def _layout(self):
+        return self.nerf.geo_mlp.grid.layout
+
+    def _check_dp_layout(self, dist):
+        if dist is not None and self._layout() != 'tcnn':
+            raise NotImplementedError(f'data-parallel training needs the tcnn table layout: the {self._layout()!r} grid gradient has no '
+                                      'integer exchange between ranks (perf_hashgrid_bwd_lines refuses raw fields / given units)')
+
     def _batch(self, sup_pool, generator=None):
         dist, rank, world = self._dist()
+        self._check_dp_layout(dist)
         bs = self.train_conf.pixel_loss_batch_size
         rays, col, dep, nrm = sup_pool.rand_ray_color_data(bs, rand_mode=self.pixel_sup_rand_mode, generator=generator,
                                                             rank=rank, world_size=world)
@@ -743,6 +762,7 @@ class NeRFScene:
     def _draw(self, sup_pool, want_bg):
         """The step's batch and uniform draws from the device generator -> (rays, colors, depths, global batch, dist_info, rand)."""
         dist, rank, world = self._dist()
+        self._check_dp_layout(dist)
         if self._rng_counter is None:
             self._rng_seed = int(torch.initial_seed())
             self._rng_counter = torch.zeros(1, dtype=torch.int64, device=sup_pool.all_sup_colors.device)
@@ -1252,6 +1272,7 @@ class NeRFScene:
         argument and issues nothing but the graph.  Without it: replay(lr, progress) refreshes the two scalars per call."""
         assert isinstance(optimizer, FusedAdam), 'graph capture needs the fused Adam (device-side step/lr)'
         dist_info = self._dist()
+        self._check_dp_layout(dist_info[0])
         assert dist_info[0] is None or self._sharded(dist_info, optimizer), \
             'graphed data-parallel steps need the sharded exchange (dp_mode = "sharded", fixed-point grid backward)'
         assert self._can_fuse() if kind == 'geo' else self.fused_steps, 'graph capture covers the explicit step chains'
@@ -1441,12 +1462,24 @@ class NeRFScene:
         # The fixed-point headroom feedback of the two grid gradients makes results depend on the call history: it travels
         # with the checkpoint, under a private TOP-LEVEL key -- the reference's loader reads only 'render' / 'nerf' /
         # 'estimator' (nerf.py:368-380) and its strict nerf.load_state_dict would reject a key inside 'nerf'.
+        extra = {'geo_headroom': self.nerf.geo_mlp.headroom_state().detach().clone(),
+                 'app_headroom': self.nerf.app_mlp.headroom_state().detach().clone()}
+        if self._layout() != 'tcnn':            # (the table layout: the same parameters mean another field under another layout)
+            g = self.nerf.geo_mlp.grid
+            extra['grid_layout'] = {'layout': g.layout, 'sb_shift': tuple(g.sb_shift), 'local_min_res': int(g.local_min_res)}
         return {'render': self.renderer.state_dict(), 'nerf': self.nerf.state_dict(),
-                'estimator': self.estimator.state_dict(),
-                self._STATE_KEY: {'geo_headroom': self.nerf.geo_mlp.headroom_state().detach().clone(),
-                                  'app_headroom': self.nerf.app_mlp.headroom_state().detach().clone()}}
+                'estimator': self.estimator.state_dict(), self._STATE_KEY: extra}
 
     def load_state_dict(self, state_dict):
+        extra = state_dict.get(self._STATE_KEY) or {}
+        g = self.nerf.geo_mlp.grid
+        mine = {'layout': g.layout, 'sb_shift': tuple(g.sb_shift), 'local_min_res': int(g.local_min_res)} if g.layout != 'tcnn' else None
+        theirs = extra.get('grid_layout')
+        if theirs is not None:
+            theirs = dict(theirs, sb_shift=tuple(int(v) for v in theirs['sb_shift']))
+        if mine != theirs:
+            raise ValueError(f'checkpoint table layout {theirs or "tcnn"} does not match this scene\'s {mine or "tcnn"}: '
+                             'the same parameters hold another field under another layout')
         self.renderer.load_state_dict(state_dict['render'])
         self.nerf.load_state_dict(state_dict['nerf'])
         self.estimator.load_state_dict(state_dict['estimator'])

@@ -44,13 +44,14 @@ def _init_params(mlp: MlpConfig, grid: GridConfig, seed: int, device=None) -> to
             parts.append((torch.rand(o * i, generator=g, device='cpu') * 2 - 1) * s)
     device = torch.device(device) if device is not None else torch.device('cpu')
     if device.type != 'cuda':
-        parts.append((torch.rand(grid.n_params, generator=g, device='cpu') * 2 - 1) * 1e-4)
+        parts.append(grid.canonicalize_((torch.rand(grid.n_params, generator=g, device='cpu') * 2 - 1) * 1e-4))
         return torch.cat(parts).to(device)
     n_net = sum(p.numel() for p in parts)
     out = torch.empty(n_net + grid.n_params, dtype=torch.float32, device=device)
     if n_net:
         out[:n_net] = torch.cat(parts).to(device)
     out[n_net:].uniform_(-1e-4, 1e-4, generator=torch.Generator(device=device).manual_seed(seed))
+    grid.canonicalize_(out[n_net:])         # ('line_overlap': the two copies of a shared vertex hold one value; other layouts: no-op)
     return out
 
 

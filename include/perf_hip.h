@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PERF_ABI_VERSION 14
+#define PERF_ABI_VERSION 15
 
 #define PERF_OK 0
 #define PERF_E_INVALID (-1)   /* bad argument */
@@ -416,6 +416,17 @@ int perf_pano_raygen(const float* pose, int32_t height, int32_t width, int32_t r
 /* Same with the pose (12+ floats, row major) read from DEVICE memory: a hipGraph holding a whole frame of
  * CoreRunner.render_dense (core_exp_runner.py:223-246) is replayed with a new pose per frame. */
 int perf_pano_raygen_dev(const float* pose_dev, int32_t height, int32_t width, int32_t row0, int32_t nrows,
+                         float* rays_o, float* rays_d, void* stream);
+/* gen_pers_rays (utils/camera_utils.py:237-241) with cam_rays_cam_space (:60-80), OpenCV style, for rows [row0,row0+nrows) of an
+ * H x W perspective frame of vertical field of view fovy (radians, in (0, pi)): y = linspace(-tan(fovy/2), tan(fovy/2), H) down
+ * the rows, x = linspace(-span_x, span_x, W) across with span_x = tan(fovy/2) * W/H (spans in double, endpoints rounded to fp32
+ * as torch.linspace rounds them), d = R (x, y, 1) / ||(x, y, 1)||, o = t.  The reference's render_dense renders these for any
+ * cam_type other than 'pano' (core_exp_runner.py:235), keeping the trajectory's look-at rotation.
+ * pose: 16 host floats, row major 4x4.  rays_o, rays_d [nrows*W,3]. */
+int perf_pers_raygen(const float* pose, int32_t height, int32_t width, double fovy, int32_t row0, int32_t nrows,
+                     float* rays_o, float* rays_d, void* stream);
+/* Same with the pose (12+ floats, row major) read from DEVICE memory (a captured perspective frame replayed per pose). */
+int perf_pers_raygen_dev(const float* pose_dev, int32_t height, int32_t width, double fovy, int32_t row0, int32_t nrows,
                          float* rays_o, float* rays_d, void* stream);
 
 /* ---- occupancy-grid marching (nerfacc traverse_grids; nerf_renderer.py:145-155) ------------ */

@@ -5,12 +5,12 @@ module raises.  Build the library with `python -m perf_amd.build` (or __graft_en
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p)
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libperf_hip.so')
 
-ABI_VERSION = 14         # PERF_ABI_VERSION of include/perf_hip.h this binding was written against
+ABI_VERSION = 15         # PERF_ABI_VERSION of include/perf_hip.h this binding was written against
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -88,6 +88,8 @@ _SIGS = {
     'perf_mlp_bwd': (c_int, [POINTER(MlpDesc), P, P, P, c_int64, P, P, P, P, P, P, c_int64, c_int64, P, c_int, P]),
     'perf_pano_raygen': (c_int, [POINTER(c_float), c_int32, c_int32, c_int32, c_int32, P, P, P]),
     'perf_pano_raygen_dev': (c_int, [P, c_int32, c_int32, c_int32, c_int32, P, P, P]),
+    'perf_pers_raygen': (c_int, [POINTER(c_float), c_int32, c_int32, c_double, c_int32, c_int32, P, P, P]),
+    'perf_pers_raygen_dev': (c_int, [P, c_int32, c_int32, c_double, c_int32, c_int32, P, P, P]),
     'perf_occ_pack_bits': (c_int, [P, P, c_int64, P]),
     'perf_occ_jitter_points': (c_int, [c_uint64, c_uint64, c_int64, c_int64, c_int32, POINTER(c_float), P, P]),
     'perf_occ_ema_update': (c_int, [P, P, c_int64, c_float, P, P]),

@@ -1,4 +1,4 @@
-// Streaming helpers: parameter cast, fused Adam, sample positions, panorama ray generation,
+// Streaming helpers: parameter cast, fused Adam, sample positions, panorama and perspective ray generation,
 // occupancy bit packing and the occupancy pre-grid splat.  All are one-pass HBM-bound kernels with
 // fully coalesced accesses.
 #include <stdarg.h>
@@ -177,6 +177,31 @@ __global__ __launch_bounds__(256) void pano_raygen_kernel(RayGen rg, const float
     ro[3 * t] = P[3]; ro[3 * t + 1] = P[7]; ro[3 * t + 2] = P[11];
 }
 
+// gen_pers_rays (utils/camera_utils.py:237-241) on cam_rays_cam_space (:60-80), OpenCV style: y = linspace(-span_y, span_y, H)[i]
+// down the rows, x = linspace(-span_x, span_x, W)[j] across, v = (x, y, 1) / ||(x, y, 1)|| (a true division, as xyz / norm), d = R v,
+// o = t.  The squared norm is summed as torch's CPU norm sums it (x*x, then y*y fused onto it, then 1), the rotation as
+// torch.matmul (three products, added left to right).
+__global__ __launch_bounds__(256) void pers_raygen_kernel(RayGen rg, const float* __restrict__ pose_dev, float* __restrict__ ro,
+                                                          float* __restrict__ rd) {
+    if (pose_dev) {                 // pose read from device memory (a captured hipGraph is replayed with new poses)
+#pragma unroll
+        for (int k = 0; k < 12; ++k) rg.pose[k] = pose_dev[k];
+    }
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t total = (int64_t)rg.nrows * rg.width;
+    if (t >= total) return;
+    const int i = rg.row0 + (int)(t / rg.width), j = (int)(t % rg.width);
+    const float y = linspace_at(rg.i_start, rg.i_end, rg.i_step, rg.height, i);
+    const float x = linspace_at(rg.j_start, rg.j_end, rg.j_step, rg.width, j);
+    const float norm = sqrtf(add_rn(__fmaf_rn(y, y, mul_rn(x, x)), 1.0f));   // (sqrtf and / round correctly: hipcc default)
+    const float vx = __fdiv_rn(x, norm), vy = __fdiv_rn(y, norm), vz = __fdiv_rn(1.0f, norm);
+    const float* P = rg.pose;
+    rd[3 * t] = add_rn(add_rn(mul_rn(P[0], vx), mul_rn(P[1], vy)), mul_rn(P[2], vz));
+    rd[3 * t + 1] = add_rn(add_rn(mul_rn(P[4], vx), mul_rn(P[5], vy)), mul_rn(P[6], vz));
+    rd[3 * t + 2] = add_rn(add_rn(mul_rn(P[8], vx), mul_rn(P[9], vy)), mul_rn(P[10], vz));
+    ro[3 * t] = P[3]; ro[3 * t + 1] = P[7]; ro[3 * t + 2] = P[11];
+}
+
 __global__ __launch_bounds__(256) void occ_pack_kernel(const uint8_t* __restrict__ b, uint32_t* __restrict__ bits, int64_t n_cells) {
     const int64_t wi = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (wi * 32 >= n_cells) return;
@@ -329,36 +354,66 @@ extern "C" int perf_points_normalize(const float* x, const float* aabb, float* x
     return PERF_OK;
 }
 
-static int raygen_launch(const float* pose, const float* pose_dev, int32_t height, int32_t width, int32_t row0, int32_t nrows,
-                         float* rays_o, float* rays_d, void* stream);
+// The launch of both cameras.  fovy == 0: the panorama (pixel centres (i + .5) / H, (j + .5) / W); otherwise the perspective
+// frame of that vertical field of view, span_y = tan(fovy / 2) and span_x = span_y * (W / H) in double as NumPy forms them.
+// Either way the linspace endpoints are rounded to fp32 as torch.linspace rounds them and the step is formed in fp32 from those.
+static int raygen_launch(double fovy, const float* pose, const float* pose_dev, int32_t height, int32_t width, int32_t row0,
+                         int32_t nrows, float* rays_o, float* rays_d, void* stream);
 
 extern "C" int perf_pano_raygen(const float* pose, int32_t height, int32_t width, int32_t row0, int32_t nrows,
                                 float* rays_o, float* rays_d, void* stream) {
     PERF_REQUIRE(pose, "NULL pointer");
-    return raygen_launch(pose, nullptr, height, width, row0, nrows, rays_o, rays_d, stream);
+    return raygen_launch(0.0, pose, nullptr, height, width, row0, nrows, rays_o, rays_d, stream);
 }
 
 extern "C" int perf_pano_raygen_dev(const float* pose_dev, int32_t height, int32_t width, int32_t row0, int32_t nrows,
                                     float* rays_o, float* rays_d, void* stream) {
     PERF_REQUIRE(pose_dev, "NULL pointer");
-    return raygen_launch(nullptr, pose_dev, height, width, row0, nrows, rays_o, rays_d, stream);
+    return raygen_launch(0.0, nullptr, pose_dev, height, width, row0, nrows, rays_o, rays_d, stream);
 }
 
-static int raygen_launch(const float* pose, const float* pose_dev, int32_t height, int32_t width, int32_t row0, int32_t nrows,
-                         float* rays_o, float* rays_d, void* stream) {
+extern "C" int perf_pers_raygen(const float* pose, int32_t height, int32_t width, double fovy, int32_t row0, int32_t nrows,
+                                float* rays_o, float* rays_d, void* stream) {
+    PERF_REQUIRE(pose, "NULL pointer");
+    PERF_REQUIRE(fovy > 0.0 && fovy < M_PI, "perf_pers_raygen: fovy %g outside (0, pi)", fovy);
+    return raygen_launch(fovy, pose, nullptr, height, width, row0, nrows, rays_o, rays_d, stream);
+}
+
+extern "C" int perf_pers_raygen_dev(const float* pose_dev, int32_t height, int32_t width, double fovy, int32_t row0, int32_t nrows,
+                                    float* rays_o, float* rays_d, void* stream) {
+    PERF_REQUIRE(pose_dev, "NULL pointer");
+    PERF_REQUIRE(fovy > 0.0 && fovy < M_PI, "perf_pers_raygen_dev: fovy %g outside (0, pi)", fovy);
+    return raygen_launch(fovy, nullptr, pose_dev, height, width, row0, nrows, rays_o, rays_d, stream);
+}
+
+static int raygen_launch(double fovy, const float* pose, const float* pose_dev, int32_t height, int32_t width, int32_t row0,
+                         int32_t nrows, float* rays_o, float* rays_d, void* stream) {
+    const bool pers = fovy != 0.0;
     PERF_REQUIRE(rays_o && rays_d, "NULL pointer");
-    PERF_REQUIRE(height >= 2 && width >= 2 && row0 >= 0 && nrows >= 0 && row0 + nrows <= height, "bad panorama shape");
+    PERF_REQUIRE(height >= 2 && width >= 2 && row0 >= 0 && nrows >= 0 && row0 <= height && nrows <= height - row0,
+                 pers ? "bad perspective frame shape" : "bad panorama shape");
     if (nrows == 0) return PERF_OK;
     RayGen rg;
     for (int i = 0; i < 16; ++i) rg.pose[i] = pose ? pose[i] : 0.f;
-    rg.i_start = (float)(.5 / height); rg.i_end = (float)(1. - .5 / height);
-    rg.j_start = (float)(.5 / width); rg.j_end = (float)(1. - .5 / width);
+    if (pers) {
+        const double span_y = tan(fovy * .5), span_x = span_y * ((double)width / (double)height);
+        rg.i_start = (float)-span_y; rg.i_end = (float)span_y;
+        rg.j_start = (float)-span_x; rg.j_end = (float)span_x;
+    } else {
+        rg.i_start = (float)(.5 / height); rg.i_end = (float)(1. - .5 / height);
+        rg.j_start = (float)(.5 / width); rg.j_end = (float)(1. - .5 / width);
+    }
     rg.i_step = (rg.i_end - rg.i_start) / (float)(height - 1);
     rg.j_step = (rg.j_end - rg.j_start) / (float)(width - 1);
     rg.height = height; rg.width = width; rg.row0 = row0; rg.nrows = nrows;
     const int64_t total = (int64_t)nrows * width;
-    hipLaunchKernelGGL(pano_raygen_kernel, dim3((unsigned)div_up(total, 256)), dim3(256), 0, as_stream(stream), rg, pose_dev, rays_o, rays_d);
-    PERF_LAUNCH_CHECK("perf_pano_raygen");
+    if (pers) {
+        hipLaunchKernelGGL(pers_raygen_kernel, dim3((unsigned)div_up(total, 256)), dim3(256), 0, as_stream(stream), rg, pose_dev, rays_o, rays_d);
+        PERF_LAUNCH_CHECK("perf_pers_raygen");
+    } else {
+        hipLaunchKernelGGL(pano_raygen_kernel, dim3((unsigned)div_up(total, 256)), dim3(256), 0, as_stream(stream), rg, pose_dev, rays_o, rays_d);
+        PERF_LAUNCH_CHECK("perf_pano_raygen");
+    }
     return PERF_OK;
 }
 

@@ -561,6 +561,44 @@ def pano_raygen_dev(pose_dev, height, width, row0=0, nrows=None, out=None):
     return o, d
 
 
+def _pose16(pose):
+    vals = [float(v) for v in torch.as_tensor(pose).detach().cpu().reshape(-1).tolist()]
+    if len(vals) not in (12, 16):
+        raise _lib.PerfError(f'pose must be a [4,4] or [3,4] matrix, got {len(vals)} values')
+    return (ctypes.c_float * 16)(*vals)
+
+
+def _ray_bufs(out, nrows, width, dev):
+    if out is None:
+        return (torch.empty(nrows, width, 3, dtype=torch.float32, device=dev),
+                torch.empty(nrows, width, 3, dtype=torch.float32, device=dev))
+    o, d = out
+    for t in (o, d):
+        if _f32(t, 'rays').numel() < nrows * width * 3:
+            raise _lib.PerfError(f'ray buffer of {t.numel()} floats for {nrows}x{width} rays')
+    return o, d
+
+
+def pers_raygen(pose, height, width, fovy, row0=0, nrows=None, device='cuda'):
+    """gen_pers_rays / cam_rays_cam_space (utils/camera_utils.py:60-80, 237-241) for rows [row0, row0+nrows) of a height x width
+    perspective frame of vertical field of view fovy (radians): -> (o, d) [nrows, width, 3].  pose [4,4] or [3,4] on any device."""
+    nrows = height - row0 if nrows is None else nrows
+    o, d = _ray_bufs(None, nrows, width, device)
+    _call('perf_pers_raygen', _pose16(pose), height, width, float(fovy), row0, nrows, _p(o), _p(d), _stream())
+    return o, d
+
+
+def pers_raygen_dev(pose_dev, height, width, fovy, row0=0, nrows=None, out=None):
+    """pers_raygen with the pose (float32 [4,4] or [12+]) in device memory; `out` = (o, d) preallocated [nrows*width,3] buffers
+    (a captured hipGraph writes the same buffers on every replay)."""
+    nrows = height - row0 if nrows is None else nrows
+    if _f32(pose_dev, 'pose').numel() < 12:
+        raise _lib.PerfError('pose_dev must hold at least 12 floats (row major 3x4)')
+    o, d = _ray_bufs(out, nrows, width, pose_dev.device)
+    _call('perf_pers_raygen_dev', _p(pose_dev), height, width, float(fovy), row0, nrows, _p(o), _p(d), _stream())
+    return o, d
+
+
 # ---- occupancy marching ----------------------------------------------------------------------------
 def occ_pack_bits(binaries: torch.Tensor) -> torch.Tensor:
     b = binaries.reshape(-1)

@@ -129,6 +129,13 @@ def gen_pano_rays(pose, height=512, width=1024, device='cuda'):
     return Rays(o, d)
 
 
+def gen_pers_rays(pose, fov, res, device='cuda'):
+    """utils/camera_utils.py:237-241: a res x res perspective frame of field of view fov (radians), OpenCV style, the pose's
+    rotation and translation applied; generated in one kernel."""
+    o, d = ops.pers_raygen(pose, res, res, fov, device=device)
+    return Rays(o, d)
+
+
 def default_train_conf():
     """configs/nerf.yaml:24-74"""
     opt = lambda i, p, a, l: SimpleNamespace(init_lr=i, peak_lr=p, peak_at=a, lr_alpha=l)
@@ -1354,14 +1361,15 @@ class NeRFScene:
 
     # ---- hipGraph capture of a whole eval frame (BASELINE config 4: render_dense, core_exp_runner.py:223-246) ----------
     @torch.no_grad()
-    def make_graphed_render(self, height, width, query_keys=('rgb', 'distance'), batch_size=32768, samples_per_ray=None):
+    def make_graphed_render(self, height, width, query_keys=('rgb', 'distance'), batch_size=32768, samples_per_ray=None, fovy=None):
         """One panorama frame -- rays generated from a device-resident pose, then ceil(H*W / batch_size) batches of
         NeRFScene.render_once (marching, no-grad density pass, visibility compaction, colour field, compositing, eval
         background) -- captured as ONE hipGraph with capacity-sized sample arrays and device-side counts.  Returns
         frame(pose [4,4]) -> {key: [H, W, C]} (tensors owned by the graph: valid until the next call).  After a replay the
         per-batch marched counts are checked against the capacity (one read-back per frame, after the frame is complete);
         a frame that did not fit is rendered again through a re-captured, larger graph, so results never depend on the
-        capacity."""
+        capacity.  fovy (radians): the frame is a height x width perspective view (gen_pers_rays: what the reference's render_dense
+        renders for cam_type != 'pano') instead of a panorama."""
         self.set_eval()
         dev = self.nerf.aabb.device
         n = height * width
@@ -1380,7 +1388,10 @@ class NeRFScene:
         r = self.renderer
 
         def body():
-            ops.pano_raygen_dev(pose_dev, height, width, out=(o_buf, d_buf))
+            if fovy is None:
+                ops.pano_raygen_dev(pose_dev, height, width, out=(o_buf, d_buf))
+            else:
+                ops.pers_raygen_dev(pose_dev, height, width, fovy, out=(o_buf, d_buf))
             fo, fd = o_buf.view(-1, 3), d_buf.view(-1, 3)
             for b in range(n_batches):
                 lo, hi = b * batch_size, min((b + 1) * batch_size, n)

@@ -1,17 +1,19 @@
 """BASELINE config 4 (render_dense, core_exp_runner.py:223-247): a dense camera trajectory through a trained scene,
-512x1024 panoramic frames, fp16 inference, reference-faithful variable-count sampling.
+512x1024 panoramic frames (--cam-type pano, the reference's default: rotation reset to identity) or res x res perspective
+frames of a 75-degree field of view that keep the trajectory's look-at rotation (--cam-type pers, the reference's
+gen_pers_rays branch), fp16 inference, reference-faithful variable-count sampling.
 
-  python tools/render_dense.py [--poses 600] [--geo-steps 300] [--app-steps 150]
+  python tools/render_dense.py [--poses 600] [--geo-steps 300] [--app-steps 150] [--cam-type pers [--fov-deg 75] [--res 512]]
 
 Frames are rendered back to back on the device (the reference writes PNGs and a video in between: host IO, out of
-scope); prints frames/s, rays/s, ray-samples/s actually evaluated, and a checksum of the frames."""
+scope); prints the camera, frames/s, rays/s, ray-samples/s actually evaluated, and a checksum of the frames."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from perf_amd import ops, synthetic
 from perf_amd.pose_sampler import CirclePoseSampler, DenseTravelPoseSampler
-from perf_amd.scene import NeRFScene, SupInfoPool, gen_pano_rays
+from perf_amd.scene import NeRFScene, SupInfoPool, gen_pano_rays, gen_pers_rays
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--poses', type=int, default=600)
@@ -20,6 +22,9 @@ ap.add_argument('--app-steps', type=int, default=150)
 ap.add_argument('--dtype', default='fp16')
 ap.add_argument('--head', type=int, default=2, help='two-phase sampler: density first on that many samples per ray (0 = one phase)')
 ap.add_argument('--batch', type=int, default=32768, help='rays per graph-captured eval batch (the reference hard-codes 32768, nerf.py:86)')
+ap.add_argument('--cam-type', choices=('pano', 'pers'), default='pano', help="the reference's render_dense(cam_type=...): 'pano' or a perspective frame")
+ap.add_argument('--fov-deg', type=float, default=75., help='field of view of the perspective frames (core_exp_runner.py:235)')
+ap.add_argument('--res', type=int, default=512, help='side of the square perspective frames (core_exp_runner.py:235)')
 args = ap.parse_args()
 
 torch.manual_seed(0); np.random.seed(0)
@@ -58,20 +63,24 @@ t0 = time.perf_counter()
 dense_seq = DenseTravelPoseSampler(sparse, n_dense_poses=args.poses)   # the same trajectory computed in line, for the record
 t_sampler = time.perf_counter() - t0
 assert torch.equal(dense_seq.sample_poses, dense.sample_poses) and np.array_equal(np.random.get_state()[1], rng1[1])
+pano = args.cam_type == 'pano'
+fov = float(np.deg2rad(args.fov_deg))
 poses = []
 for i in range(dense.n_poses):
     p = dense.sample_pose(i).clone().float()
-    p[:3, :3] = torch.eye(3)                                        # core_exp_runner.py:232
+    if pano:
+        p[:3, :3] = torch.eye(3)                                    # core_exp_runner.py:232 (a perspective frame keeps it, :235)
     poses.append(p)
 
-fh, fw = 512, 1024
+fh, fw = (512, 1024) if pano else (args.res, args.res)
+def frame_rays(p):
+    return gen_pano_rays(p, fh, fw) if pano else gen_pers_rays(p, fov, args.res)
 def frame_eager(p):
-    r = gen_pano_rays(p, fh, fw)
-    return scene.render(r, ['rgb', 'distance'], batch_size=args.batch)
+    return scene.render(frame_rays(p), ['rgb', 'distance'], batch_size=args.batch)
 
-# ONE hipGraph per frame: ray generation from a device-resident pose + 16 eval batches of 32,768 rays (nerf.py:86)
+# ONE hipGraph per frame: ray generation from a device-resident pose + the eval batches of 32,768 rays (nerf.py:86)
 scene.renderer.head_samples = args.head or None
-frame = scene.make_graphed_render(fh, fw, ('rgb', 'distance'), batch_size=args.batch)
+frame = scene.make_graphed_render(fh, fw, ('rgb', 'distance'), batch_size=args.batch, fovy=None if pano else fov)
 for p in poses[:3]:
     frame(p)
 torch.cuda.synchronize()
@@ -92,14 +101,26 @@ for p in poses[:60]:
 torch.cuda.synchronize()
 t_eager = (time.perf_counter() - t0) / 60
 from perf_amd.scene import Rays as _Rays
-_r0 = gen_pano_rays(poses[0], fh, fw)
+# sample counts of every frame of the trajectory, rendered once more outside the timed loop: the samples whose density was
+# evaluated (the two-phase sampler's head samples + the tails of the rays still alive) and the samples kept by the visibility
+# compaction (what the colour field and the compositing evaluate)
 scene.set_eval(); scene.renderer.sample_capacity = fh * fw * 64
+_counts = []
 with torch.no_grad():
-    _c = scene.render_once(_Rays(_r0.o.reshape(-1, 3), _r0.d.reshape(-1, 3)), ['n_marched_dev', 'n_samples_dev'])
+    for p in poses:
+        _r = frame_rays(p)
+        _c = scene.render_once(_Rays(_r.o.reshape(-1, 3), _r.d.reshape(-1, 3)), ['n_marched_dev', 'n_samples_dev'])
+        _counts.append(torch.stack([_c['n_marched_dev'].reshape(()), _c['n_samples_dev'].reshape(())]))
+_counts = torch.stack(_counts).cpu()
 scene.renderer.sample_capacity = None
-print(json.dumps({'config': 'render_dense: %d poses, %dx%d panoramic frames in %d hipGraph-captured %d-ray batches, %s, variable-count sampling' % (len(poses), fw, fh, (fh * fw + args.batch - 1) // args.batch, args.batch, args.dtype),
-                  'frame0_marched_samples': int(_c['n_marched_dev'].item()), 'frame0_kept_samples': int(_c['n_samples_dev'].item()),
+marched_total, kept_total = (int(v) for v in _counts.sum(0))
+print(json.dumps({'config': 'render_dense: %d poses, %dx%d %s frames in %d hipGraph-captured %d-ray batches, %s, variable-count sampling' % (len(poses), fw, fh, 'panoramic' if pano else 'perspective', (fh * fw + args.batch - 1) // args.batch, args.batch, args.dtype),
+                  'camera': args.cam_type, 'fov_deg': None if pano else args.fov_deg, 'frame_hw': [fh, fw],
+                  'frame0_marched_samples': int(_counts[0, 0]), 'frame0_kept_samples': int(_counts[0, 1]),
                   'frames_per_s': len(poses) / t, 'rays_per_s': len(poses) * fh * fw / t, 'seconds': t,
+                  'ray_samples_per_s': {'density_evaluated': marched_total / t, 'kept': kept_total / t},
+                  'samples_per_ray': {'density_evaluated': marched_total / (len(poses) * fh * fw), 'kept': kept_total / (len(poses) * fh * fw)},
+                  'count_capacity_exceeded': bool((_counts[:, 0] > fh * fw * 64).any()),
                   'eager_sync_free_frames_per_s': 1.0 / t_eager, 'graphed_frame_equals_eager_frame': same,
                   'per_ray_sample_capacity': frame.state['per_ray'], 'head_samples': args.head,
                   'pose_sampler_host_s': t_sampler, 'pose_sampler_start_call_s': t_start_call, 'pose_sampler_wait_s': t_wait,

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PERF_ABI_VERSION 15
+#define PERF_ABI_VERSION 16
 
 #define PERF_OK 0
 #define PERF_E_INVALID (-1)   /* bad argument */
@@ -614,6 +614,26 @@ int perf_render_finish_eval(const float* opacity, float* distance, float* color,
  * (values == NULL: n_channels must be 1 and out[r] = sum_i w_i).  One wave per ray, no atomics. */
 int perf_accumulate_fwd(const float* weights, const float* values, const int32_t* packed_info, int64_t n_rays,
                         int32_t n_channels, float* out, void* stream);
+
+/* Density and its spatial gradient in one pass (ABI 16): grad [n,3] fp32 = d out_0 / d x in WORLD units -- the derivative of row 0 of
+ * act(MLP(encode(x01))) * sel w.r.t. x01, times inv_extent[axis] = 1 / (aabb_max - aabb_min) (a HOST array of 3 floats; NULL: 1, the
+ * gradient w.r.t. x01) -- and, when sigma != NULL, sigma [n] fp32 = that row itself, bit-identical to perf_field_infer's.  sel[i] == 0
+ * rows give zeros.  The activation's derivative is the reference's: PERF_ACT_EXP -> exp(min(y - shift, 15)) (_TruncExp.backward,
+ * modules/fields/ngp_nerf.py:24-40).  One kernel: every wave gathers the corners of its 32 samples once, forms the features AND
+ * their derivatives along x, y, z in registers, runs the network forward on MFMA, pulls row 0 back through the ReLU masks and the
+ * transposed weights and contracts -- no feature gradient in memory, no weight gradient, 16-bit working copy only (table16 / w16 as
+ * perf_field_infer takes them).  n / n_dev as everywhere: rows at and beyond *n_dev are left untouched.
+ * Built: PERF_LAYOUT_TCNN, PERF_INTERP_LINEAR, n_hidden_layers == 1, 1..16 levels, both 16-bit types, any n >= 0.  Refused with
+ * PERF_E_INVALID: the line-local layouts, Smoothstep, two hidden layers, more than 16 levels, mlp->n_levels != grid->n_levels. */
+int perf_field_grad_x(const perf_grid_desc* grid, const perf_mlp_desc* mlp, const float* x01, const uint8_t* sel,
+                      const void* table16, const void* w16, const float* inv_extent, float* grad, float* sigma,
+                      int64_t n, const int64_t* n_dev, int dtype, void* stream);
+
+/* Per-ray normal from per-sample density gradients (ABI 16): N = sum_i w_i n_i over the ray's samples with n_i = -grad_i / |grad_i|
+ * (0 where grad_i is zero or not finite), normal[r] = N / |N|, exactly 0 where |N| == 0 (rays without samples).  grad [n,3] as
+ * perf_field_grad_x writes it, weights [n] as perf_composite_fwd does.  16 lanes per ray, fixed summation order. */
+int perf_normal_composite(const float* weights, const float* grad, const int32_t* packed_info, int64_t n_rays,
+                          float* normal, void* stream);
 
 /* nerfacc.pack_info: (start,count) per ray from SORTED int64 ray_indices [n]. */
 int perf_pack_info(const int64_t* ray_indices, int64_t n, int64_t n_rays, int32_t* packed_info, void* stream);

@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_in
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libperf_hip.so')
 
-ABI_VERSION = 15         # PERF_ABI_VERSION of include/perf_hip.h this binding was written against
+ABI_VERSION = 16         # PERF_ABI_VERSION of include/perf_hip.h this binding was written against
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -117,6 +117,8 @@ _SIGS = {
     'perf_composite_bwd': (c_int, [P, P, P, P, c_int64, P, P, P, P, P, P, P, P, P, P, P]),
     'perf_render_finish_eval': (c_int, [P, P, P, c_int64, P, P]),
     'perf_accumulate_fwd': (c_int, [P, P, P, c_int64, c_int32, P, P]),
+    'perf_field_grad_x': (c_int, [POINTER(GridDesc), POINTER(MlpDesc), P, P, P, P, POINTER(c_float), P, P, c_int64, P, c_int, P]),
+    'perf_normal_composite': (c_int, [P, P, P, c_int64, P, P]),
     'perf_pack_info': (c_int, [P, c_int64, c_int64, P, P]),
     'perf_distloss_fwd': (c_int, [P, P, P, P, c_int64, P, P]),
     'perf_distloss_bwd': (c_int, [P, P, P, P, c_int64, c_float, P, P, P]),

@@ -124,6 +124,30 @@ class NGPNeRF(nn.Module):
         sig, feat = ops.field_infer(net.grid, net.mlp, x01, sel, net.working_copy(), n_dev=n_dev, want_features=True)
         return sig[:, 0], feat
 
+    def _inv_extent(self):
+        a = self._aabb_host
+        return [1.0 / (a[3 + i] - a[i]) for i in range(3)]
+
+    @torch.no_grad()
+    def density_grad_at(self, x01, sel, n_dev=None):
+        """(sigma [n], d sigma / d x [n,3] in world units) at normalised positions, one kernel on the 16-bit working copy
+        (ops.field_grad_x).  Evaluation only: nothing is recorded for autograd."""
+        net = self.geo_mlp
+        return ops.field_grad_x(net.grid, net.mlp, x01, sel, net.working_copy(), self._inv_extent(), n_dev=n_dev)
+
+    @torch.no_grad()
+    def query_normal(self, x):
+        """World positions [..., 3] -> (sigma [..., 1], unit normal [..., 3]); n = -grad sigma / |grad sigma| faces the side the density
+        falls towards (the camera's side of a surface: -dir . n > 0, the reference's convention), zero where the gradient is zero."""
+        shape = list(x.shape[:-1])
+        x01, sel = ops.points_normalize(x.reshape(-1, 3).contiguous().float(), self._aabb_host)
+        sigma, g = self.density_grad_at(x01, sel)
+        m = g.abs().amax(dim=-1, keepdim=True)
+        u = g / torch.where(m > 0, m, torch.ones_like(m))
+        nrm = torch.linalg.vector_norm(u, dim=-1, keepdim=True)
+        normal = torch.where(nrm > 0, -u / torch.where(nrm > 0, nrm, torch.ones_like(nrm)), torch.zeros_like(u))
+        return sigma.view(shape + [1]), normal.view(shape + [3])
+
     def rgb_at(self, x01, sel, n_dev=None):
         return field_apply(self.app_mlp, x01, self.app_mlp.params, sel, n_dev)
 
@@ -203,6 +227,12 @@ class InferenceNeRF:
     def density_at(self, x01, sel, n_dev=None):
         mlp, w16 = self.nets['geo_mlp']
         return ops.field_infer(self.grid, mlp, x01, sel, w16, n_dev=n_dev)[:, 0]
+
+    @torch.no_grad()
+    def density_grad_at(self, x01, sel, n_dev=None):
+        mlp, w16 = self.nets['geo_mlp']
+        a = self._aabb_host
+        return ops.field_grad_x(self.grid, mlp, x01, sel, w16, [1.0 / (a[3 + i] - a[i]) for i in range(3)], n_dev=n_dev)
 
     @torch.no_grad()
     def rgb_at(self, x01, sel, n_dev=None):

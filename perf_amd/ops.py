@@ -503,6 +503,33 @@ def field_infer(grid: GridConfig, mlp: MlpConfig, x01, sel, w16, n_dev=None, wan
     return (out, feat) if want_features else out
 
 
+def field_grad_x(grid: GridConfig, mlp: MlpConfig, x01, sel, w16, inv_extent=None, n_dev=None, want_sigma=True, out=None):
+    """Density and its spatial gradient in one kernel (perf_field_grad_x): -> (sigma [n] or None, grad [n,3]) with
+    grad = d(act(MLP(encode(x01)))[0] * sel) / dx in world units, inv_extent = the three factors 1 / (aabb_max - aabb_min) (None: 1,
+    the gradient w.r.t. x01).  w16 = the 16-bit working copy [MLP weights | table] (what field_infer takes); no gradient is recorded.
+    n_dev: rows at and beyond the device count are left untouched; out = (sigma, grad) buffers to write into."""
+    n = x01.shape[0]
+    n_net = mlp.n_params
+    if out is not None:
+        sigma, grad = out
+    else:
+        grad = torch.empty(n, 3, dtype=torch.float32, device=x01.device)
+        sigma = torch.empty(n, dtype=torch.float32, device=x01.device) if want_sigma else None
+    ie = None if inv_extent is None else (ctypes.c_float * 3)(*[float(v) for v in inv_extent])
+    gd, md = grid.desc(), mlp.desc()
+    _call('perf_field_grad_x', ctypes.byref(gd), ctypes.byref(md), _p(_f32(x01, 'x01')), _p(sel), _p(w16[n_net:]), _p(w16[:n_net]), ie,
+          _p(grad), _p(sigma), n, _nd(n_dev), dtype_code(w16.dtype), _stream())
+    return sigma, grad
+
+
+def normal_composite(weights, grad, packed):
+    """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
+    R = packed.shape[0]
+    out = torch.empty(R, 3, dtype=torch.float32, device=weights.device)
+    _call('perf_normal_composite', _p(_f32(weights, 'weights')), _p(_f32(grad, 'grad')), _p(packed), R, _p(out), _stream())
+    return out
+
+
 class IndexedFeat(NamedTuple):
     """Level-major features [L, n_src, 2] of MORE samples than the caller means, and the row of each sample it does mean
     (int32 [n]; rows past the live count are not read): what compact_prefix(index_features=True) hands to the gradient pass

@@ -39,6 +39,12 @@ class _VolumeRenderFn(torch.autograd.Function):
 volume_render = _VolumeRenderFn.apply
 
 
+def _check_normal_request(with_normal):
+    if with_normal and torch.is_grad_enabled():
+        raise RuntimeError("'normal' is an evaluation output: render it under torch.no_grad() (a loss on normals needs second-order "
+                           "terms through the hash table, which the gradient kernel does not record)")
+
+
 class NeRFOCCRenderer(nn.Module):
     def __init__(self, max_radius, bg_color):
         super().__init__()
@@ -99,8 +105,12 @@ class NeRFOCCRenderer(nn.Module):
                 st['rgbs'] = nerf.rgb_at(x01, sel, sm.n_dev)
         return st
 
-    def stage_composite(self, nerf: NGPNeRF, st, geo_inference=False, app_inference=False, rand=None):
+    def stage_composite(self, nerf: NGPNeRF, st, geo_inference=False, app_inference=False, rand=None, with_normal=False):
+        """with_normal (evaluation only): also 'normal' [R,3], the unit vector of sum_i w_i n_i with n_i = -grad sigma_i / |grad sigma_i|
+        over the kept samples and the weights 'rgb' uses (world frame, zero for rays without samples): two more launches
+        (NGPNeRF.density_grad_at, ops.normal_composite); without it the launches and every output are what they were."""
         rand = rand or {}
+        _check_normal_request(with_normal)
         n_rays = st['n_rays']
         x01, sel, packed = st['x01'], st['sel'], st['packed']
         dev = x01.device
@@ -142,22 +152,30 @@ class NeRFOCCRenderer(nn.Module):
             ops.render_finish_eval(opacities, distances, colors, n_dev)      # same arithmetic, one launch, in place
 
         # (capacity mode: per-sample arrays have sample_capacity rows, the first n_samples_dev of them are live)
-        return {'is_valid': True, 'rgb': colors, 'distance': distances, 'weights': weights, 'opacities': opacities,
-                'trans': trans, 't_starts': st['t_starts'], 't_ends': st['t_ends'], 'ray_indices': st['ray_indices'],
-                'packed_info': packed, 'n_samples_dev': n_dev, 'n_marched_dev': st.get('n_marched_dev')}
+        res = {'is_valid': True, 'rgb': colors, 'distance': distances, 'weights': weights, 'opacities': opacities,
+               'trans': trans, 't_starts': st['t_starts'], 't_ends': st['t_ends'], 'ray_indices': st['ray_indices'],
+               'packed_info': packed, 'n_samples_dev': n_dev, 'n_marched_dev': st.get('n_marched_dev')}
+        if with_normal:
+            _, grad_x = nerf.density_grad_at(x01, sel, n_dev)
+            res['normal'] = ops.normal_composite(weights, grad_x, packed)
+        return res
 
     def render(self, nerf: NGPNeRF, estimator: OccGridEstimator, rays_o, rays_d, near, far,
-               geo_inference=False, app_inference=False, rand=None):
+               geo_inference=False, app_inference=False, rand=None, with_normal=False):
         """`rand` (optional dict with 'jitter' [R], 'bg' [R,3], 'noise' [R,1]) injects the random draws of
         :152,:185,:193 for tests; by default they are drawn with torch.rand on the device in that order."""
         assert near.shape[-1] == 1 and len(near.shape) == 2
         n_rays = rays_o.shape[0]
         dev = rays_o.device
+        _check_normal_request(with_normal)
         st = self.stage_sample(nerf, estimator, rays_o, rays_d, rand)
         if st is None:
-            return {'is_valid': False, 'rgb': torch.zeros(n_rays, 3, device=dev), 'distance': torch.zeros(n_rays, 1, device=dev),
-                    'opacities': torch.zeros(n_rays, 1, device=dev)}
-        return self.stage_composite(nerf, st, geo_inference, app_inference, rand)
+            res = {'is_valid': False, 'rgb': torch.zeros(n_rays, 3, device=dev), 'distance': torch.zeros(n_rays, 1, device=dev),
+                   'opacities': torch.zeros(n_rays, 1, device=dev)}
+            if with_normal:
+                res['normal'] = torch.zeros(n_rays, 3, device=dev)
+            return res
+        return self.stage_composite(nerf, st, geo_inference, app_inference, rand, with_normal=with_normal)
 
 
 class NeRFPropRenderer(nn.Module):

@@ -136,6 +136,14 @@ def gen_pers_rays(pose, fov, res, device='cuda'):
     return Rays(o, d)
 
 
+def normals_to_camera(normal, pose):
+    """World-frame normals [..., 3] (the 'normal' query key) -> the frame of the camera at `pose` [4,4] (or its rotation [3,3]):
+    n_cam = R^T n, the inverse of what apply_rot (utils/camera_utils.py:44-46) does to the ray directions.  This is the frame
+    SupInfoPool.register_sup_info(normal=...) expects: its validity test takes the panorama's own un-rotated directions."""
+    rot = torch.as_tensor(pose, dtype=normal.dtype, device=normal.device)[:3, :3]
+    return torch.matmul(normal, rot)              # row vectors: n^T R = (R^T n)^T
+
+
 def default_train_conf():
     """configs/nerf.yaml:24-74"""
     opt = lambda i, p, a, l: SimpleNamespace(init_lr=i, peak_lr=p, peak_at=a, lr_alpha=l)
@@ -536,7 +544,10 @@ class NeRFScene:
         eval has no randomness, so the batch size does not change the result (tests/test_gpu_fullsize.py), only the launch
         overhead.  sync_free: every batch runs with capacity-sized sample arrays and device-side counts -- the host never
         waits for a sample count; ONE read-back at the end checks that no batch marched more samples than its capacity
-        (otherwise the capacity is raised and the panorama rendered again, so results never depend on it)."""
+        (otherwise the capacity is raised and the panorama rendered again, so results never depend on it).
+        query_keys: 'rgb', 'distance', 'opacities' and -- evaluation only -- 'normal': the unit vector of sum_i w_i n_i with
+        n_i = -grad sigma_i / |grad sigma_i| over the kept samples (world frame, [..., 3], zero for rays without samples; normals_to_camera
+        rotates it into a panorama's own frame)."""
         last_train = self.nerf.training
         self.set_eval()
         rays_o, rays_d = rays.collapse()
@@ -586,8 +597,10 @@ class NeRFScene:
                 cache.clear()
             cache[key] = (1e-2 * torch.ones([n, 1], device=rays_o.device), torch.ones([n, 1], device=rays_o.device))
         near, far = cache[key]
+        # ('normal': the density gradient composited with the colour's weights -- evaluation only, asked for by key)
+        kw = {'with_normal': True} if 'normal' in query_keys else {}
         res = self.renderer.render(self.nerf, self.estimator, rays_o, rays_d, near, far,
-                                   geo_inference=geo_inference, app_inference=app_inference, rand=rand)
+                                   geo_inference=geo_inference, app_inference=app_inference, rand=rand, **kw)
         if (res is None) or (not res['is_valid']):
             return res
         return {k: res.get(k) for k in list(query_keys) + ['is_valid']}
@@ -1378,7 +1391,7 @@ class NeRFScene:
         pose_dev = torch.eye(4, dtype=torch.float32, device=dev)
         o_buf = torch.empty(height, width, 3, dtype=torch.float32, device=dev)
         d_buf = torch.empty(height, width, 3, dtype=torch.float32, device=dev)
-        width_of = {'rgb': 3, 'distance': 1, 'opacities': 1}
+        width_of = {'rgb': 3, 'distance': 1, 'opacities': 1, 'normal': 3}
         # one batch per frame (config 4): the frame's results ARE the renderer's tensors (owned by the graph's pool: same addresses on
         # every replay) and the marched count is read where the renderer left it -- no copy nodes; several batches: gathered by copies
         single = n_batches == 1

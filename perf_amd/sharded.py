@@ -266,5 +266,11 @@ class LevelShardedNeRF:
     def rgb_at(self, x01, sel, n_dev=None):
         return self._field('app_mlp', x01, sel, n_dev)
 
+    def density_grad_at(self, x01, sel, n_dev=None):
+        """Refused: the gradient kernel (ops.field_grad_x) needs all levels of a sample's table on one device."""
+        raise NotImplementedError("'normal' is not available on the level-sharded field: the density-gradient kernel gathers every "
+                                  "level of a sample on one GPU, and this field's levels live on several (render normals from an "
+                                  "unsharded NGPNeRF / InferenceNeRF)")
+
     def sample_points(self, rays_o, rays_d, ray_indices, t_starts, t_ends):
         return ops.points_from_rays(rays_o, rays_d, ray_indices, t_starts, t_ends, self._aabb_host)

@@ -19,7 +19,9 @@ def render_dense(scene, pose_sampler, n_poses=180, height=512, width=1024, query
     dense: a DenseTravelPoseSampler, or the DensePoseFuture of DenseTravelPoseSampler.start(pose_sampler, n_poses) issued
     earlier (e.g. before the scene was trained): the 10,000-step tour annealing has then run beside the GPU work and the
     frame loop starts at once.  Without it the trajectory is started here and the frame graph is captured meanwhile.
-    height, width: the panorama's size (cam_type='pano'); fov (radians), res: the perspective frame's (any other cam_type)."""
+    height, width: the panorama's size (cam_type='pano'); fov (radians), res: the perspective frame's (any other cam_type).
+    query_keys: any of 'rgb', 'distance', 'opacities', 'normal' (world-frame unit normals from the density gradient, [H, W, 3]; two more
+    launches per batch, only when asked for)."""
     pano = cam_type == 'pano'
     if dense is None:
         dense = DenseTravelPoseSampler.start(pose_sampler, n_dense_poses=n_poses)

@@ -3,10 +3,10 @@
 frames of a 75-degree field of view that keep the trajectory's look-at rotation (--cam-type pers, the reference's
 gen_pers_rays branch), fp16 inference, reference-faithful variable-count sampling.
 
-  python tools/render_dense.py [--poses 600] [--geo-steps 300] [--app-steps 150] [--cam-type pers [--fov-deg 75] [--res 512]]
+  python tools/render_dense.py [--poses 600] [--geo-steps 300] [--app-steps 150] [--cam-type pers [--fov-deg 75] [--res 512]] [--normals]
 
 Frames are rendered back to back on the device (the reference writes PNGs and a video in between: host IO, out of
-scope); prints the camera, frames/s, rays/s, ray-samples/s actually evaluated, and a checksum of the frames."""
+scope); prints the camera, frames/s (--normals: also with the 'normal' query key, the two graphs alternated), rays/s, ray-samples/s actually evaluated, and a checksum of the frames."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -25,6 +25,7 @@ ap.add_argument('--batch', type=int, default=32768, help='rays per graph-capture
 ap.add_argument('--cam-type', choices=('pano', 'pers'), default='pano', help="the reference's render_dense(cam_type=...): 'pano' or a perspective frame")
 ap.add_argument('--fov-deg', type=float, default=75., help='field of view of the perspective frames (core_exp_runner.py:235)')
 ap.add_argument('--res', type=int, default=512, help='side of the square perspective frames (core_exp_runner.py:235)')
+ap.add_argument('--normals', action='store_true', help="also render ('rgb', 'distance', 'normal') frames and report frames/s with and without the key")
 args = ap.parse_args()
 
 torch.manual_seed(0); np.random.seed(0)
@@ -100,6 +101,32 @@ for p in poses[:60]:
     frame_eager(p)
 torch.cuda.synchronize()
 t_eager = (time.perf_counter() - t0) / 60
+normals = None
+if args.normals:
+    # the same trajectory with the 'normal' key, a graph of its own; the two graphs alternated twice so that both see the same box state
+    frame_n = scene.make_graphed_render(fh, fw, ('rgb', 'distance', 'normal'), batch_size=args.batch, fovy=None if pano else fov)
+    for p in poses[:3]:
+        frame_n(p)
+    torch.cuda.synchronize()
+    def timed(fn):
+        t0 = time.perf_counter()
+        for p in poses:
+            out = fn(p)
+        torch.cuda.synchronize()
+        return len(poses) / (time.perf_counter() - t0), out
+    fps = {'without': [], 'with': []}
+    for _ in range(2):
+        fps['without'].append(timed(frame)[0])
+        f, last_n = timed(frame_n)
+        fps['with'].append(f)
+    plain = frame(poses[-1])
+    nn = last_n['normal']
+    len_n = torch.linalg.vector_norm(nn, dim=-1)
+    normals = {'frames_per_s_without_normal': fps['without'], 'frames_per_s_with_normal': fps['with'],
+               'rgb_and_distance_equal_without_the_key': bool(torch.equal(plain['rgb'], last_n['rgb']) and torch.equal(plain['distance'], last_n['distance'])),
+               'last_frame_unit_or_zero': bool((((len_n - 1).abs() < 1e-5) | (len_n == 0)).all()),
+               'last_frame_rays_with_a_normal': float((len_n > 0).float().mean()),
+               'last_frame_mean_minus_dir_dot_normal': float((-(frame_rays(poses[-1]).d.reshape(-1, 3)) * nn.reshape(-1, 3)).sum(-1)[len_n.reshape(-1) > 0].mean())}
 from perf_amd.scene import Rays as _Rays
 # sample counts of every frame of the trajectory, rendered once more outside the timed loop: the samples whose density was
 # evaluated (the two-phase sampler's head samples + the tails of the rays still alive) and the samples kept by the visibility
@@ -126,5 +153,5 @@ print(json.dumps({'config': 'render_dense: %d poses, %dx%d %s frames in %d hipGr
                   'pose_sampler_host_s': t_sampler, 'pose_sampler_start_call_s': t_start_call, 'pose_sampler_wait_s': t_wait,
                   'wall_s_including_sampler': {'overlapped (started before training, as this tool does)': t + t_start_call + t_wait,
                                                'in line (round 2)': t + t_sampler},
-                  'last_frame_rgb_sum': checksum,
+                  'last_frame_rgb_sum': checksum, 'normals': normals,
                   'kernel_ms_one_frame': {k: round(n * ms, 3) for k, (n, ms) in sorted(kern.items(), key=lambda kv: -kv[1][0] * kv[1][1])}}, indent=1))

@@ -1317,24 +1317,41 @@ static int64_t plan_bitmaps(const GridParams& gp, int64_t n, TileParams* tp, int
     return (int64_t)rows * tp->bm_row_words * 4 + (int64_t)idx * tp->bm_blocks * 4;
 }
 
+// The ONE layout of a call's workspace: [replica slabs][shifts][tile codes][escape words][bitmaps][their escape words].  The size
+// query returns `total`; the call takes the offsets and decides from workspace_bytes / alignment which optional sections it uses (a
+// workspace WITHOUT room for the codes / bitmaps selects the position-streaming owners / the global-atomics scatter: how the tests
+// reach those paths).  n == 0 asks for the minimum: slabs and shifts.  bm_bytes == 0: no plan with bitmap levels on offer.
+struct BwdLayout { int64_t shifts_at, codes_at, esc_words, bits_at, bm_bytes, total; };
+
+static BwdLayout plan_layout(const GridParams& gp, int64_t n) {
+    BwdLayout L{};
+    TileParams tp; int nb, bm_levels = 0; int64_t w, slab_entries = 0;
+    const int bm_tiles = n < kMaxCodedSamples ? kBitmapMaxTiles : 0;
+    for (int plan = 0; plan < 4; ++plan) {      // slabs: the largest of the plans a call may pick (both modes, without / with bitmap levels)
+        plan_tiles(gp, (plan & 1) != 0, &tp, &nb, &w, (plan & 2) ? bm_tiles : 0);
+        if (w > slab_entries) slab_entries = w;
+    }
+    L.shifts_at = (slab_entries * (int64_t)sizeof(float2) + 15) & ~(int64_t)15;
+    L.codes_at = L.shifts_at + kShiftBytes;
+    L.esc_words = div_up(n, kCodeSamplesPerBlock);
+    // tp: the fixed-point plan with bitmap levels (tiles, code slots and bitmap rows are those of the fp32 plan: only the replicas differ)
+    int slots = plan_codes(gp, n, &tp);
+    if (n > 0 && tp.bitmap_levels) L.bm_bytes = plan_bitmaps(gp, n, &tp, &bm_levels);
+    if (L.bm_bytes > kBitmapMaxBytes) L.bm_bytes = 0;
+    if (tp.bitmap_levels && !L.bm_bytes) {      // no bitmaps: the call plans without them, and more levels take tile codes
+        plan_tiles(gp, true, &tp, &nb, &w, 0);
+        slots = plan_codes(gp, n, &tp);
+    }
+    const int64_t code_bytes = (int64_t)slots * tp.n_pad * 4 + (slots ? L.esc_words * 4 : 0);
+    L.bits_at = (L.codes_at + code_bytes + 15) & ~(int64_t)15;
+    L.total = slab_entries * (int64_t)sizeof(float2) + 16 + kShiftBytes + code_bytes + (L.bm_bytes ? L.bm_bytes + 16 : 0);
+    return L;
+}
+
 extern "C" int64_t perf_hashgrid_bwd_workspace_bytes(const perf_grid_desc* grid, int64_t n) {
     GridParams gp;
     if (fill_params(grid, &gp)) return -1;
-    TileParams tp; int nb; int64_t ws;
-    int64_t ws2;
-    plan_tiles(gp, false, &tp, &nb, &ws);
-    plan_tiles(gp, true, &tp, &nb, &ws2, (n > 0 && n < kMaxCodedSamples) ? kBitmapMaxTiles : 0);
-    if (n == 0) {       // (the minimal workspace -- no codes, no bitmaps -- must still hold the replica slabs of whatever plan a call picks)
-        TileParams t3; int nb3; int64_t ws3;
-        plan_tiles(gp, true, &t3, &nb3, &ws3, kBitmapMaxTiles);
-        if (ws3 > ws2) ws2 = ws3;
-    }
-    const int slots = plan_codes(gp, n, &tp);
-    int bm_levels = 0;
-    int64_t bm_bytes = plan_bitmaps(gp, n, &tp, &bm_levels);
-    if (bm_bytes > kBitmapMaxBytes) bm_bytes = 0;
-    return (ws > ws2 ? ws : ws2) * (int64_t)sizeof(float2) + 16 + kShiftBytes + (int64_t)slots * tp.n_pad * 4 +
-           (slots ? div_up(n, kCodeSamplesPerBlock) * 4 : 0) + (bm_bytes ? bm_bytes + 16 : 0);
+    return plan_layout(gp, n).total;
 }
 
 extern "C" int perf_hashgrid_bwd(const perf_grid_desc* grid, const float* x01, const float* dfeat,
@@ -1394,32 +1411,12 @@ int perf_internal_hashgrid_bwd(const perf_grid_desc* grid, const float* x01, con
     int n_blocks = 0;
     int64_t ws_entries = 0;
     const bool aligned_ws = (reinterpret_cast<uintptr_t>(workspace) & 15) == 0;
-    // workspace layout: [replica slabs (larger of both modes)][shifts][tile codes][escape words][bitmaps][their escape words]
-    // (a workspace WITHOUT room for the codes / bitmaps selects the position-streaming owners / the global-atomics scatter: how the
-    //  tests reach those paths)
-    const bool want_bitmaps = n > 0 && n < kMaxCodedSamples && aligned_ws;
-    int64_t slab_entries = 0;       // (the largest of the plans a call may end up with: the offsets below must not depend on the choice)
-    { TileParams t2; int nb2; int64_t w2;
-      plan_tiles(gp, fixed, &t2, &nb2, &w2); slab_entries = w2;
-      plan_tiles(gp, !fixed, &t2, &nb2, &w2); if (w2 > slab_entries) slab_entries = w2;
-      if (want_bitmaps) { plan_tiles(gp, fixed, &t2, &nb2, &w2, kBitmapMaxTiles); if (w2 > slab_entries) slab_entries = w2; } }
-    const int64_t shifts_at = (slab_entries * (int64_t)sizeof(float2) + 15) & ~(int64_t)15;
-    const int64_t codes_at = shifts_at + kShiftBytes;
-    const int64_t esc_words = div_up(n, kCodeSamplesPerBlock);
+    const BwdLayout lay = plan_layout(gp, n);
+    const int64_t shifts_at = lay.shifts_at, codes_at = lay.codes_at, esc_words = lay.esc_words, bits_at = lay.bits_at;
     // levels of 256..2048 tiles take LDS owners fed by per-tile bitmaps when the workspace holds the bitmaps, global atomics otherwise
-    int bitmap_tiles = 0, bm_levels = 0;
-    int64_t bits_at = 0, bm_bytes = 0;
-    if (want_bitmaps) {
-        TileParams t0; int nb0; int64_t w0;
-        plan_tiles(gp, fixed, &t0, &nb0, &w0, kBitmapMaxTiles);
-        if (t0.bitmap_levels) {
-            const int slots0 = plan_codes(gp, n, &t0);
-            bm_bytes = plan_bitmaps(gp, n, &t0, &bm_levels);
-            bits_at = (codes_at + (int64_t)slots0 * t0.n_pad * 4 + (slots0 ? esc_words * 4 : 0) + 15) & ~(int64_t)15;
-            if (bm_bytes <= kBitmapMaxBytes && workspace_bytes >= bits_at + bm_bytes) bitmap_tiles = kBitmapMaxTiles;
-        }
-    }
-    plan_tiles(gp, fixed, &tp, &n_blocks, &ws_entries, bitmap_tiles);
+    const bool use_bitmaps = aligned_ws && lay.bm_bytes && workspace_bytes >= bits_at + lay.bm_bytes;
+    int bm_levels = 0;
+    plan_tiles(gp, fixed, &tp, &n_blocks, &ws_entries, use_bitmaps ? kBitmapMaxTiles : 0);
     PERF_REQUIRE(!(raw_fields || shifts_dev) || tp.atomic_levels == 0u,
                  "perf_hashgrid_bwd: raw fields / given units are not available for levels on the global-atomics scatter (more than 2048 tiles, or no room for the per-tile bitmaps in the workspace)");
     tp.run_merge = 1;

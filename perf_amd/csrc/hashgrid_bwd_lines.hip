@@ -500,13 +500,15 @@ static int split_lines(const perf_grid_desc* grid, GridParams* gp, GridLocal* gl
     return P;
 }
 
-// bytes at the END of the workspace that the line-local owners take: [16][replica slabs][tile codes of n samples] (n = 0: without codes)
-static int64_t lines_tail_bytes(const GridParams& gp, const GridLocal& gl, int64_t n) {
+// the ONE layout of what the line-local owners take at the END of the workspace: [16][replica slabs][tile codes of n samples]
+struct LinesTail { int64_t owners, coded; };       // bytes without / with the tile codes (which start `owners` bytes into the tail)
+static LinesTail lines_tail(const GridParams& gp, const GridLocal& gl, int64_t n) {
     LinesPlan lp; int64_t slab = 0;
     plan_lines(gp, gl, true, true, &lp, &slab);
     int levels = 0;
     for (int l = 0; l < gp.n_levels; ++l) levels += (lp.owner_levels >> l) & 1u;
-    return 16 + ((slab * (int64_t)sizeof(float2) + 15) & ~(int64_t)15) + (int64_t)levels * ((n + 1) & ~(int64_t)1) * 8;
+    const int64_t owners = 16 + ((slab * (int64_t)sizeof(float2) + 15) & ~(int64_t)15);
+    return {owners, owners + (int64_t)levels * ((n + 1) & ~(int64_t)1) * 8};
 }
 
 // the padding in front of a line-local level (it starts on a super-block boundary) is part of the table: an overwriting call writes 0
@@ -526,7 +528,7 @@ extern "C" int64_t perf_hashgrid_bwd_lines_workspace_bytes(const perf_grid_desc*
     if (P < 0 || n < 0) return -1;
     int64_t a = 0;
     if (P > 0) { a = perf_hashgrid_bwd_workspace_bytes(&pre, n); if (a < 0) return -1; }
-    return ((a + 15) & ~(int64_t)15) + lines_tail_bytes(gp, gl, n);
+    return ((a + 15) & ~(int64_t)15) + lines_tail(gp, gl, n).coded;
 }
 
 extern "C" int perf_hashgrid_bwd_lines(const perf_grid_desc* grid, const float* x01, const float* dfeat, float* grad_table, int64_t n,
@@ -583,21 +585,20 @@ int perf_internal_hashgrid_bwd_lines(const perf_grid_desc* grid, const float* x0
     // workspace: [the prefix's (perf_hashgrid_bwd_workspace_bytes)][16][line-local replica slabs]; without room for the tail every
     // line-local level takes the global-atomics scatter (and the prefix gets the whole workspace)
     // (a workspace with room for the slabs but not for the tile codes selects the position-streaming owners)
-    const int64_t tail0 = lines_tail_bytes(gp, gl, 0), tail_n = lines_tail_bytes(gp, gl, n);
+    const LinesTail lt = lines_tail(gp, gl, n);
     int64_t pre_min = 0;
     if (P > 0) { pre_min = perf_hashgrid_bwd_workspace_bytes(&pre, 0); if (pre_min < 0) return PERF_E_INVALID; }
     pre_min = (pre_min + 15) & ~(int64_t)15;
     const bool aligned_ws = workspace && ((reinterpret_cast<uintptr_t>(workspace) & 15) == 0);
-    const bool coded = aligned_ws && n > 0 && workspace_bytes >= pre_min + tail_n;
-    const bool owners = aligned_ws && workspace_bytes >= pre_min + tail0;
-    const int64_t tail = coded ? tail_n : tail0;
-    const int64_t slab_at = owners ? ((workspace_bytes - tail) & ~(int64_t)15) : workspace_bytes;
+    const bool coded = aligned_ws && n > 0 && workspace_bytes >= pre_min + lt.coded;
+    const bool owners = aligned_ws && workspace_bytes >= pre_min + lt.owners;
+    const int64_t slab_at = owners ? ((workspace_bytes - (coded ? lt.coded : lt.owners)) & ~(int64_t)15) : workspace_bytes;
     float2* slabs = owners ? reinterpret_cast<float2*>(reinterpret_cast<char*>(workspace) + slab_at + 16) : nullptr;
     LinesPlan lp; int64_t slab_entries = 0;
     plan_lines(gp, gl, owners, true, &lp, &slab_entries);
     unsigned long long* codes = nullptr;
     if (coded) {
-        codes = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + slab_at + 16 + ((slab_entries * (int64_t)sizeof(float2) + 15) & ~(int64_t)15));
+        codes = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + slab_at + lt.owners);
         lp.n_pad = (n + 1) & ~(int64_t)1;
         int slot = 0;
         for (int l = 0; l < gp.n_levels; ++l) if ((lp.owner_levels >> l) & 1u) lp.code_slot[l] = slot++;

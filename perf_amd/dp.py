@@ -91,7 +91,6 @@ class ShardedExchange:
     kernels: an object with
         stats_pack(level_absmax, field_max_prev_or_None, n_dev, n, out)
         units(stats_all, world, shifts_out, n_total_out, margin_bits)  (applies the headroom feedback)
-        grid_bwd_raw(x01, dfeat, payload_view, n_dev, shifts)         (int32 fields into payload_view)
         unfix(shard, lo, hi, shifts, field_max_out, flag)             (in place int32 -> fp32)
         slot_pack(level_absmax, field_max, n_dev, n, flag, n_marched, capacity, rank, world, slots_out)
         slot_unpack(slots, world, stats_all_or_None, job_flags_out, n_total_out)

@@ -314,16 +314,34 @@ def hashgrid_bwd_redo(grid: GridConfig, x01, dfeat, out, n_dev=None, hr_state=No
     return out
 
 
-_FIELD_BWD_WS = {}
 FIELD_BWD_ONE_CALL = True       # False: the three entry points one by one (tools/shim_step_profile.py --three-calls: the A/B of the host cost)
 
 
+class Workspace:
+    """Grow-only holder of ONE float32 scratch block; its owner (a network: NetworkWithInputEncoding) takes the block with it."""
+
+    def __init__(self):
+        self.block = None
+
+    def get(self, nbytes, device):
+        """A block of at least nbytes.  Grown geometrically: the operator-shim path calls with a different exact n every step -- a
+        buffer per size would pin a pool of differently sized blocks and push the caching allocator into hipMalloc (measured: +0.3 ms
+        per step); any buffer that is large enough serves (the library lays it out from n)."""
+        ws = self.block
+        if ws is None or ws.numel() * 4 < nbytes or ws.device != device:
+            grown = max(nbytes, int(1.5 * ws.numel() * 4) if ws is not None else 0)
+            ws = torch.empty(grown // 4 + 4, dtype=torch.float32, device=device)
+            if not (ws.is_cuda and torch.cuda.is_current_stream_capturing()):   # (a block first made INSIDE a capture belongs to that graph's pool: not kept)
+                self.block = ws
+        return ws
+
+
 def field_bwd(grid: GridConfig, mlp: MlpConfig, x01, w16_net, feat16, dout, sel=None, fixed=True, redo=True, hr_state=None, n_dev=None,
-              grad=None, extra=0, book=None):
+              grad=None, extra=0, book=None, ws=None):
     """The whole backward of one field in ONE boundary call (perf_field_bwd: MLP backward -> grid backward -> predicated fp32 repair)
-    -> flat fp32 gradient [network | grid (+ `extra` trailing slots)].  feat16: [L, n, 2] or an IndexedFeat.  The workspace (MLP
-    partials, tile codes, dfeat) is cached per (device, grid, network) and grown on demand: consecutive backwards on one stream reuse
-    it -- do not overlap two backwards of the same field on different streams."""
+    -> flat fp32 gradient [network | grid (+ `extra` trailing slots)].  feat16: [L, n, 2] or an IndexedFeat.  ws (a Workspace): the
+    holder of the call's scratch memory (MLP partials, tile codes, dfeat), grown on demand: consecutive backwards on one stream reuse
+    it -- do not overlap two backwards with one holder on different streams.  ws=None: a block of this call's own."""
     index, stride = None, 0
     if isinstance(feat16, IndexedFeat):
         feat16, index = feat16.feat, feat16.index
@@ -347,18 +365,7 @@ def field_bwd(grid: GridConfig, mlp: MlpConfig, x01, w16_net, feat16, dout, sel=
     nbytes = _lib.load().perf_field_bwd_workspace_bytes(ctypes.byref(gd), ctypes.byref(md), n, None, None, None)
     if nbytes < 0:
         raise _lib.PerfError('perf_field_bwd_workspace_bytes: bad arguments')
-    # ONE workspace per (device, field), grown geometrically: the operator-shim path calls with a different exact n every step -- a
-    # buffer per size would pin a pool of differently sized blocks and push the caching allocator into hipMalloc (measured: +0.3 ms
-    # per step); any buffer that is large enough serves (the library lays it out from n)
-    key = (str(dev), id(gd), mlp.n_levels, mlp.n_hidden_layers, mlp.n_output_dims)
-    ws = _FIELD_BWD_WS.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        grown = max(nbytes, int(1.5 * ws.numel() * 4) if ws is not None else 0)
-        ws = torch.empty(grown // 4 + 4, dtype=torch.float32, device=dev)
-        if not torch.cuda.is_current_stream_capturing():       # (a block first made INSIDE a capture belongs to that graph's pool: not kept)
-            if len(_FIELD_BWD_WS) >= 16 and key not in _FIELD_BWD_WS:
-                _FIELD_BWD_WS.pop(next(iter(_FIELD_BWD_WS)))
-            _FIELD_BWD_WS[key] = ws
+    ws = (ws or Workspace()).get(nbytes, dev)
     if book is not None and fixed and redo and hr_state is not None and n > 0 and book.args['overflow'] is not None \
             and book.args['overflow'].data_ptr() == overflow_flag(dev).data_ptr():
         # book (a StepBook): the step's bookkeeping rides in the repair launch (perf_field_bwd_book) -- one launch per step fewer; the flag

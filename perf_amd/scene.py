@@ -384,7 +384,7 @@ class FusedAdam:
         self.refresh_lr()
         fixed = getattr(self.net, 'grid_grad_accum', 'fp32') == 'fixed'
         flag = ops.overflow_flag(p.device) if fixed else None
-        # (a flagged fixed-point gradient was repaired in place by the redo launch behind the backward, NeRFScene._field_grad:
+        # (a flagged fixed-point gradient was repaired in place by the redo launch behind the backward, tcnn.field_backward:
         #  the event is counted, the step is taken)
         rode = book is not None and book.done        # (the backward's repair launch did the bookkeeping: Adam consumes the flag)
         if not rode:
@@ -909,35 +909,6 @@ class NeRFScene:
         return torch.rand(n_local * world, cols, device=device)[rank * n_local:(rank + 1) * n_local].contiguous()
 
     # ---- fused steps: explicit kernel chain instead of autograd + ~25 tiny torch ops (same arithmetic) ----------
-    def _field_grad(self, net, x01, w16, feat, sel, dout, n_dev=None, extra=0, book=None):
-        """Flat gradient [network | grid] (+ `extra` trailing slots: the data-parallel path appends the sample count)."""
-        n_net = net.mlp.n_params
-        fixed = net.grid_grad_accum == 'fixed'
-        n_all = n_net + net.grid.n_params
-        if not fixed or net.redo_supported:
-            # ONE boundary call (perf_field_bwd): MLP backward -> grid backward -> the predicated fp32 repair launch that keeps a
-            # flagged fixed-point step from being dropped (a no-op dispatch otherwise)
-            grad = ops.field_bwd(net.grid, net.mlp, x01, w16[:n_net], feat, dout, sel, fixed=fixed, redo=True,
-                                 hr_state=net.headroom_state() if fixed else None, n_dev=n_dev, extra=extra, book=book)
-            if fixed and not self.fused_adam:
-                # torch.optim.Adam has no perf_step_bookkeeping behind it to consume the flag: left set, every later backward
-                # would run its (slow) fp32 repair as well
-                ops.overflow_flag(x01.device).zero_()
-            return grad
-        grad = torch.empty(n_all + extra, dtype=torch.float32, device=x01.device)
-        res = ops.mlp_bwd(net.mlp, w16[:n_net], feat, dout, sel, want_absmax=fixed, n_dev=n_dev, dw_out=grad[:n_net])
-        ops.hashgrid_bwd_into(net.grid, x01, res[0], grad[n_net:n_all], level_absmax=res[2] if fixed else None, n_dev=n_dev,
-                              hr_state=net.headroom_state() if fixed else None)
-        if fixed and net.redo_supported:
-            # never drop a step: should a fixed-point field have neared the int32 range (device flag), this predicated launch
-            # rewrites the table gradient with fp32 LDS accumulation; a no-op dispatch otherwise (perf_hashgrid_bwd, redo_flag)
-            ops.hashgrid_bwd_redo(net.grid, x01, res[0], grad[n_net:n_all], n_dev=n_dev, hr_state=net.headroom_state())
-            if not self.fused_adam:
-                # torch.optim.Adam has no perf_step_bookkeeping behind it to consume the flag: left set, every later backward
-                # would run its (slow) fp32 repair as well
-                ops.overflow_flag(x01.device).zero_()
-        return grad
-
     def _step_book(self, optimizer, dist_info, n_dev, n_marched):
         """Single process, sync-free mode, fused Adam: the step's bookkeeping as a block the backward's repair launch carries (the
         arguments _apply_grad hands optimizer.step); None otherwise."""
@@ -1052,6 +1023,30 @@ class NeRFScene:
         net.params.grad = None
         self._poll_health(net)
 
+    def _backward_and_step(self, net, optimizer, dist_info, st, w16, feat, dout, beside_stats=None, beside_grads=None):
+        """The tail of a fused step: backward of `net` (tcnn.field_backward) -> [gradient exchange] -> optimizer.  st: the sampler's
+        stage of this step; falsy: this rank has no sample at all (it still takes part in every collective: the collectives stay
+        matched across ranks).  beside_stats / beside_grads: callables run while the statistics all-gather (sharded mode) / the
+        gradient exchange are in flight."""
+        dp = dist_info[0] is not None
+        sharded = self._sharded(dist_info, optimizer)
+        if not st:
+            if sharded:
+                self._dp_sharded_step(net, optimizer, dist_info, None, None, None, None, None, None, None)
+            elif dp:                           # the count slot says "no samples here"
+                self._apply_grad(net, torch.zeros(net.params.numel() + self.DP_EXTRA, device=net.params.device), optimizer, dist_info, None, n_kept=0)
+            return
+        x01, sel, n_dev, n_marched = st['x01'], st['sel'], st['n_dev'], st['n_marched_dev']
+        if sharded:
+            self._dp_sharded_step(net, optimizer, dist_info, x01, w16, feat, sel, dout, n_dev, n_marched, early=beside_stats, late=beside_grads)
+            return
+        book = self._step_book(optimizer, dist_info, n_dev, n_marched)
+        # (torch.optim.Adam has no perf_step_bookkeeping behind it to consume the overflow flag)
+        grad = _tcnn.field_backward(net, x01, w16, feat, sel, dout, n_dev=n_dev, extra=self.DP_EXTRA if dp else 0, book=book,
+                                    consume_flag=not self.fused_adam)
+        self._apply_grad(net, grad, optimizer, dist_info, beside_grads if dp else None, n_kept=n_dev if n_dev is not None else x01.shape[0],
+                         n_marched=n_marched, book=book)
+
     def sync_params(self):
         """Sharded data parallelism keeps the fp32 master of a table slice only on its owner: refresh the replicas (one fp32
         all-gather per network; before checkpoints, after an episode).  No-op otherwise."""
@@ -1079,15 +1074,8 @@ class NeRFScene:
                                             with_rgb=not (self.skip_unused_color or (dist_info[0] is not None and self.overlap_comm)),
                                             keep_features=self.reuse_sampling_features and self.renderer.sample_capacity is not None)
         geo = self.nerf.geo_mlp
-        extra = self.DP_EXTRA if dist_info[0] is not None else 0
-        sharded = self._sharded(dist_info, optimizer)
-        if st is None or st is False:
-            if sharded:                        # keep the collectives matched across ranks: this rank contributes nothing
-                self._dp_sharded_step(geo, optimizer, dist_info, None, None, None, None, None, None, None)
-            elif dist_info[0] is not None:     # the count slot says "no samples here"
-                self._apply_grad(geo, torch.zeros(geo.params.numel() + self.DP_EXTRA, device=geo.params.device), optimizer, dist_info, None, n_kept=0)
-            self.global_iter_step_geo += 1
-            return
+        if not st:                             # (None, or False from the prefetch: no samples on this rank)
+            return self._backward_and_step(geo, optimizer, dist_info, None, None, None, None)
         x01, sel, packed, ts, te, n_dev = st['x01'], st['sel'], st['packed'], st['t_starts'], st['t_ends'], st['n_dev']
         self._last_counts = (st['n_marched_dev'], n_dev)
         n_net = geo.mlp.n_params
@@ -1129,35 +1117,23 @@ class NeRFScene:
         def prefetch_now():
             self._geo_pre = self._geo_prefetch(sup_pool, rand_in, generator)
 
-        if sharded:
-            # What runs beside the 26.6 MB reduce-scatter of the gradient fields: the deferred colour render (an encode + MLP +
-            # accumulation that feed no loss term of this step: ~0.2 ms of compute at 1 M samples) and the next step's batch
-            # draw.  Exact units: the colour render hides the statistics all-gather instead (it sits on the critical path there).
-            want_prefetch = self.overlap_comm and prefetch_next and not self._capturing
-            exact = self.dp_units == 'exact'
+        # What runs beside the gradient exchange (sharded: the 26.6 MB reduce-scatter of the gradient fields; else the all-reduce): the
+        # deferred colour render (an encode + MLP + accumulation that feed no loss term of this step: ~0.2 ms of compute at 1 M
+        # samples) and the next step's batch draw.  Sharded with exact units: the colour render hides the statistics all-gather
+        # instead (it sits on the critical path there).
+        sharded = self._sharded(dist_info, optimizer)
+        exact = sharded and self.dp_units == 'exact'
+        want_prefetch = self.overlap_comm and prefetch_next and not (sharded and self._capturing)
 
-            def beside_reduce_scatter():
-                if defer_color and not exact:
-                    color_now()
-                if want_prefetch:
-                    prefetch_now()
-            self._dp_sharded_step(geo, optimizer, dist_info, x01, w16, feat, sel, dsig.view(-1, 1), n_dev, st['n_marched_dev'],
-                                  early=color_now if (defer_color and exact) else None,
-                                  late=beside_reduce_scatter if ((defer_color and not exact) or want_prefetch) else None)
-            self.global_iter_step_geo += 1
-            return
-        book = self._step_book(optimizer, dist_info, n_dev, st['n_marched_dev'])
-        grad = self._field_grad(geo, x01, w16, feat, sel, dsig.view(-1, 1), n_dev=n_dev, extra=extra, book=book)
-        overlap = None
-        if self.overlap_comm and dist_info[0] is not None:
-            def overlap():
-                if defer_color:
-                    color_now()
-                if prefetch_next:
-                    prefetch_now()
-        self._apply_grad(geo, grad, optimizer, dist_info, overlap, n_kept=n_dev if n_dev is not None else x01.shape[0],
-                         n_marched=st['n_marched_dev'], book=book)
-        self.global_iter_step_geo += 1
+        def beside_grads():
+            if defer_color and not exact:
+                color_now()
+            if want_prefetch:
+                prefetch_now()
+        # (a callable makes the collective asynchronous: the sharded exchange gets one only when there is something to run)
+        busy = self.overlap_comm and dist_info[0] is not None and (not sharded or (defer_color and not exact) or want_prefetch)
+        self._backward_and_step(geo, optimizer, dist_info, st, w16, feat, dsig.view(-1, 1),
+                                beside_stats=color_now if (defer_color and exact) else None, beside_grads=beside_grads if busy else None)
 
     @torch.no_grad()
     def _app_step_fused(self, optimizer, sup_pool, progress, rand, generator):
@@ -1171,15 +1147,8 @@ class NeRFScene:
             rays, gt_colors, gt_depths, bs, dist_info = self._batch(sup_pool, generator)
         st = self.renderer.stage_sample(self.nerf, self.estimator, rays.o, rays.d, rand)
         app = self.nerf.app_mlp
-        extra = self.DP_EXTRA if dist_info[0] is not None else 0
-        sharded = self._sharded(dist_info, optimizer)
         if st is None:
-            if sharded:
-                self._dp_sharded_step(app, optimizer, dist_info, None, None, None, None, None, None, None)
-            elif dist_info[0] is not None:
-                self._apply_grad(app, torch.zeros(app.params.numel() + self.DP_EXTRA, device=app.params.device), optimizer, dist_info, None, n_kept=0)
-            self.global_iter_step_app += 1
-            return
+            return self._backward_and_step(app, optimizer, dist_info, None, None, None, None)
         x01, sel, packed, ts, te, n_dev = st['x01'], st['sel'], st['packed'], st['t_starts'], st['t_ends'], st['n_dev']
         self._last_counts = (st['n_marched_dev'], n_dev)
         sig = st['sig0'] if st['sig0'] is not None else self.nerf.density_at(x01, sel, n_dev)
@@ -1199,15 +1168,7 @@ class NeRFScene:
         hd = ops.train_head_app(sig.reshape(-1).contiguous(), rgbs, ts, te, packed, bg, gt_colors, bs, tc.color_loss_weight, self.loss_scale)
         drgb = hd['d_rgb']
         self.last_losses['color_loss'] = lambda t=hd['color_terms'], s=1.0 / (3 * bs): t.sum() * s
-        if sharded:
-            self._dp_sharded_step(app, optimizer, dist_info, x01, w16, feat, sel, drgb, n_dev, st['n_marched_dev'])
-            self.global_iter_step_app += 1
-            return
-        book = self._step_book(optimizer, dist_info, n_dev, st['n_marched_dev'])
-        grad = self._field_grad(app, x01, w16, feat, sel, drgb, n_dev=n_dev, extra=extra, book=book)
-        self._apply_grad(app, grad, optimizer, dist_info, None, n_kept=n_dev if n_dev is not None else x01.shape[0],
-                         n_marched=st['n_marched_dev'], book=book)
-        self.global_iter_step_app += 1
+        self._backward_and_step(app, optimizer, dist_info, st, w16, feat, drgb)
 
     def _can_fuse(self):
         tc = self.train_conf
@@ -1215,7 +1176,9 @@ class NeRFScene:
 
     def train_one_step_geo(self, optimizer, sup_pool, progress, rand=None, generator=None, prefetch_next=True):
         if self._can_fuse():
-            return self._geo_step_fused(optimizer, sup_pool, progress, rand, generator, prefetch_next)
+            self._geo_step_fused(optimizer, sup_pool, progress, rand, generator, prefetch_next)
+            self.global_iter_step_geo += 1
+            return
         tc = self.train_conf
         optimizer.zero_grad()
         pre = getattr(self, '_geo_pre', None) or self._geo_prefetch(sup_pool, rand, generator)
@@ -1257,7 +1220,9 @@ class NeRFScene:
 
     def train_one_step_app(self, optimizer, sup_pool, progress, rand=None, generator=None):
         if self.fused_steps and self.train_conf.color_loss_weight > 1e-7:
-            return self._app_step_fused(optimizer, sup_pool, progress, rand, generator)
+            self._app_step_fused(optimizer, sup_pool, progress, rand, generator)
+            self.global_iter_step_app += 1
+            return
         tc = self.train_conf
         optimizer.zero_grad()
         rays, gt_colors, gt_depths, bs, dist_info = self._batch(sup_pool, generator)
@@ -1346,8 +1311,10 @@ class NeRFScene:
             self.graph_nodes[kind] = _graph_node_count(graph)
             graph.instantiate()
 
+        # bwd_ws: the backward workspace the captured launches were recorded with -- the network's holder may grow past it (an eager
+        # step with more samples), and the block must not go back to the allocator while the graph can still be replayed
         state = {'graph': graph, 'n': 0, 'counts': self._last_counts, 'capacity': self.renderer.sample_capacity,
-                 'mode': optimizer.net.grid_grad_accum}
+                 'mode': optimizer.net.grid_grad_accum, 'bwd_ws': optimizer.net.bwd_workspace.block}
 
         def replay(lr=None, progress=None):
             if optimizer.sched_table is None:                    # no device-side schedule: refresh the two scalars

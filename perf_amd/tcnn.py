@@ -78,7 +78,7 @@ class _FieldFn(torch.autograd.Function):
         x01, w16, feat, sel = ctx.saved_tensors
         module = ctx.module
         sel = sel if ctx.has_sel else None
-        return None, _field_backward(module, x01, w16, feat, sel, dout, n_dev=ctx.n_dev, clear_flag=True), None, None, None
+        return None, field_backward(module, x01, w16, feat, sel, dout, n_dev=ctx.n_dev, consume_flag=True), None, None, None
 
 
 def field_apply(module, x01, params, sel=None, n_dev=None):
@@ -89,35 +89,35 @@ def field_apply(module, x01, params, sel=None, n_dev=None):
     return _FieldFn.apply(x01, params, sel, module, n_dev)
 
 
-def _field_backward(module, x01, w16, feat, sel, dout, n_dev=None, clear_flag=False):
-    """Flat gradient [network | grid] of one field.  Fixed-point accumulation never costs a step: should a field of the
-    grid gradient near the int32 range (device flag), the predicated repair launch right behind the backward rewrites the
-    table gradient with fp32 LDS accumulation -- a no-op dispatch otherwise; the host is not asked (no read-back per
-    backward, capturable).  clear_flag: the autograd (shim) path has no perf_step_bookkeeping behind it to consume the flag."""
+def field_backward(module, x01, w16, feat, sel, dout, n_dev=None, extra=0, book=None, consume_flag=False):
+    """Flat fp32 gradient [network | grid (+ `extra` trailing slots)] of one field: THE sequence of a field's backward, for the autograd
+    Functions and the fused steps alike.  Fixed-point accumulation never costs a step: should a field of the grid gradient near the
+    int32 range (device flag), the predicated repair launch right behind the backward rewrites the table gradient with fp32 LDS
+    accumulation -- a no-op dispatch otherwise; the host is not asked (no read-back per backward, capturable).  book (a StepBook):
+    the step's bookkeeping rides in the repair launch.  consume_flag: the caller has no perf_step_bookkeeping behind it to consume
+    the flag (autograd, torch.optim.Adam) -- left set, every later backward would run its (slow) fp32 repair as well."""
     n_net = module.mlp.n_params
     fixed = module.grid_grad_accum == 'fixed'
+    dout = dout.contiguous().float()
+    hr_state = module.headroom_state() if fixed else None
     if not fixed or module.redo_supported:
-        # ONE boundary call: MLP backward -> grid backward -> predicated repair launch (perf_field_bwd), cached workspace
-        grad = ops.field_bwd(module.grid, module.mlp, x01, w16[:n_net], feat, dout.contiguous().float(), sel, fixed=fixed, redo=True,
-                             hr_state=module.headroom_state() if fixed else None, n_dev=n_dev)
-        if fixed and clear_flag:
+        # ONE boundary call: MLP backward -> grid backward -> predicated repair launch (perf_field_bwd), the network's own workspace
+        grad = ops.field_bwd(module.grid, module.mlp, x01, w16[:n_net], feat, dout, sel, fixed=fixed, redo=True, hr_state=hr_state,
+                             n_dev=n_dev, extra=extra, book=book, ws=module.bwd_workspace)
+        if fixed and consume_flag:
             ops.overflow_flag(x01.device).zero_()
         return grad
-    grad = torch.empty(n_net + module.grid.n_params, dtype=torch.float32, device=x01.device)
-    res = ops.mlp_bwd(module.mlp, w16[:n_net], feat, dout.contiguous().float(), sel, want_absmax=fixed, n_dev=n_dev, dw_out=grad[:n_net])
-    ops.hashgrid_bwd_into(module.grid, x01, res[0], grad[n_net:], level_absmax=res[2] if fixed else None, n_dev=n_dev,
-                          hr_state=module.headroom_state() if fixed else None)
-    if fixed:
-        if module.redo_supported:
-            ops.hashgrid_bwd_redo(module.grid, x01, res[0], grad[n_net:], n_dev=n_dev, hr_state=module.headroom_state())
-            if clear_flag:
-                ops.overflow_flag(x01.device).zero_()
-        elif clear_flag and not torch.cuda.is_current_stream_capturing():
-            # (grids with levels beyond LDS owners -- BASELINE config 5 -- have no repair launch: ask the host, redo in fp32)
-            flag = ops.overflow_flag(x01.device)
-            if bool(int(flag.item())):
-                flag.zero_()
-                ops.hashgrid_bwd_into(module.grid, x01, res[0], grad[n_net:], level_absmax=None, n_dev=n_dev)
+    # (grids with levels beyond LDS owners -- BASELINE config 5 -- have no repair launch: a raised flag is the caller's; one with
+    #  nothing behind it to consume the flag asks the host and redoes the table gradient in fp32)
+    n_all = n_net + module.grid.n_params
+    grad = torch.empty(n_all + extra, dtype=torch.float32, device=x01.device)
+    res = ops.mlp_bwd(module.mlp, w16[:n_net], feat, dout, sel, want_absmax=True, n_dev=n_dev, dw_out=grad[:n_net])
+    ops.hashgrid_bwd_into(module.grid, x01, res[0], grad[n_net:n_all], level_absmax=res[2], n_dev=n_dev, hr_state=hr_state)
+    if consume_flag and not torch.cuda.is_current_stream_capturing():
+        flag = ops.overflow_flag(x01.device)
+        if bool(int(flag.item())):
+            flag.zero_()
+            ops.hashgrid_bwd_into(module.grid, x01, res[0], grad[n_net:n_all], level_absmax=None, n_dev=n_dev)
     return grad
 
 
@@ -144,9 +144,9 @@ class _DualFieldFn(torch.autograd.Function):
         sel = sel if ctx.has_sel else None
         ga = gb = None
         if ctx.needs_input_grad[1] and da is not None:
-            ga = _field_backward(ctx.mods[0], x01, wa, fa, sel, da, clear_flag=True)
+            ga = field_backward(ctx.mods[0], x01, wa, fa, sel, da, consume_flag=True)
         if ctx.needs_input_grad[2] and db is not None:
-            gb = _field_backward(ctx.mods[1], x01, wb, fb, sel, db, clear_flag=True)
+            gb = field_backward(ctx.mods[1], x01, wb, fb, sel, db, consume_flag=True)
         return None, ga, gb, None, None, None
 
 
@@ -178,6 +178,7 @@ class NetworkWithInputEncoding(nn.Module):
         self._hr_state = ops.headroom_state(self.params.device)     # (plain attribute; NeRFScene.state_dict() carries it)
         self.grid_grad_accum = GRID_GRAD_ACCUM                      # this module's accumulation mode ('fixed' | 'fp32')
         self.redo_supported = ops.hashgrid_bwd_redo_supported(self.grid)
+        self.bwd_workspace = ops.Workspace()        # scratch memory of field_backward (plain attribute: dropped with the network)
 
     # -- 16-bit working copy, refreshed when the fp32 master changes -------------------------------
     def working_copy(self, params=None):

@@ -200,6 +200,66 @@ def test_graph_replay_of_the_variable_count_step_equals_eager():
     assert ce[3] <= 1024 * 128 and ce[4] == 0 and ce[5] == 0, ce             # largest batch; nothing skipped
 
 
+def test_graph_replay_keeps_the_backward_workspace_it_was_captured_with():
+    """The network's backward workspace (tcnn.field_backward, ops.Workspace) is grow-only: an eager backward with more samples than
+    any before replaces the block.  A captured step has the OLD block's address baked in, so the replay's state keeps that block
+    alive: after the growth the holder has a new block, the replay still holds the captured one, and replays + eager steps around
+    the growth give the parameters of an uninterrupted eager run, bit for bit."""
+    from perf_amd import ops, tcnn
+    from perf_amd.scene import Rays
+    results = {}
+    for mode in ('eager', 'graph'):
+        scene, pool, rays, dist, rgb = _room_scene(train_steps=40, batch=1024)
+        g = torch.Generator(device='cuda'); g.manual_seed(5)
+        B = 1024
+        idx = torch.randint(0, len(pool), (B,), device='cuda', generator=g)
+        pool.rand_ray_color_data = lambda bs, **kw: (Rays(pool.all_sup_rays.o[idx], pool.all_sup_rays.d[idx]), pool.all_sup_colors[idx],
+                                                      pool.all_sup_distances[idx], pool.all_sup_normals[idx])
+        rand = {'jitter': torch.rand(B, device='cuda', generator=g), 'noise': torch.rand(B, 1, device='cuda', generator=g),
+                'bg': torch.rand(B, 3, device='cuda', generator=g)}
+        scene.renderer.sample_capacity = B * 128
+        net = scene.nerf.geo_mlp
+        opt = scene.make_optimizer(net, 0.0)
+        conf = scene.train_conf.geo_optimizer
+        orig = scene.train_one_step_geo
+        step = lambda o_, p_, progress, **kw: orig(o_, p_, progress=progress, rand=rand)
+        if mode == 'eager':
+            for i in range(6):
+                scene.update_lr(opt, conf, 0.1)
+                step(opt, pool, progress=0.5)
+        else:
+            scene.train_one_step_geo = step
+            scene.update_lr(opt, conf, 0.1)
+            step(opt, pool, progress=0.5)                       # step 1 eagerly: the block exists before the capture, the holder's own
+            replay = scene.make_graphed_step('geo', opt, pool, warmup=0)
+            block = net.bwd_workspace.block
+            ptr = block.data_ptr()
+            assert replay.state['bwd_ws'] is block and replay.state['bwd_ws'].data_ptr() == ptr
+            for i in range(2):
+                replay(scene.lr_at(conf, 0.1), 0.5)
+            # one eager backward with twice the capacity's samples: the holder has to grow (the headroom feedback it applies is taken
+            # back: this backward is not part of the run that is compared)
+            n = 2 * B * 128
+            x = torch.rand(n, 3, device='cuda', generator=g)
+            w16 = net.working_copy()
+            feat = ops.hashgrid_fwd(net.grid, x, w16[net.mlp.n_params:])
+            hr = net.headroom_state().clone()
+            grad = tcnn.field_backward(net, x, w16, feat, None, torch.randn(n, 1, device='cuda', generator=g) * 1e-3, consume_flag=True)
+            net.headroom_state().copy_(hr)
+            torch.cuda.synchronize()
+            assert bool(torch.isfinite(grad).all())
+            assert net.bwd_workspace.block is not block and net.bwd_workspace.block.numel() > block.numel()
+            assert replay.state['bwd_ws'] is block and block.data_ptr() == ptr and net.bwd_workspace.block.data_ptr() != ptr
+            for i in range(2):
+                replay(scene.lr_at(conf, 0.1), 0.5)
+            scene.update_lr(opt, conf, 0.1)
+            step(opt, pool, progress=0.5)                       # ... and an eager step on the grown block
+        results[mode] = (net.params.detach().clone(), opt.exp_avg.clone(), int(opt.step_count))
+    pe, me, se = results['eager']; pg, mg, sg = results['graph']
+    assert se == sg == 6
+    assert torch.equal(pe, pg) and torch.equal(me, mg)
+
+
 def test_adam_gate_skips_a_batch_without_samples(ops):
     """perf_adam_step_dev with a zero gate leaves parameters, moments and (through perf_step_bookkeeping) the step count
     untouched -- the reference returns before optimizer.step() when a batch has no samples (nerf.py:204-206)."""

@@ -940,12 +940,14 @@ def test_hashgrid_bwd_bitmap_owners_equal_the_atomics_scatter(ops):
     bitmaps and what runs without them (64-bit fixed-point global atomics; code-streaming owners up to 64 dense tiles) add up the same integers -- bit-identical tables, for ragged sizes, ray-ordered samples, a live count
     below the capacity and positions outside the unit cube (which send a level back to the generic owners)."""
     g = torch.Generator().manual_seed(43)
-    for log2_t, n_levels, n, kind, live, base in ((22, 5, 5003, 'uniform', None, 64), (23, 6, 40000, 'rays', None, 64), (24, 4, 20001, 'uniform', 12345, 64),
-                                                  (22, 5, 9000, 'outside', None, 64), (25, 3, 70000, 'rays', None, 64), (22, 3, 30000, 'rays', None, 96),
-                                                  (22, 3, 8000, 'outside', 7000, 96)):
+    for log2_t, n_levels, n, kind, live, base, scale in ((22, 5, 5003, 'uniform', None, 64, 2.0), (23, 6, 40000, 'rays', None, 64, 2.0),
+                                                         (24, 4, 20001, 'uniform', 12345, 64, 2.0), (22, 5, 9000, 'outside', None, 64, 2.0),
+                                                         (25, 3, 70000, 'rays', None, 64, 2.0), (22, 3, 30000, 'rays', None, 96, 2.0),
+                                                         (22, 3, 8000, 'outside', 7000, 96, 2.0), (20, 4, 4096, 'uniform', None, 32, 1.3819)):
         # (base 64: 16 dense tiles with codes, 128 dense tiles, then hashed levels of 256-2048 tiles; base 96: 64 dense tiles --
-        #  bitmaps against the code-streaming dense owners)
-        cfg = _grid_cfg(n_levels=n_levels, log2_hashmap_size=log2_t, base_resolution=base, per_level_scale=2.0)
+        #  bitmaps against the code-streaming dense owners; base 32 / 1.3819: four dense levels whose largest replica slabs belong to
+        #  the plan WITHOUT bitmap levels -- the reported workspace holds them, and its last level's 64 tiles take the bitmap owners)
+        cfg = _grid_cfg(n_levels=n_levels, log2_hashmap_size=log2_t, base_resolution=base, per_level_scale=scale)
         if kind == 'rays':
             R = n // 128 + 1
             d = torch.nn.functional.normalize(torch.randn(R, 3, generator=g), dim=-1)

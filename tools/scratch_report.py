@@ -2,7 +2,7 @@
 """Which kernels of libperf_hip.so carry scratch (private segment) and how many vector registers they take: compiles every unit of
 perf_amd/csrc with the build's flags + -save-temps into a temporary directory and reads the kernel descriptors of the gfx950 assembly
 (no GPU needed).  `python tools/scratch_report.py [out.json]`."""
-import glob, json, os, re, shutil, subprocess, sys, tempfile
+import argparse, glob, json, os, re, shutil, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -10,6 +10,9 @@ from perf_amd import build as B
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('out', nargs='?', help='also write the report (JSON) to this file')
+    args = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix='perf_scratch_')
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     procs = []
@@ -32,8 +35,8 @@ def main():
     shutil.rmtree(tmp, ignore_errors=True)
     txt = json.dumps(rep, indent=1)
     print(txt)
-    if len(sys.argv) > 1:
-        open(sys.argv[1], 'w').write(txt + '\n')
+    if args.out:
+        open(args.out, 'w').write(txt + '\n')
 
 
 if __name__ == '__main__':

@@ -297,6 +297,147 @@ def hashgrid_encode(x: torch.Tensor, table: torch.Tensor, lv: GridLevels,
     return (w[..., None] * vals).sum(2).reshape(N, lv.n_levels * lv.n_feat)
 
 
+# --------------------------------------------------------------------------------------
+# the fixed-point table gradient as INTEGERS (perf_amd/csrc/hashgrid_bwd.hip, hashgrid_bwd_lines.hip, grid_fixed_point.hpp)
+# --------------------------------------------------------------------------------------
+PAIR_PATH_MAX_CELL_X = 16384 - 1     # hashgrid_bwd.hip: kTileEntries - 1 (bwd_apply: `gx < kTileEntries - 1` takes apply_pairs)
+
+
+def grid_fixed_weights(x: np.ndarray, lv: GridLevels, level: int, interpolation: str = 'Linear'):
+    """(idx u32 [N,8], w f32 [N,8]): the corner entries of one level and the fp32 interpolation weights AS THE GRADIENT KERNELS FORM
+    THEM.  The fraction is grid_corner_indices' (one fma); Smoothstep is applied to it in fp32 first, (f*f) * (3 - 2f).  The
+    association of the three-factor product is part of the specification -- it decides the last bit of w, hence which way a
+    contribution of x.5 units rounds -- and is stated HERE, once per level class:
+
+      * hashed levels of the tcnn layout, cells with gx + 1 < 16384 (any grid this project trains: res + 2 < 16384):
+            w = wx * (wy * wz)         hashgrid_bwd.hip:191-193 (apply_pairs: the (y,z) product is shared by the two x corners),
+                                       restated by the fixed-point atomics scatter at :1115-1124
+      * the same levels' cells with gx + 1 >= 16384 (finer hashed levels; positions left of the unit cube, gx = -1 as uint32):
+            w = (wx * wy) * wz         hashgrid_bwd.hip:292 (bwd_apply's generic corner loop)
+      * dense levels of the tcnn layout:
+            w = (wx * wy) * wz         hashgrid_bwd.hip:223 (apply_pairs_dense), :292 (bwd_apply), :814 (run_apply)
+      * line-local levels (both line layouts, dense or hashed):
+            w = (wx * wy) * wz         grid_device.hpp:162 (corner_weights, used by hashgrid_bwd_lines.hip line_apply and its scatter)
+
+    The switch INSIDE a hashed level (res + 2 >= 16384) is restated, not avoided: the rule is per sample, on the cell's x."""
+    xn = np.ascontiguousarray(x, F32)
+    idx, f = grid_corner_indices(xn, lv, level)
+    if interpolation == 'Smoothstep':
+        f = ((f * f).astype(F32) * (F32(3.0) - (F32(2.0) * f).astype(F32)).astype(F32)).astype(F32)
+    else:
+        assert interpolation == 'Linear'
+    one = (F32(1.0) - f).astype(F32)
+    local = lv.local is not None and bool(lv.local[level])
+    pair = np.zeros(xn.shape[0], bool)
+    if bool(lv.hashed[level]) and not local:
+        gx = np.floor(grid_pos(xn[:, 0], lv.scale[level])).astype(np.int64) & U32_MASK
+        pair = gx < PAIR_PATH_MAX_CELL_X
+    w = np.zeros((xn.shape[0], 8), F32)
+    for c in range(8):
+        wx = f[:, 0] if (c & 1) else one[:, 0]
+        wy = f[:, 1] if (c & 2) else one[:, 1]
+        wz = f[:, 2] if (c & 4) else one[:, 2]
+        generic = ((wx * wy).astype(F32) * wz).astype(F32)
+        paired = (wx * (wy * wz).astype(F32)).astype(F32)
+        w[:, c] = np.where(pair, paired, generic)
+    return idx, w
+
+
+def fold_overlap_copies(table: np.ndarray, lv: GridLevels) -> np.ndarray:
+    """layout='line_overlap', in place on a [total, F] array of GRADIENTS: the two storage copies of a shared vertex (position 3 of a
+    run, position 0 of the next run of the same super-block row) both receive the sum of the two (hashgrid_bwd_lines.hip:overlap_twin).
+    Integer arrays fold as integers."""
+    assert lv.layout == 'line_overlap'
+    runs = 1 << (lv.sb_shift[0] - 2)
+    for l in range(lv.n_levels):
+        if not lv.local[l]:
+            continue
+        lo, n = int(lv.offset[l]), int(lv.size[l])
+        v = table[lo:lo + n].reshape(n // (32 * runs), runs, 8, 4, -1)
+        s = v[:, :-1, :, 3] + v[:, 1:, :, 0]
+        v[:, :-1, :, 3] = s
+        v[:, 1:, :, 0] = s
+    return table
+
+
+def grid_fixed_fields(x, dfeat, lv: GridLevels, shifts, interpolation: str = 'Linear', n_live=None, weights=None, workers: int = 8) -> np.ndarray:
+    """The fixed-point table gradient as the integers the kernels add up: int64 [total, 2].
+
+    x [N,3] f32, dfeat [L,N,2] f32, shifts [>= L] ints (one unit of level l = 2^-shifts[l]).  Every (live sample, level, corner, feature)
+    contributes  rint(fl32(w * g) * 2^shift)  -- ties to even, __float2int_rn -- with w from grid_fixed_weights (fp32, the association
+    named there).  The kernels form fl32(w * fl32(g * 2^shift)) or fl32(fl32(w * g) * 2^shift): the same number, a power of two
+    commuting with the rounding, as long as nothing underflows fp32 (|w g| >= 2^-126 or 0) and |g| 2^shift < 2^31.
+    Integer sums do not depend on order, replica or rank: one np.bincount per (level, corner, feature) with integer-valued float64
+    weights is exact (|sum| < 2^53).  'line_overlap': the two copies of a shared vertex are folded (fold_overlap_copies).
+    The kernels hold a field in an int32 that wraps; this oracle does not wrap -- a caller that means to compare keeps |field| < 2^31.
+    weights (optional): [grid_fixed_weights(x, lv, l, interpolation) for l in levels] of the SAME x, for a caller that asks for several
+    units or live counts of one batch (they are most of the cost); workers: levels are independent and are computed by that many
+    threads (numpy releases the interpreter lock in the passes that matter).  Neither changes a number -- every level is the same plain
+    per-level loop below, integer sums do not depend on who adds them -- and both exist for ONE caller: the benchmark batch of 2^20
+    samples x 16 levels, several units and live counts of it, inside a test that has to stay a few seconds long."""
+    xn = np.ascontiguousarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, F32)
+    dn = np.ascontiguousarray(dfeat.detach().cpu().numpy() if isinstance(dfeat, torch.Tensor) else dfeat, F32)
+    n_live = xn.shape[0] if n_live is None else int(n_live)
+    assert dn.shape == (lv.n_levels, xn.shape[0], 2) and 0 <= n_live <= xn.shape[0]
+    out = np.zeros((lv.total, 2), np.int64)
+    if n_live == 0:
+        return out
+    xn = xn[:n_live]
+
+    def level(l):
+        g = dn[l, :n_live]
+        if not g.any():
+            return
+        idx, w = weights[l] if weights is not None else grid_fixed_weights(xn, lv, l, interpolation)
+        idx, w = idx[:n_live], w[:n_live]
+        lo, size = int(lv.offset[l]), int(lv.size[l])
+        to_fixed = np.float64(2.0) ** int(shifts[l])
+        acc = np.zeros((size, 2), np.float64)
+        for c in range(8):
+            ok = idx[:, c] < size                                   # (a line-local corner past a level's end receives nothing)
+            ic = idx[:, c].astype(np.int64) if ok.all() else idx[ok, c].astype(np.int64)
+            wc = w[:, c] if ok.all() else w[ok, c]
+            for k in range(2):
+                gk = g[:, k] if ok.all() else g[ok, k]
+                v = np.rint((wc * gk).astype(F32).astype(np.float64) * to_fixed)
+                acc[:, k] += np.bincount(ic, weights=v, minlength=size)
+        out[lo:lo + size] = acc.astype(np.int64)
+
+    if workers > 1 and lv.n_levels > 1:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=min(workers, lv.n_levels)) as ex:
+            list(ex.map(level, range(lv.n_levels)))
+    else:
+        for l in range(lv.n_levels):
+            level(l)
+    if lv.layout == 'line_overlap':
+        fold_overlap_copies(out, lv)
+    return out
+
+
+def fixed_field_max(fields: np.ndarray, lv: GridLevels, entry_lo: int = 0, entry_hi: int = None) -> np.ndarray:
+    """Largest |field| per level over the entries [entry_lo, entry_hi), int64 [L], in the kernels' convention: a negative field v
+    counts as -(v + 1) = |v| - 1 (one's complement: no branch for INT32_MIN; hashgrid_bwd.hip:1038, hashgrid_aux.hip:177)."""
+    entry_hi = lv.total if entry_hi is None else entry_hi
+    out = np.zeros(lv.n_levels, np.int64)
+    for l in range(lv.n_levels):
+        lo, hi = max(int(lv.offset[l]), entry_lo), min(int(lv.offset[l]) + int(lv.size[l]), entry_hi)
+        if hi > lo:
+            v = fields[lo:hi]
+            out[l] = np.where(v < 0, -(v + 1), v).max()
+    return out
+
+
+def fixed_fields_to_float(fields: np.ndarray, lv: GridLevels, shifts) -> np.ndarray:
+    """fl32(field) * 2^-shift per level, f32 [total, 2]: the conversion of the owners' write-back, the replica reduction and
+    perf_fixed_unfix ((float)int32 rounds to nearest even above 2^24; the power of two is exact).  Entries between levels stay 0."""
+    out = np.zeros(fields.shape, F32)
+    for l in range(lv.n_levels):
+        lo, hi = int(lv.offset[l]), int(lv.offset[l]) + int(lv.size[l])
+        out[lo:hi] = fields[lo:hi].astype(F32) * F32(2.0 ** -int(shifts[l]))
+    return out
+
+
 def mlp_shapes(n_in: int, n_hidden_layers: int, width: int = 64, n_out_padded: int = 16):
     shapes = [(width, n_in)] + [(width, width)] * (n_hidden_layers - 1) + [(n_out_padded, width)]
     return shapes

@@ -14,6 +14,7 @@ the constants PARSED from the sources, so the test follows them -- and checks th
   4. the resolution that is left: inside the band the largest contribution of a call is at least 2^(31 - 28) = 8 units, and with the
      static fan-in guess (no state) never less than 2^7 units.
 """
+import math
 import os
 import re
 
@@ -38,9 +39,15 @@ def _constants():
     assert clamp, 'fixed_point_shift: the clamps of the headroom moved'
     floor = re.search(r'adj > (-\d+)\) adj -= 1', hpp)
     assert floor
+    # the exponent rule: e from frexpf (am < 2^e), 0 for am <= 0, clamped from below; shift = 31 - h - e
+    expo = re.search(r'int e = 0;\s*if \(am > 0\.f\) \(void\)frexpf\(am, &e\);[^\n]*\n\s*if \(e < (-\d+)\) e = \1;', hpp)
+    assert expo, 'fixed_point_shift: the exponent rule moved'
+    assert re.search(r'return 31 - h - e;', hpp), 'fixed_point_shift: the shift is no longer 31 - h - e'
+    assert re.search(r'fan = \(8ull \* \(unsigned long long\)n_live \+ size - 1ull\) / size;', hpp), 'fixed_point_shift: the fan-in guess moved'
     return dict(top=_const(hpp, 'kHeadroomTopBit'), low=_const(hpp, 'kHeadroomLowBit'), bias=_const(hpp, 'kHeadroomStartBias'),
                 flag=int(flags.pop()), h_min=int(clamp.group(1)), h_max=int(clamp.group(2)), h_min_static=int(clamp.group(3)),
-                h_max_static=int(clamp.group(4)), adj_floor=int(floor.group(1)), max_replicas=_const(bwd, 'kMaxReplicas'))
+                h_max_static=int(clamp.group(4)), adj_floor=int(floor.group(1)), max_replicas=_const(bwd, 'kMaxReplicas'),
+                e_min=int(expo.group(1)))
 
 
 C = _constants()
@@ -61,6 +68,36 @@ def headroom_bits(fan, adj=None):
     if adj is None:
         return min(max(h, C['h_min_static']), C['h_max_static'])
     return min(max(h + adj + C['bias'], C['h_min']), C['h_max'])
+
+
+def fixed_point_shift(am, n_live, size, adj=None):
+    """grid_fixed_point.hpp:fixed_point_shift: one unit of a level is 2^-shift.  am = the level's max |dfeat| (fp32), n_live the live
+    sample count, size the level's entries, adj the level's headroom state (None: no state, the static guess)."""
+    am = float(np.float32(am))
+    e = 0
+    if am > 0.0:
+        _, e = math.frexp(am)                        # am = m 2^e, 0.5 <= m < 1 (frexpf; a subnormal am gives e < -126)
+    e = max(e, C['e_min'])
+    fan = (8 * int(n_live) + int(size) - 1) // int(size)
+    return 31 - headroom_bits(fan, adj) - e
+
+
+def test_the_exponent_rule_of_the_unit():
+    assert C['e_min'] == -80
+    # the largest contribution |w g| <= am < 2^e spans less than 2^(31 - h) units: h bits of headroom below the int32 sign
+    for am in (1.0, 0.75, 1.5, 3e-5, 2.0 ** -60, 123456.0, float(np.nextafter(np.float32(2.0), np.float32(0.0)))):
+        for n, size in ((4099, 4096), (1 << 20, 1 << 18), (1, 1 << 18)):
+            for adj in (None, 0, -5, 7):
+                sh = fixed_point_shift(am, n, size, adj)
+                fan = (8 * n + size - 1) // size
+                h = headroom_bits(fan, adj)
+                assert am * 2.0 ** sh < 2.0 ** (31 - h) <= 2.0 * am * 2.0 ** sh
+    # an exact power of two sits at the BOTTOM of its binade (frexp: 1.0 = 0.5 * 2^1)
+    assert fixed_point_shift(1.0, 1, 1 << 18) == fixed_point_shift(1.5, 1, 1 << 18) == fixed_point_shift(0.5, 1, 1 << 18) - 1
+    # no gradient at all: e = 0; vanishing gradients: the clamp keeps 2^shift a finite fp32 (shift <= 31 - 4 + 80 < 128)
+    assert fixed_point_shift(0.0, 1000, 4096) == 31 - headroom_bits(2)
+    assert fixed_point_shift(1e-30, 1000, 4096) == fixed_point_shift(2.0 ** -90, 1000, 4096) == 31 - headroom_bits(2) + 80
+    assert 31 - C['h_min'] - C['e_min'] < 128
 
 
 def test_partial_sums_may_wrap_only_the_final_sum_has_to_fit():

@@ -165,17 +165,63 @@ def _mlp_case(ops, dt, nh, n_out, act, n, n_levels=16, seed=0):
     return cfgm, w, feat, sel, tdt, ulp
 
 
-def _mlp_oracle(cfgm, w, feat, sel, dt):
+def _mlp_oracle(cfgm, w, feat, sel, dt, round_dy=False):
+    """round_dy: the gradient that arrives at the network's linear output -- dY = dout * act'(y) * sel -- is rounded to the 16-bit
+    type on the way back, as mlp_bwd rounds it before its MFMA chain (autograd through quant= already rounds every dH, not dY)"""
     n = feat.shape[1]
     x = feat.permute(1, 0, 2).reshape(n, -1)
     if cfgm.n_in_pad > x.shape[1]:
         x = torch.cat([x, torch.zeros(n, cfgm.n_in_pad - x.shape[1])], 1)
     y = O.mlp_forward(x, w, cfgm.n_in_pad, cfgm.n_hidden_layers, cfgm.n_output_dims, 'None', quant=dt)
+    if round_dy and y.requires_grad:
+        y.register_hook(lambda g: g.to(DT[dt][0]).to(g.dtype))
     if cfgm.output_activation == 'Sigmoid':
         y = torch.sigmoid(y)
     elif cfgm.output_activation == 'Exponential':
         y = O.trunc_exp(y - cfgm.exp_shift)
     return y * sel[:, None].float()
+
+
+def _rms(t):
+    return float(t.double().pow(2).mean().sqrt()) if t.numel() else 0.0
+
+
+def _assert_blocks_within_twice_the_emulation_noise(what, cfgm, w16, f16, sel, dt, out, dout=None, dfeat=None, dw=None):
+    """PER BLOCK -- each output column, each level's dfeat, each layer's dw -- the kernel's distance from the exact result T against
+    the 16-bit emulation's own distance from T, on the same 16-bit operands:
+        rms(kernel - T) <= 2 * rms(oracle - T) + 2^-20 * max|T of the block|
+    T is the float64 forward / autograd with no intermediate rounding, the oracle is quant=dt with dY rounded as well (without that
+    the kernel's dfeat and dw sit sqrt(2) from T where the emulation rounds once, and a two-entry block -- one sample's level -- has
+    measured 2.46).  Kernel and emulation round the same quantities the same number of times and differ in accumulation order and 16-bit ties: a kernel that needs more than twice the
+    emulation's noise rounds something the emulation does not.  The bound of a block is about that block -- a layer twenty times
+    smaller than the largest has a bound twenty times smaller.  Prints every block's ratio; returns the largest per kind."""
+    grads = dout is not None
+    wt, ft = w16.double().requires_grad_(grads), f16.double().requires_grad_(grads)
+    wo, fo = w16.float().requires_grad_(grads), f16.float().requires_grad_(grads)
+    yt = _mlp_oracle(cfgm, wt, ft, sel, None)
+    yo = _mlp_oracle(cfgm, wo, fo, sel, dt, round_dy=True)
+    assert yt.dtype == torch.float64 and yo.dtype == torch.float32
+    blocks = [(f'out[:, {c}]', out[:, c], yo.detach()[:, c], yt.detach()[:, c]) for c in range(cfgm.n_output_dims)]
+    if grads:
+        (yt * dout.double()).sum().backward()
+        (yo * dout).sum().backward()
+        blocks += [(f'dfeat[{l}]', dfeat[l], fo.grad[l], ft.grad[l]) for l in range(cfgm.n_levels)]
+        off = 0
+        for k, (o, i) in enumerate(cfgm.shapes):
+            blocks.append((f'dw[layer {k}]', dw[off:off + o * i], wo.grad[off:off + o * i], wt.grad[off:off + o * i]))
+            off += o * i
+    worst, bad = {}, []
+    for name, got, orc, t in blocks:
+        ek, eo, floor = _rms(got.double() - t), _rms(orc.double() - t), 2.0 ** -20 * float(t.abs().max())
+        ratio = ek / eo if eo > 0 else (0.0 if ek <= floor else float('inf'))
+        print(f'[per block] {what} {name}: rms(kernel - T) {ek:.3e}  rms(oracle - T) {eo:.3e}  ratio {ratio:.3f}  floor {floor:.1e}')
+        kind = name.split('[')[0]
+        worst[kind] = max(worst.get(kind, 0.0), ratio if ek > floor else 0.0)
+        if not ek <= 2.0 * eo + floor:
+            bad.append((name, ek, eo, floor))
+    print(f'[per block] {what} largest ratio per kind: ' + ', '.join(f'{k} {v:.3f}' for k, v in worst.items()))
+    assert not bad, (what, bad)
+    return worst
 
 
 @pytest.mark.parametrize('dt', ['bf16', 'fp16'])
@@ -190,6 +236,7 @@ def test_mlp_fwd(ops, dt, nh, n_out, act):
     # and from hidden activations that round differently at 16-bit ties: a few 16-bit ulps of the largest activation
     tol = 8 * ulp * max(1.0, float(ref.abs().max()))
     assert (out - ref).abs().max() < tol, (out - ref).abs().max()
+    _assert_blocks_within_twice_the_emulation_noise(f'mlp_fwd {dt} nh{nh} o{n_out} {act}', cfgm, w16, f16, sel, dt, out)
 
 
 def test_mlp_fwd_small_input(ops):
@@ -197,6 +244,7 @@ def test_mlp_fwd_small_input(ops):
     out = ops.mlp_fwd(cfgm, w.to(tdt).cuda(), feat.to(tdt).cuda(), None).cpu()
     ref = _mlp_oracle(cfgm, w.to(tdt).float(), feat.to(tdt).float(), torch.ones(300, dtype=torch.uint8), 'fp16')
     assert (out - ref).abs().max() < 8 * ulp * max(1.0, float(ref.abs().max()))
+    _assert_blocks_within_twice_the_emulation_noise('mlp_fwd small input', cfgm, w.to(tdt), feat.to(tdt), torch.ones(300, dtype=torch.uint8), 'fp16', out)
 
 
 @pytest.mark.parametrize('dt', ['bf16', 'fp16'])
@@ -217,6 +265,8 @@ def test_mlp_bwd(ops, dt, nh, n_out, act):
         return (a - b).abs().max() <= k * ulp * float(b.abs().max()) + 1e-6
     assert close(dfeat.cpu(), fr.grad, 16), ((dfeat.cpu() - fr.grad).abs().max(), fr.grad.abs().max())
     assert close(dw.cpu(), wr.grad, 16), ((dw.cpu() - wr.grad).abs().max(), wr.grad.abs().max())
+    out = ops.mlp_fwd(cfgm, w16.cuda(), f16.cuda(), sel.cuda()).cpu()
+    _assert_blocks_within_twice_the_emulation_noise(f'mlp_bwd {dt} nh{nh} o{n_out} {act}', cfgm, w16, f16, sel, dt, out, dout, dfeat.cpu(), dw.cpu())
 
 
 @pytest.mark.parametrize('nh,n_out,act,n_levels,n,with_sel', [
@@ -251,6 +301,8 @@ def test_mlp_tiles_ahead(ops, nh, n_out, act, n_levels, n, with_sel):
     k = 16 * max(1.0, math.sqrt(n / 2000.0))
     assert close(dw.cpu(), wr.grad, k), ((dw.cpu() - wr.grad).abs().max(), wr.grad.abs().max())
     assert float(amax.max()) == float(dfeat.abs().max())
+    _assert_blocks_within_twice_the_emulation_noise(f'mlp_tiles_ahead nh{nh} o{n_out} {act} L{n_levels} n{n}', cfgm, w16, f16, sel, dt, out, dout,
+                                                    dfeat.cpu(), dw.cpu())
 
 
 @pytest.mark.parametrize('dt', ['bf16', 'fp16'])
@@ -279,6 +331,8 @@ def test_mlp_more_than_16_levels(ops, dt, nh, n_out, act, n_levels):
     own = dfeat.abs().amax(dim=(1, 2))
     assert bool((amax[:n_levels] >= own).all()) and float(amax[n_levels:].abs().sum()) == 0.0
     assert float(amax.max()) == float(own.max())
+    _assert_blocks_within_twice_the_emulation_noise(f'mlp_more_than_16_levels {dt} nh{nh} o{n_out} {act} L{n_levels}', cfgm, w16, f16, sel, dt, out, dout,
+                                                    dfeat.cpu(), dw.cpu())
 
 
 def test_cast_and_adam(ops):

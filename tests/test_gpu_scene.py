@@ -164,19 +164,38 @@ def test_geo_step_gradient_matches_oracle(golden_dir, dtype):
     k16 = 8.0 if dtype == 'bf16' else 1.0
     assert abs(float(dl) - float(rdl)) < 2e-3 * k16 * max(1.0, abs(float(rdl)))
     assert abs(float(distl) - float(rdistl)) < 2e-2 * k16 * max(1e-3, abs(float(rdistl)))
-    worst = _assert_field_gradient_close(grad, geo_r.grad, O.geo_spec(), *GRAD_TOL[dtype])
+    tdt = {'bf16': torch.bfloat16, 'fp16': torch.float16}[dtype]
+    geo_t = geo.to(tdt).float().requires_grad_(True)              # T: the same 16-bit parameters and sample set, no intermediate rounding
+    ref_t = O.occ_render(o, d, geo_t, app.to(tdt).float(), occ, AABB, kept_counts=counts, **{**kw, 'quant': None})
+    O.geo_step_loss(ref_t, gt_dist, progress=0.25)[0].backward()
+    worst = _assert_field_gradient_close(grad, geo_r.grad, O.geo_spec(), *GRAD_TOL[dtype], exact=geo_t.grad, what=f'geo step {dtype}')
     print(f'[geo gradient {dtype}] worst level (rel L2, max-abs, level): {max(worst)}')
 
 
-def _assert_field_gradient_close(grad, ref, spec, tol_l2=3e-2, tol_max=4e-2):
+def _assert_field_gradient_close(grad, ref, spec, tol_l2=3e-2, tol_max=4e-2, exact=None, what=''):
     """Flat field gradient [network | grid] against the oracle's autograd: relative L2 of the network part, and PER GRID
     LEVEL both the relative L2 and the max-abs error (normalised by the level's largest reference entry) -- a whole-table
     L2 would hide an error confined to one level.  The HIP side multiplies 16-bit operands (features, weights,
-    activations) where the oracle's quant=... emulation rounds the same operands, so a few 16-bit ulps per product."""
+    activations) where the oracle's quant=... emulation rounds the same operands, so a few 16-bit ulps per product.
+    exact: the same gradient WITHOUT intermediate rounding, on the same 16-bit parameters (T).  Then, per LAYER of the network part,
+    rms(kernel - T) <= 2 * rms(oracle - T) + 2^-20 * max|T of the layer|: the bound of a layer is about that layer and about the
+    emulation's own noise there (the form of tests/test_gpu_ops.py:_assert_blocks_within_twice_the_emulation_noise)."""
     def rel(a, b):
         return float((a - b).norm() / (b.norm() + 1e-12))
     n_net = spec.n_net
     assert rel(grad[:n_net], ref[:n_net]) < tol_l2, rel(grad[:n_net], ref[:n_net])
+    if exact is not None:
+        off, bad = 0, []
+        for k, (o, i) in enumerate(O.mlp_shapes(spec.n_in, spec.n_hidden_layers)):
+            t = exact[off:off + o * i].double()
+            ek = float((grad[off:off + o * i].double() - t).pow(2).mean().sqrt())
+            eo = float((ref[off:off + o * i].double() - t).pow(2).mean().sqrt())
+            floor = 2.0 ** -20 * float(t.abs().max())
+            print(f'[per block] {what} dw[layer {k}]: rms(kernel - T) {ek:.3e}  rms(oracle - T) {eo:.3e}  ratio {ek / max(eo, 1e-300):.3f}  floor {floor:.1e}')
+            if not ek <= 2.0 * eo + floor:
+                bad.append((k, ek, eo, floor))
+            off += o * i
+        assert off == n_net and not bad, (what, bad)
     lv = spec.lv
     worst = []
     for l in range(lv.n_levels):
@@ -246,7 +265,11 @@ def test_app_step_gradient_matches_oracle(golden_dir, dtype):
     loss.backward()
     assert geo_r.grad is None
     assert abs(float(scene.last_losses['color_loss']) - float(cl)) < 2e-3 * (8.0 if dtype == 'bf16' else 1.0) * max(1.0, abs(float(cl)))
-    worst = _assert_field_gradient_close(grad, app_r.grad, O.app_spec(), *GRAD_TOL[dtype])
+    tdt = {'bf16': torch.bfloat16, 'fp16': torch.float16}[dtype]
+    app_t = app.to(tdt).float().requires_grad_(True)              # T: the same 16-bit parameters and sample set, no intermediate rounding
+    ref_t = O.occ_render(o, d, geo.to(tdt).float(), app_t, occ, AABB, kept_counts=counts, geo_grad=False, app_grad=True, **{**kw, 'quant': None})
+    O.app_step_loss(ref_t, gt_rgb)[0].backward()
+    worst = _assert_field_gradient_close(grad, app_r.grad, O.app_spec(), *GRAD_TOL[dtype], exact=app_t.grad, what=f'app step {dtype}')
     print(f'[app gradient {dtype}] worst level (rel L2, max-abs, level): {max(worst)}')
 
 
@@ -764,7 +787,9 @@ def test_network_with_20_level_grid_forward_and_gradient(nh, n_out, act):
     (yr * dout).sum().backward()
     ulp = 2.0 ** -10
     assert float((y.detach().cpu() - yr.detach()).abs().max()) < 16 * ulp * max(1.0, float(yr.abs().max()))
-    _assert_field_gradient_close(net.params.grad.cpu(), pr.grad, spec)
+    pt = p0.to(torch.float16).float().requires_grad_(True)        # T: the same 16-bit parameters, no intermediate rounding
+    (O.network_with_encoding(x, pt, spec, quant=None) * dout).sum().backward()
+    _assert_field_gradient_close(net.params.grad.cpu(), pr.grad, spec, exact=pt.grad, what=f'20-level field nh{nh} o{n_out} {act}')
 
 
 def test_supervision_sampling_modes():

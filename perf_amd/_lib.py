@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libperf_hip.so')
 
 ABI_VERSION = 16         # PERF_ABI_VERSION of include/perf_hip.h this binding was written against
+EXT_ABI_VERSION = 1      # PERF_EXT_ABI_VERSION of include/perf_hip_ext.h (entry points added after perf_hip.h was frozen)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -136,6 +137,13 @@ _SIGS = {
     'perf_occ_splat': (c_int, [P, P, P, c_int64, c_int32, P, P]),
 }
 
+# include/perf_hip_ext.h: exported from the same library, versioned on its own (perf_ext_version)
+_SIGS_EXT = {
+    'perf_ext_version': (c_int, []),
+    'perf_field_grad_x_bwd_workspace_bytes': (c_int64, [POINTER(GridDesc), POINTER(MlpDesc), c_int64]),
+    'perf_field_grad_x_bwd': (c_int, [POINTER(GridDesc), POINTER(MlpDesc), P, P, P, P, POINTER(c_float), P, P, P, P, c_int64, c_int64, P, c_int, P]),
+}
+
 _lib = None
 
 
@@ -151,13 +159,18 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()):
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
         fn.restype = res
         fn.argtypes = args
     # the binding and the library must agree on the ABI version and on the layout of the POD descriptors
     if lib.perf_version() != ABI_VERSION:
         raise PerfError(f'{LIB_PATH} has ABI version {lib.perf_version()}, this binding expects {ABI_VERSION}: '
+                        'rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_ext_version() != EXT_ABI_VERSION:
+        raise PerfError(f'{LIB_PATH} has extension ABI version {lib.perf_ext_version()}, this binding expects {EXT_ABI_VERSION}: '
                         'rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):

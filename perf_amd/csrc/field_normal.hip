@@ -16,7 +16,7 @@
 // No feature gradient goes through memory, no weight gradient is formed.  Plain vector stores only.
 //
 // Built: tcnn table layout, Linear interpolation, one hidden layer, up to 16 levels, bf16 / fp16.  Everything else is refused.
-#include "mlp_device.hpp"
+#include "field_normal_device.hpp"
 
 namespace perf {
 
@@ -27,41 +27,16 @@ struct GradXIn {
     float inv_extent[3];
 };
 
-// Fragment slots in LDS (16 B per lane each): the forward's A1[m][s] and Ao[s] as Layout<1, KS> numbers them, then
-//   kA1P + s: A1T'[s]  row rho of the 32 x 32 result <-> input feature perm_in(rho), slot (h, j) <-> neuron slot_neuron(s, h, j)
-//   kWoR + s: Wo[0][slot_neuron(s, h, j)], j = 0..7 -- the B operand of the pull-back before masking
-// perm_in: D row rho = d_row(r, hh) is register r = (rho & 3) + 4 (rho >> 3) of half hh = (rho >> 2) & 1, and that register stands for
-// feature r & 1 of level 8 (r >> 3) + 2 ((r >> 1) & 3) + hh.
-__device__ __forceinline__ int perm_in(int rho) {
-    const int hh = (rho >> 2) & 1, r = (rho & 3) + 4 * (rho >> 3);
-    return 16 * (r >> 3) + 4 * ((r >> 1) & 3) + 2 * hh + (r & 1);
-}
-
 template <typename T16, int KS>
 __global__ __launch_bounds__(256) void field_grad_x_kernel(MlpParams mp, const uint16_t* __restrict__ w, const uint8_t* __restrict__ sel,
                                                            float* __restrict__ grad, float* __restrict__ sigma, int64_t n,
                                                            const int64_t* __restrict__ n_dev, GradXIn in) {
-    using L = Layout<1, KS>;
-    constexpr int kA1P = L::n_fwd, kWoR = L::n_fwd + 4;
     const int64_t n_live = live_count(n, n_dev);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32x4* frag = reinterpret_cast<u32x4*>(smem);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
-    stage_fragments<1, KS, false>(w, frag);
-    {   // one pulled-back fragment pair per wave (blocks of four waves)
-        const int s = wave;
-        const int fin = perm_in(c);
-        uint16_t a[8], b[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int nr = slot_neuron(s, h, j);
-            a[j] = fin < L::n_in_pad ? w[L::w1_off + nr * L::n_in_pad + fin] : (uint16_t)0;
-            b[j] = w[L::wo_off + nr];
-        }
-        frag[(kA1P + s) * 64 + lane] = pack8(a);
-        frag[(kWoR + s) * 64 + lane] = pack8(b);
-    }
+    stage_grad_x_fragments<KS>(w, frag);
     __syncthreads();
     const int64_t n_tiles = (n_live + kTile - 1) / kTile;
     const int64_t tile_step = (int64_t)gridDim.x * 4;
@@ -70,74 +45,12 @@ __global__ __launch_bounds__(256) void field_grad_x_kernel(MlpParams mp, const u
         const bool valid = si < n_live;
         float x = 0.5f, y = 0.5f, z = 0.5f;
         if (valid) { x = in.x01[3 * si]; y = in.x01[3 * si + 1]; z = in.x01[3 * si + 2]; }
-        // ---- 1. features and their derivatives (per unit of the level's grid coordinate times scale = per unit of x01)
-        u32x4 b1[KS];
+        // ---- 1.-3. (field_normal_device.hpp)
+        u32x4 b1[KS], hb[4], dh[4];
         float dF[8 * KS][3];        // [2 * (4 s + i) + feature][axis]
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int level = 8 * s + 2 * i + h;
-                const int q = 2 * (4 * s + i);
-                uint32_t pair = 0u;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) dF[q][a] = dF[q + 1][a] = 0.f;
-                if (valid && level < mp.n_levels) {
-                    const float scale = in.gp.scale[level];
-                    const Corners cr = corners_of(x, y, z, scale, in.gp.res[level], in.gp.size[level], in.gp.hashed[level] != 0);
-                    const uint32_t* t = in.table + in.gp.offset[level];
-                    uint32_t v[8];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = t[cr.idx[k]];
-                    float wgt[8];
-                    corner_weights(cr.f, false, wgt);
-                    float v0[8], v1[8], a0 = 0.f, a1 = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {            // (encode_pair's sum, term for term)
-                        v0[k] = T16::lo(v[k]); v1[k] = T16::hi(v[k]);
-                        a0 = fmaf(wgt[k], v0[k], a0);
-                        a1 = fmaf(wgt[k], v1[k], a1);
-                    }
-                    pair = T16::pack(a0, a1);
-                    const float fx = cr.f[0], fy = cr.f[1], fz = cr.f[2];
-                    const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy}, wz[2] = {1.0f - fz, fz};
-                    float gx0 = 0.f, gx1 = 0.f, gy0 = 0.f, gy1 = 0.f, gz0 = 0.f, gz1 = 0.f;
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {            // corner k = bit 0: x, bit 1: y, bit 2: z
-                        const int a = p & 1, b = p >> 1;
-                        const float wyz = wy[a] * wz[b], wxz = wx[a] * wz[b], wxy = wx[a] * wy[b];
-                        const int kx = 2 * a + 4 * b, ky = a + 4 * b, kz = a + 2 * b;
-                        gx0 = fmaf(wyz, v0[kx + 1] - v0[kx], gx0); gx1 = fmaf(wyz, v1[kx + 1] - v1[kx], gx1);
-                        gy0 = fmaf(wxz, v0[ky + 2] - v0[ky], gy0); gy1 = fmaf(wxz, v1[ky + 2] - v1[ky], gy1);
-                        gz0 = fmaf(wxy, v0[kz + 4] - v0[kz], gz0); gz1 = fmaf(wxy, v1[kz + 4] - v1[kz], gz1);
-                    }
-                    dF[q][0] = gx0 * scale; dF[q][1] = gy0 * scale; dF[q][2] = gz0 * scale;
-                    dF[q + 1][0] = gx1 * scale; dF[q + 1][1] = gy1 * scale; dF[q + 1][2] = gz1 * scale;
-                }
-                b1[s][i] = pair;
-            }
-        // ---- 2. forward (mlp_fwd_kernel's, NH = 1)
-        u32x4 hb[4];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            f32x16 acc = f32x16{0};
-#pragma unroll
-            for (int s = 0; s < KS; ++s) acc = T16::mfma(frag[(L::f_a1 + m * KS + s) * 64 + lane], b1[s], acc);
-            relu_pack_plain<T16>(acc, hb[2 * m], hb[2 * m + 1]);
-        }
-        f32x16 o = f32x16{0};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) o = T16::mfma(frag[(L::f_ao + s) * 64 + lane], hb[s], o);
-        // ---- 3. pull row 0 back through the masks and W1^T
-        f32x16 dx = f32x16{0};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const u32x4 wo = frag[(kWoR + s) * 64 + lane];
-            u32x4 dh;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) dh[i] = wo[i] & nonzero_halves(hb[s][i]);
-            dx = T16::mfma(frag[(kA1P + s) * 64 + lane], dh, dx);
-        }
+        features_and_derivatives<T16, KS>(in.gp, in.table, mp.n_levels, valid, h, x, y, z, b1, dF);
+        f32x16 o, dx;
+        forward_and_pull_back<T16, KS>(frag, lane, b1, hb, dh, o, dx);
         // ---- 4. contract with the feature derivatives, add the two halves of the sample
         float g[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -197,7 +110,7 @@ __global__ __launch_bounds__(256) void normal_composite_kernel(const float* __re
 template <typename T16, int KS>
 static void launch_grad_x(int blocks, hipStream_t st, MlpParams mp, const uint16_t* w, const uint8_t* sel, float* grad, float* sigma,
                           int64_t n, const int64_t* n_dev, const GradXIn& in) {
-    constexpr int lds_bytes = (Layout<1, KS>::n_fwd + 8) * 1024;
+    constexpr int lds_bytes = GradXFrags<KS>::n * 1024;
     field_grad_x_kernel<T16, KS><<<dim3(blocks), dim3(256), lds_bytes, st>>>(mp, w, sel, grad, sigma, n, n_dev, in);
 }
 

@@ -57,6 +57,45 @@ def contract_to_unisphere(x, aabb, eps: float = 1e-6):
     return u * 0.25 + 0.5
 
 
+class _DensityGradFn(torch.autograd.Function):
+    """(sigma, d sigma / d x) of the density network, differentiable with respect to its PARAMETERS: forward ops.field_grad_x, backward
+    ops.field_grad_x_bwd, both on the 16-bit working copy.  Positions get no gradient."""
+
+    @staticmethod
+    def forward(ctx, x01, params, sel, net, inv_extent, n_dev):
+        w16 = net.working_copy(params)
+        out = None
+        if n_dev is not None:       # (rows at and beyond the device count are not written by the kernel: zeros, not allocator garbage)
+            out = (torch.zeros(x01.shape[0], dtype=torch.float32, device=x01.device), torch.zeros(x01.shape[0], 3, dtype=torch.float32, device=x01.device))
+        sigma, grad = ops.field_grad_x(net.grid, net.mlp, x01, sel, w16, inv_extent, n_dev=n_dev, out=out)
+        ctx.net, ctx.inv_extent, ctx.n_dev, ctx.has_sel = net, inv_extent, n_dev, sel is not None
+        ctx.save_for_backward(x01, w16, sel if sel is not None else torch.empty(0, device=x01.device))
+        ctx.set_materialize_grads(False)
+        return sigma, grad
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dsigma, dgrad):
+        if dsigma is None and dgrad is None:
+            return None, None, None, None, None, None
+        x01, w16, sel = ctx.saved_tensors
+        net = ctx.net
+        g = ops.field_grad_x_bwd(net.grid, net.mlp, x01, sel if ctx.has_sel else None, w16, ctx.inv_extent,
+                                 None if dsigma is None else dsigma.contiguous().float(), None if dgrad is None else dgrad.contiguous().float(),
+                                 n_dev=ctx.n_dev, ws=net.bwd_workspace)
+        return None, g, None, None, None, None
+
+
+def unit_normals(g):
+    """n = -g / |g| per row of a density gradient [..., 3], in torch (differentiable): scaled by the largest component first, as
+    NGPNeRF.query_normal does (|g|^2 of a trunc_exp gradient can leave fp32), and 0 where g is 0 or not finite."""
+    m = g.detach().abs().amax(dim=-1, keepdim=True)
+    ok = (m > 0) & (m <= 3.0e38)
+    u = torch.where(ok, g, torch.zeros_like(g)) / torch.where(ok, m, torch.ones_like(m))
+    nrm = torch.linalg.vector_norm(torch.where(ok, u, torch.ones_like(u)), dim=-1, keepdim=True)
+    return torch.where(ok, -u / nrm, torch.zeros_like(u))
+
+
 class _DensityNet(tcnn.NetworkWithInputEncoding):
     """geo network whose kernel epilogue applies trunc_exp(y - shift) * selector."""
 
@@ -134,6 +173,16 @@ class NGPNeRF(nn.Module):
         (ops.field_grad_x).  Evaluation only: nothing is recorded for autograd."""
         net = self.geo_mlp
         return ops.field_grad_x(net.grid, net.mlp, x01, sel, net.working_copy(), self._inv_extent(), n_dev=n_dev)
+
+    def density_and_grad_at(self, x01, sel, n_dev=None):
+        """(sigma [n], d sigma / d x [n,3] in world units) with autograd: differentiable with respect to geo_mlp.params ONLY (a loss on
+        surface normals during training) -- the forward is density_grad_at's kernel to the bit, the backward ONE fused kernel
+        (ops.field_grad_x_bwd).  Positions are not trained: x01.requires_grad raises."""
+        if x01.requires_grad:
+            raise NotImplementedError('density_and_grad_at is differentiable with respect to geo_mlp.params only: x01.requires_grad is set '
+                                      '(the second derivative with respect to positions is not built)')
+        net = self.geo_mlp
+        return _DensityGradFn.apply(x01, net.params, sel, net, self._inv_extent(), n_dev)
 
     @torch.no_grad()
     def query_normal(self, x):

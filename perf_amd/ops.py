@@ -529,6 +529,30 @@ def field_grad_x(grid: GridConfig, mlp: MlpConfig, x01, sel, w16, inv_extent=Non
     return sigma, grad
 
 
+def field_grad_x_bwd(grid: GridConfig, mlp: MlpConfig, x01, sel, w16, inv_extent=None, dsigma=None, dgrad=None, n_dev=None, grad=None,
+                     ws=None):
+    """Backward of field_grad_x with respect to the field's parameters (perf_field_grad_x_bwd, include/perf_hip_ext.h): given the
+    upstream gradients dsigma [n] and dgrad [n,3] (either may be None, not both) -> flat fp32 gradient [network | grid] of
+    sum(dsigma * sigma) + sum(dgrad * grad_x), OVERWRITTEN in full (all zeros for an empty or dead batch).  One kernel on the 16-bit
+    working copy w16; the network part is deterministic, the table part is scattered with fp32 atomics (order-dependent in its last
+    bits).  ws (a Workspace): the holder of the call's scratch memory -- a network's bwd_workspace, as for field_bwd."""
+    n = x01.shape[0]
+    n_net = mlp.n_params
+    dev = x01.device
+    if grad is None:
+        grad = torch.empty(n_net + grid.n_params, dtype=torch.float32, device=dev)
+    ie = None if inv_extent is None else (ctypes.c_float * 3)(*[float(v) for v in inv_extent])
+    gd, md = grid.desc(), mlp.desc()
+    nbytes = _lib.load().perf_field_grad_x_bwd_workspace_bytes(ctypes.byref(gd), ctypes.byref(md), n)
+    if nbytes < 0:
+        _lib.check(-1, 'perf_field_grad_x_bwd_workspace_bytes')
+    block = (ws or Workspace()).get(nbytes, dev)
+    _call('perf_field_grad_x_bwd', ctypes.byref(gd), ctypes.byref(md), _p(_f32(x01, 'x01')), _p(sel), _p(w16[n_net:]), _p(w16[:n_net]), ie,
+          _p(None if dsigma is None else _f32(dsigma, 'dsigma')), _p(None if dgrad is None else _f32(dgrad, 'dgrad')), _p(grad), _p(block),
+          block.numel() * 4, n, _nd(n_dev), dtype_code(w16.dtype), _stream())
+    return grad
+
+
 def normal_composite(weights, grad, packed):
     """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
     R = packed.shape[0]

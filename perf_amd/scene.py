@@ -144,8 +144,17 @@ def normals_to_camera(normal, pose):
     return torch.matmul(normal, rot)              # row vectors: n^T R = (R^T n)^T
 
 
+def normals_to_world(normal, pose):
+    """The inverse of normals_to_camera: camera-frame normals [..., 3] at `pose` -> world frame, n_world = R n_cam.  The geometry
+    step's normal loss (train_conf.normal_loss_weight) compares the pool's normals with the WORLD-frame density gradient."""
+    rot = torch.as_tensor(pose, dtype=normal.dtype, device=normal.device)[:3, :3]
+    return torch.matmul(normal, rot.transpose(-1, -2))
+
+
 def default_train_conf():
-    """configs/nerf.yaml:24-74"""
+    """configs/nerf.yaml:24-74.  Not the reference's, read with getattr(..., 0.): normal_loss_weight -- above 1e-7 the geometry step adds
+    sum_i w_i (1 - n_i . n_gt) / batch over the kept samples of rays with a supervised normal (NeRFScene._normal_loss) and runs as
+    the eager autograd step, as with density_loss_weight."""
     opt = lambda i, p, a, l: SimpleNamespace(init_lr=i, peak_lr=p, peak_at=a, lr_alpha=l)
     return SimpleNamespace(
         raw_phase_iter_geo=3000, raw_phase_iter_app=1500,
@@ -180,6 +189,8 @@ class SupInfoPool:
         self._ranges = []              # per registration: [start, end) in the flat arrays (rand_mode 'only_first' / 'only_last')
 
     def register_rays(self, rays_o, rays_d, colors, distances, normals=None):
+        """normals [n,3] (optional; zero = none): what the geometry step's normal loss is trained against, taken as WORLD-frame unit
+        vectors facing the camera's side of the surface.  Normals of a camera whose pose is rotated go through normals_to_world first."""
         o = rays_o.reshape(-1, 3).contiguous().float(); d = rays_d.reshape(-1, 3).contiguous().float()
         c = colors.reshape(-1, 3).contiguous().float(); t = distances.reshape(-1, 1).contiguous().float()
         n = torch.zeros_like(c) if normals is None else normals.reshape(-1, 3).contiguous().float()
@@ -196,7 +207,11 @@ class SupInfoPool:
     def register_sup_info(self, pose, mask, rgb, distance, normal=None):
         """Panorama [H,W,*] maps -> supervision rays of its valid pixels, with PanoSupInfo's validity rules
         (sup_info.py:27-120): mask > 0.5 and distance > 1e-5; no depth edge (|normalised 3x3 Laplacian of the distance map|
-        < 0.01, eroded then dilated by a 3x3 box); with a normal map, surfaces seen at cos > 0.15."""
+        < 0.01, eroded then dilated by a 3x3 box); with a normal map, surfaces seen at cos > 0.15.
+        The normal map is tested against the panorama's own un-rotated directions and stored as given, while the normal loss
+        (train_conf.normal_loss_weight) takes the pool's normals as WORLD-frame vectors: the two frames agree for a pose without
+        rotation; a normal map registered under a rotated pose must be rotated first for that loss (normals_to_world, the inverse
+        of normals_to_camera)."""
         h, w, _ = rgb.shape
         dev = rgb.device
         pose = torch.as_tensor(pose, dtype=torch.float32, device=dev)
@@ -663,13 +678,18 @@ class NeRFScene:
         sync_free = self.fused_adam and self.fused_steps          # capacity-sized arrays + device-side counts: no host read-back
         use_graphs = bool(use_graphs) and sync_free and self.dp_graph_ok()
         saved_capacity = self.renderer.sample_capacity
-        if sync_free and saved_capacity is None:
-            per_rank = self.train_conf.pixel_loss_batch_size // max(self._dist()[2], 1)
+        # (a geometry phase with a normal loss runs the eager autograd step on exact-size sample arrays: its loss reads per-sample
+        #  rows, and a capacity-sized array's rows beyond the live count hold anything)
+        with_normal_loss = getattr(self.train_conf, 'normal_loss_weight', 0.) > 1e-7
+        per_rank = self.train_conf.pixel_loss_batch_size // max(self._dist()[2], 1)
+        if sync_free and saved_capacity is None and not with_normal_loss:
             self.renderer.sample_capacity = per_rank * self.TRAIN_SAMPLES_PER_RAY
         try:
             geo_optimizer = self.make_optimizer(self.nerf.geo_mlp, self.train_conf.geo_optimizer.init_lr)
             self._run_phase('geo', geo_optimizer, self.train_conf.geo_optimizer, geo_res_iters, sup_pool, callback,
                             use_graphs and self._can_fuse(), lambda i: i / app_res_iters)
+            if sync_free and saved_capacity is None and with_normal_loss:
+                self.renderer.sample_capacity = per_rank * self.TRAIN_SAMPLES_PER_RAY
             app_optimizer = self.make_optimizer(self.nerf.app_mlp, self.train_conf.app_optimizer.init_lr)
             self._run_phase('app', app_optimizer, self.train_conf.app_optimizer, app_res_iters, sup_pool, callback,
                             use_graphs, lambda i: i / app_res_iters)
@@ -768,19 +788,21 @@ class NeRFScene:
             raise NotImplementedError(f'data-parallel training needs the tcnn table layout: the {self._layout()!r} grid gradient has no '
                                       'integer exchange between ranks (perf_hashgrid_bwd_lines refuses raw fields / given units)')
 
-    def _batch(self, sup_pool, generator=None):
+    def _batch(self, sup_pool, generator=None, with_normals=False):
+        """with_normals: the batch's normals [n,3] as one more trailing element (the geometry step's normal loss)."""
         dist, rank, world = self._dist()
         self._check_dp_layout(dist)
         bs = self.train_conf.pixel_loss_batch_size
         rays, col, dep, nrm = sup_pool.rand_ray_color_data(bs, rand_mode=self.pixel_sup_rand_mode, generator=generator,
                                                             rank=rank, world_size=world)
-        return rays, col, dep, bs, (dist, rank, world)
+        return (rays, col, dep, bs, (dist, rank, world)) + ((nrm,) if with_normals else ())
 
     def _use_device_rng(self, rand, generator):
         return self.device_rng and self.fused_steps and generator is None and not rand
 
-    def _draw(self, sup_pool, want_bg):
-        """The step's batch and uniform draws from the device generator -> (rays, colors, depths, global batch, dist_info, rand)."""
+    def _draw(self, sup_pool, want_bg, with_normals=False):
+        """The step's batch and uniform draws from the device generator -> (rays, colors, depths, global batch, dist_info, rand
+        [, normals: with_normals])."""
         dist, rank, world = self._dist()
         self._check_dp_layout(dist)
         if self._rng_counter is None:
@@ -789,7 +811,7 @@ class NeRFScene:
         bs = self.train_conf.pixel_loss_batch_size
         rays, col, dep, nrm, rand = sup_pool.draw_batch(bs, self._rng_seed, self._rng_counter, rand_mode=self.pixel_sup_rand_mode,
                                                         rank=rank, world_size=world, want_bg=want_bg)
-        return rays, col, dep, bs, (dist, rank, world), rand
+        return (rays, col, dep, bs, (dist, rank, world), rand) + ((nrm,) if with_normals else ())
 
     def _finish_step(self, loss, net, optimizer, dist_info, overlap=None):
         """backward -> [one RCCL all-reduce of the flat gradient] -> Adam.  `overlap` (a callable) is run between the
@@ -875,9 +897,9 @@ class NeRFScene:
         sampler needs no density pre-pass (early_stop_eps == 0) -- marching, positions and the frozen colour field."""
         rand = dict(rand or {})
         if self._use_device_rng(rand, generator):
-            rays, gt_colors, gt_depths, bs, dist_info, rand = self._draw(sup_pool, want_bg=False)
+            rays, gt_colors, gt_depths, bs, dist_info, rand, gt_normals = self._draw(sup_pool, want_bg=False, with_normals=True)
         else:
-            rays, gt_colors, gt_depths, bs, dist_info = self._batch(sup_pool, generator)
+            rays, gt_colors, gt_depths, bs, dist_info, gt_normals = self._batch(sup_pool, generator, with_normals=True)
         if self.fused_steps and ('jitter' not in rand or 'noise' not in rand):
             # the step's two per-ray draws in one launch; under data parallelism every rank draws the GLOBAL batch's
             # values (same seed on every rank) and keeps its slice, like the index stream: the job then trains on the very
@@ -890,7 +912,7 @@ class NeRFScene:
                 st = self.renderer.stage_sample(self.nerf, self.estimator, rays.o, rays.d, rand,
                                                 with_rgb=not (self.fused_steps and self.skip_unused_color))
                 st = st if st is not None else False
-        return {'rays': rays, 'gt_depths': gt_depths, 'bs': bs, 'dist_info': dist_info, 'st': st, 'rand': rand}
+        return {'rays': rays, 'gt_depths': gt_depths, 'gt_normals': gt_normals, 'bs': bs, 'dist_info': dist_info, 'st': st, 'rand': rand}
 
     @staticmethod
     def _rand_rows(rows, n_local, dist_info, device):
@@ -1172,7 +1194,29 @@ class NeRFScene:
 
     def _can_fuse(self):
         tc = self.train_conf
-        return self.fused_steps and tc.density_loss_weight <= 1e-7 and tc.depth_loss_weight > 1e-7 and tc.distortion_loss_weight > 1e-7
+        # (a normal loss, like a density loss, is a term the fused step does not know: the eager autograd step takes it)
+        return self.fused_steps and tc.density_loss_weight <= 1e-7 and getattr(tc, 'normal_loss_weight', 0.) <= 1e-7 \
+            and tc.depth_loss_weight > 1e-7 and tc.distortion_loss_weight > 1e-7
+
+    def _normal_loss(self, st, res, gt_normals, bs):
+        """sum_i w_i.detach() (1 - n_i . n_gt[ray_i]) / bs over the kept samples of rays with a supervised normal (|n_gt| > 0), with
+        n_i = -g_i / |g_i| of the density gradient (NGPNeRF.density_and_grad_at: differentiable w.r.t. the geometry parameters, one
+        fused backward kernel) and the composite's own weights as constants.  The pool's normals are taken as WORLD-frame vectors."""
+        from .fields import unit_normals
+        if st.get('n_dev') is not None:
+            # (measured: with capacity-sized sample arrays and a device-side count the step's depth loss stopped falling -- cause not
+            #  found; train_one_episode therefore runs such a geometry phase on exact-size arrays, and a caller's own capacity is refused)
+            raise NotImplementedError('the normal loss needs exact-size sample arrays: renderer.sample_capacity is set (capacity-sized '
+                                      'arrays with a device-side count are not built for this loss)')
+        _, g = self.nerf.density_and_grad_at(st['x01'], st['sel'])
+        ray = st['ray_indices'].long()
+        n_gt = gt_normals[ray]
+        w = res['weights'].detach().reshape(-1)
+        keep = n_gt.abs().amax(dim=-1) > 0
+        w = torch.where(keep, w, torch.zeros_like(w))
+        terms = w * (1.0 - (unit_normals(g) * n_gt).sum(-1))
+        self.last_normal_batch = {'weights': w, 'grad': g.detach(), 'ray_indices': ray, 'gt_normals': gt_normals, 'keep': keep, 'bs': bs}
+        return terms.sum() / bs
 
     def train_one_step_geo(self, optimizer, sup_pool, progress, rand=None, generator=None, prefetch_next=True):
         if self._can_fuse():
@@ -1213,6 +1257,11 @@ class NeRFScene:
             rand_pts = (torch.rand(8192, 3, device=gt_depths.device) * 2. - 1.) * 0.99
             density_loss = self.nerf.query_density(rand_pts).mean()
             loss = loss + density_loss * tc.density_loss_weight
+        normal_loss_weight = getattr(tc, 'normal_loss_weight', 0.)
+        if normal_loss_weight > 1e-7:
+            normal_loss = self._normal_loss(st, res, pre['gt_normals'], bs)
+            loss = loss + normal_loss * normal_loss_weight
+            self.last_losses['normal_loss'] = normal_loss.detach()
         overlap = (lambda: setattr(self, '_geo_pre', self._geo_prefetch(sup_pool, rand, generator))) \
             if (self.overlap_comm and prefetch_next and dist_info[0] is not None) else None
         self._finish_step(loss, self.nerf.geo_mlp, optimizer, dist_info, overlap)

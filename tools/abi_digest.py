@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Digest of the C ABI declared in include/perf_hip.h: sha256 over the comment-free, whitespace-normalised text of every
+"""Digest of the C ABI declared in include/perf_hip.h (`--ext`: of its extension, include/perf_hip_ext.h, versioned by
+PERF_EXT_ABI_VERSION and recorded in include/perf_hip_ext.abi.json): sha256 over the comment-free, whitespace-normalised text of every
 `perf_*` prototype, struct and #define, in file order.  `python tools/abi_digest.py` prints {version, digest};
 `--write` records it in include/perf_hip.abi.json.  tests/test_cpu_oracle.py fails when the digest of the header differs
 from the recorded one while PERF_ABI_VERSION is unchanged: every signature change must bump the version (the load-time
@@ -13,21 +14,25 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'perf_hip.h')
 RECORD = os.path.join(ROOT, 'include', 'perf_hip.abi.json')
+EXT_HEADER = os.path.join(ROOT, 'include', 'perf_hip_ext.h')
+EXT_RECORD = os.path.join(ROOT, 'include', 'perf_hip_ext.abi.json')
 
 
-def digest(path=HEADER):
+def digest(path=HEADER, macro='PERF_ABI_VERSION'):
     text = open(path).read()
-    version = int(re.search(r'#define\s+PERF_ABI_VERSION\s+(\d+)', text).group(1))
+    version = int(re.search(r'#define\s+' + macro + r'\s+(\d+)', text).group(1))
     text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
     text = re.sub(r'//[^\n]*', ' ', text)
-    text = re.sub(r'#define\s+PERF_ABI_VERSION\s+\d+', ' ', text)
+    text = re.sub(r'#define\s+' + macro + r'\s+\d+', ' ', text)
     text = re.sub(r'\s+', ' ', text).strip()
     return {'version': version, 'digest': hashlib.sha256(text.encode()).hexdigest()}
 
 
 if __name__ == '__main__':
-    d = digest()
+    ext = '--ext' in sys.argv
+    d = digest(EXT_HEADER, 'PERF_EXT_ABI_VERSION') if ext else digest()
+    record = EXT_RECORD if ext else RECORD
     if '--write' in sys.argv:
-        json.dump(d, open(RECORD, 'w'), indent=1)
-        open(RECORD, 'a').write('\n')
+        json.dump(d, open(record, 'w'), indent=1)
+        open(record, 'a').write('\n')
     print(json.dumps(d))

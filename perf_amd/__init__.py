@@ -4,7 +4,7 @@ Host side: thin Python over a C-ABI HIP library (include/perf_hip.h).  No CPU fa
 __version__ = '0.1.0'
 
 
-def install_shims(scene=False):
+def install_shims(scene=False, sphere_field=False):
     """Put the drop-in `tinycudann`, `nerfacc` and `torch_efficient_distloss` packages on sys.path so that
     PeRF's modules/ and core_exp_runner.py import them unchanged.
 
@@ -17,7 +17,15 @@ def install_shims(scene=False):
     formulation its own NeRFScene gets over the operator shims.  Same class names, same constructor
     keywords (NeRFScene(exp_dir, train_conf=, estimator_type=, renderer_conf=); SupInfoPool().register_sup_info(pose=,
     mask=, rgb=, distance=, normal=)), same methods the runner calls (fit, render, get_pano_visibility_mask,
-    state_dict / load_state_dict, geo_check, gen_occ_grid)."""
+    state_dict / load_state_dict, geo_check, gen_occ_grid).
+
+    sphere_field=True (opt-in, independent of `scene`) lets `modules.geo_predictors.pano_joint_predictor` and
+    `modules.geo_predictors.pano_geo_refiner` load from their REAL files and then rebinds the one global `SphereDistanceField` of each
+    to perf_amd.sphere_field.SphereDistanceField.joint / .refiner -- the fused distance field in the variant that module defines.
+    `SphereDistanceField()` inside PanoJointPredictor.__call__ / PanoGeoRefiner.refine then builds the fused field; nothing else of the
+    two modules changes.  The rebound global is the bound class method, a factory, not a class: calling it is all the two modules do
+    with the name; isinstance checks, subclassing or pickling through `module.SphereDistanceField` are not served (use
+    perf_amd.sphere_field.SphereDistanceField itself for those)."""
     import os
     import sys
     d = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'shims')
@@ -25,6 +33,8 @@ def install_shims(scene=False):
         sys.path.insert(0, d)
     if scene and not any(isinstance(f, _MirrorFinder) for f in sys.meta_path):
         sys.meta_path.insert(0, _MirrorFinder())
+    if sphere_field and not any(isinstance(f, _SphereFieldFinder) for f in sys.meta_path):
+        sys.meta_path.insert(0, _SphereFieldFinder())
     return d
 
 
@@ -33,6 +43,49 @@ def uninstall_scene_shims():
     sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, _MirrorFinder)]
     for name in _MirrorFinder.SERVED:
         sys.modules.pop(name, None)
+
+
+def uninstall_sphere_field_shims():
+    import sys
+    sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, _SphereFieldFinder)]
+    for name in _SphereFieldFinder.SERVED:
+        sys.modules.pop(name, None)
+
+
+class _SphereFieldFinder:
+    """importlib finder for the two reference modules that define a SphereDistanceField (install_shims(sphere_field=True)): the module
+    is found and executed by the ordinary path machinery; its loader is wrapped so that ONE global is rebound afterwards."""
+    SERVED = {
+        'modules.geo_predictors.pano_joint_predictor': 'joint',
+        'modules.geo_predictors.pano_geo_refiner': 'refiner',
+    }
+
+    def find_spec(self, fullname, path=None, target=None):
+        if fullname not in self.SERVED:
+            return None
+        from importlib.machinery import PathFinder
+        spec = PathFinder.find_spec(fullname, path)
+        if spec is None or spec.loader is None:
+            return None
+        spec.loader = _RebindLoader(spec.loader, self.SERVED[fullname])
+        return spec
+
+
+class _RebindLoader:
+    def __init__(self, inner, variant):
+        self._inner, self._variant = inner, variant
+
+    def create_module(self, spec):
+        return self._inner.create_module(spec)
+
+    def exec_module(self, module):
+        self._inner.exec_module(module)
+        if 'SphereDistanceField' in module.__dict__:
+            from .sphere_field import SphereDistanceField
+            module.SphereDistanceField = getattr(SphereDistanceField, self._variant)
+
+    def __getattr__(self, name):             # (get_code, get_source, is_package, ...: the real loader's)
+        return getattr(self._inner, name)
 
 
 class _MirrorFinder:

@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(HERE, 'libperf_hip.so')
 
 ABI_VERSION = 16         # PERF_ABI_VERSION of include/perf_hip.h this binding was written against
 EXT_ABI_VERSION = 1      # PERF_EXT_ABI_VERSION of include/perf_hip_ext.h (entry points added after perf_hip.h was frozen)
+SPHERE_ABI_VERSION = 1   # PERF_SPHERE_ABI_VERSION of include/perf_hip_sphere.h (the sphere distance field)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -144,6 +145,14 @@ _SIGS_EXT = {
     'perf_field_grad_x_bwd': (c_int, [POINTER(GridDesc), POINTER(MlpDesc), P, P, P, P, POINTER(c_float), P, P, P, P, c_int64, c_int64, P, c_int, P]),
 }
 
+# include/perf_hip_sphere.h: the sphere distance field, exported from the same library, versioned on its own (perf_sphere_version)
+_SIGS_SPHERE = {
+    'perf_sphere_version': (c_int, []),
+    'perf_sphere_field_fwd': (c_int, [POINTER(GridDesc), P, P, P, P, P, c_int64, P]),
+    'perf_sphere_field_bwd_workspace_bytes': (c_int64, [POINTER(GridDesc), c_int64]),
+    'perf_sphere_field_bwd': (c_int, [POINTER(GridDesc), P, P, P, P, P, P, P, c_int64, c_int64, P]),
+}
+
 _lib = None
 
 
@@ -159,7 +168,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
@@ -171,6 +180,9 @@ def load():
                         'rebuild with `python -m perf_amd.build --force`')
     if lib.perf_ext_version() != EXT_ABI_VERSION:
         raise PerfError(f'{LIB_PATH} has extension ABI version {lib.perf_ext_version()}, this binding expects {EXT_ABI_VERSION}: '
+                        'rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_sphere_version() != SPHERE_ABI_VERSION:
+        raise PerfError(f'{LIB_PATH} has sphere-field ABI version {lib.perf_sphere_version()}, this binding expects {SPHERE_ABI_VERSION}: '
                         'rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):

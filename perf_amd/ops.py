@@ -553,6 +553,51 @@ def field_grad_x_bwd(grid: GridConfig, mlp: MlpConfig, x01, sel, w16, inv_extent
     return grad
 
 
+def sphere_net_params(n_levels: int) -> int:
+    """Length of the flat fp32 network buffer of the sphere distance field (include/perf_hip_sphere.h: [W1 | b1 | W2 | b2 | w3 | b3])."""
+    return 64 * (3 + 2 * n_levels) + 64 + 64 * 64 + 64 + 64 + 1
+
+
+def sphere_field_fwd(grid: GridConfig, table, net, dirs, want_grad=True):
+    """The sphere distance field in one kernel (perf_sphere_field_fwd, include/perf_hip_sphere.h): -> (raw [n], g [n,3] or None) with
+    raw = -(MLP([u; enc(0.49 u + 0.49)])) and g = d raw / du, all fp32.  table: the fp32 grid table, net: the flat fp32 network buffer
+    (sphere_net_params values), dirs: [n,3].  want_grad=False forms no gradient (the raw values are bit-identical).  No graph is
+    recorded."""
+    n = dirs.shape[0]
+    if net.numel() != sphere_net_params(grid.n_levels) or table.numel() != grid.n_params:
+        raise _lib.PerfError(f'sphere_field_fwd: net has {net.numel()} values, table {table.numel()}; the grid asks for '
+                             f'{sphere_net_params(grid.n_levels)} and {grid.n_params}')
+    raw = torch.empty(n, dtype=torch.float32, device=dirs.device)
+    g = torch.empty(n, 3, dtype=torch.float32, device=dirs.device) if want_grad else None
+    gd = grid.desc()
+    _call('perf_sphere_field_fwd', ctypes.byref(gd), _p(_f32(table, 'table')), _p(_f32(net, 'net')), _p(_f32(dirs, 'dirs')), _p(raw), _p(g), n,
+          _stream())
+    return raw, g
+
+
+def sphere_field_bwd(grid: GridConfig, table, net, dirs, draw=None, dgrad=None, grad=None, ws=None):
+    """Backward of sphere_field_fwd with respect to the parameters (perf_sphere_field_bwd): given draw = dL/d raw [n] and dgrad = dL/dg
+    [n,3] (either may be None, not both) -> flat fp32 gradient [network | table], OVERWRITTEN in full (zeros for an empty batch).  One
+    kernel; the network part is deterministic, the table part is scattered with fp32 atomics (order-dependent in its last bits).
+    ws (a Workspace): the holder of the call's scratch memory -- its owner is the field (SphereDistanceField.bwd_workspace)."""
+    n = dirs.shape[0]
+    n_net = sphere_net_params(grid.n_levels)
+    dev = dirs.device
+    if net.numel() != n_net or table.numel() != grid.n_params:
+        raise _lib.PerfError(f'sphere_field_bwd: net has {net.numel()} values, table {table.numel()}; the grid asks for {n_net} and {grid.n_params}')
+    if grad is None:
+        grad = torch.empty(n_net + grid.n_params, dtype=torch.float32, device=dev)
+    gd = grid.desc()
+    nbytes = _lib.load().perf_sphere_field_bwd_workspace_bytes(ctypes.byref(gd), n)
+    if nbytes < 0:
+        _lib.check(-1, 'perf_sphere_field_bwd_workspace_bytes')
+    block = (ws or Workspace()).get(nbytes, dev)
+    _call('perf_sphere_field_bwd', ctypes.byref(gd), _p(_f32(table, 'table')), _p(_f32(net, 'net')), _p(_f32(dirs, 'dirs')),
+          _p(None if draw is None else _f32(draw, 'draw')), _p(None if dgrad is None else _f32(dgrad, 'dgrad')), _p(grad), _p(block),
+          block.numel() * 4, n, _stream())
+    return grad
+
+
 def normal_composite(weights, grad, packed):
     """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
     R = packed.shape[0]

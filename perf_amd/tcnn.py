@@ -291,7 +291,9 @@ class Encoding(nn.Module):
     """tcnn.Encoding (HashGrid, Linear or Smoothstep interpolation), fp32 table, first-order autograd
     w.r.t. the table and the input."""
 
-    def __init__(self, n_input_dims, encoding_config, seed=DEFAULT_SEED, dtype=None):
+    def __init__(self, n_input_dims, encoding_config, seed=DEFAULT_SEED, dtype=None, device=None):
+        """device: where the table is created (default: the current HIP device; without one the constructor raises).  A table on the
+        CPU can be inspected, saved and loaded; forward needs a HIP tensor."""
         super().__init__()
         if n_input_dims != 3:
             raise ValueError('the gfx950 hash grid is built for 3 input dims')
@@ -301,7 +303,7 @@ class Encoding(nn.Module):
         self.n_output_dims = self.grid.n_output_dims
         # tcnn hands back half by default; dtype=torch.float32 / 'fp32' keeps the fp32 result
         self.out_dtype = torch.float32 if dtype in ('fp32', torch.float32) else ops.torch_dtype(dtype or 'fp16')
-        self.params = nn.Parameter(_init_params(None, self.grid, seed, _default_device()))
+        self.params = nn.Parameter(_init_params(None, self.grid, seed, device if device is not None else _default_device()))
 
     def forward(self, x):
         x = x.reshape(-1, self.n_input_dims).contiguous().float()

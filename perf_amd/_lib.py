@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(HERE, 'libperf_hip.so')
 ABI_VERSION = 16         # PERF_ABI_VERSION of include/perf_hip.h this binding was written against
 EXT_ABI_VERSION = 1      # PERF_EXT_ABI_VERSION of include/perf_hip_ext.h (entry points added after perf_hip.h was frozen)
 SPHERE_ABI_VERSION = 1   # PERF_SPHERE_ABI_VERSION of include/perf_hip_sphere.h (the sphere distance field)
+PAIR_ABI_VERSION = 1     # PERF_PAIR_ABI_VERSION of include/perf_hip_pair.h (the pair table of two fields with one grid geometry)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -153,6 +154,15 @@ _SIGS_SPHERE = {
     'perf_sphere_field_bwd': (c_int, [POINTER(GridDesc), P, P, P, P, P, P, P, c_int64, c_int64, P]),
 }
 
+# include/perf_hip_pair.h: the pair table, exported from the same library, versioned on its own (perf_pair_version)
+_SIGS_PAIR = {
+    'perf_pair_version': (c_int, []),
+    'perf_pair_fill': (c_int, [P, c_int, P, c_int64, P]),
+    'perf_hashgrid_fwd_pair': (c_int, [POINTER(GridDesc), P, P, P, P, c_int64, P, c_int, P]),
+    'perf_adam_step_dev_pair': (c_int, [P, P, P, P, P, c_int64, c_int, P, P, P, c_float, c_float, c_float, c_int, P, P, c_int, c_int64, P]),
+    'perf_mlp_fwd_rows': (c_int, [POINTER(MlpDesc), P, P, P, c_int64, P, P, c_int64, P, c_int, P]),
+}
+
 _lib = None
 
 
@@ -168,7 +178,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
@@ -183,6 +193,9 @@ def load():
                         'rebuild with `python -m perf_amd.build --force`')
     if lib.perf_sphere_version() != SPHERE_ABI_VERSION:
         raise PerfError(f'{LIB_PATH} has sphere-field ABI version {lib.perf_sphere_version()}, this binding expects {SPHERE_ABI_VERSION}: '
+                        'rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_pair_version() != PAIR_ABI_VERSION:
+        raise PerfError(f'{LIB_PATH} has pair-table ABI version {lib.perf_pair_version()}, this binding expects {PAIR_ABI_VERSION}: '
                         'rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):

@@ -3,6 +3,7 @@
 // fully coalesced accesses.
 #include <stdarg.h>
 #include <stdio.h>
+#include <type_traits>
 #include "common.hpp"
 #include "step_book_device.hpp"
 
@@ -31,13 +32,23 @@ __global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ src
 
 // torch.optim.Adam (foreach form): m = lerp(m, g, 1-b1); v = v*b2 + (1-b2)*g*g;
 // p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
-template <typename T16, bool W16>
+// PAIR (perf_adam_step_dev_pair, include/perf_hip_pair.h): beside the 16-bit working copy, every TABLE element (index >= n_net, n_net even)
+// is also stored into its field's half of a pair table: entry e = (index - n_net) / 2 is the 32-bit word pair[2 e + field].
+struct NoPairOut {};
+struct PairOut {
+    uint32_t* pair;
+    int64_t n_net;
+    int32_t field;
+};
+
+template <typename T16, bool W16, bool PAIR = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                    float* __restrict__ g, uint16_t* __restrict__ w16, int64_t n,
                                                    float one_minus_b1, float b2, float one_minus_b2, float step_size,
                                                    float inv_bc2_sqrt, float eps, int zero_grad,
                                                    const int32_t* __restrict__ step_dev, const float* __restrict__ lr_dev,
-                                                   const int64_t* __restrict__ gate_dev, int32_t* __restrict__ clear_flag) {
+                                                   const int64_t* __restrict__ gate_dev, int32_t* __restrict__ clear_flag,
+                                                   std::conditional_t<PAIR, PairOut, NoPairOut> po) {
     __shared__ float sc[2];
     if (clear_flag && blockIdx.x == 0 && threadIdx.x == 0) clear_flag[0] = 0;      // (taken or not: perf_adam_step_dev)
     if (gate_dev && gate_dev[0] <= 0) return;       // batch without samples: the reference skips the step (nerf.py:204-206)
@@ -62,6 +73,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
     pi = pi - step_size * (mi / denom);
     m[i] = mi; v[i] = vi; p[i] = pi;
     if (W16) w16[i] = T16::one(pi);
+    if constexpr (PAIR) {
+        if (i >= po.n_net) reinterpret_cast<uint16_t*>(po.pair)[(((i - po.n_net) >> 1) * 2 + po.field) * 2 + ((i - po.n_net) & 1)] = T16::one(pi);
+    }
     if (zero_grad) g[i] = 0.f;
 }
 
@@ -69,13 +83,14 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
 // issued BEFORE the scalar prologue (gate, step count -> bias corrections, learning rate: a dependent chain of device reads and
 // two powf that every workgroup repeats): the 199 MB of a 3.3 M-entry table's step stream while it runs.  Element for element
 // the arithmetic of adam_kernel.
-template <typename T16, bool W16>
+template <typename T16, bool W16, bool PAIR = false>
 __global__ __launch_bounds__(256) void adam4_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                     float* __restrict__ g, uint16_t* __restrict__ w16, int64_t n,
                                                     float one_minus_b1, float b2, float one_minus_b2, float step_size,
                                                     float inv_bc2_sqrt, float eps, int zero_grad,
                                                     const int32_t* __restrict__ step_dev, const float* __restrict__ lr_dev,
-                                                    const int64_t* __restrict__ gate_dev, int32_t* __restrict__ clear_flag) {
+                                                    const int64_t* __restrict__ gate_dev, int32_t* __restrict__ clear_flag,
+                                                    std::conditional_t<PAIR, PairOut, NoPairOut> po) {
     __shared__ float sc[2];
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     const int cnt = i + 3 < n ? 4 : (i < n ? (int)(n - i) : 0);
@@ -114,11 +129,19 @@ __global__ __launch_bounds__(256) void adam4_kernel(float* __restrict__ p, float
         *reinterpret_cast<float4*>(v + i) = make_float4(vi[0], vi[1], vi[2], vi[3]);
         *reinterpret_cast<float4*>(p + i) = make_float4(pi[0], pi[1], pi[2], pi[3]);
         if (W16) *reinterpret_cast<uint2*>(w16 + i) = make_uint2(T16::pack(pi[0], pi[1]), T16::pack(pi[2], pi[3]));
+        if constexpr (PAIR) {       // (i is a multiple of 4 and n_net even: elements (i, i + 1) and (i + 2, i + 3) are whole entries, or network weights)
+            if (i >= po.n_net) po.pair[(i - po.n_net) + po.field] = T16::pack(pi[0], pi[1]);
+            if (i + 2 >= po.n_net) po.pair[(i + 2 - po.n_net) + po.field] = T16::pack(pi[2], pi[3]);
+        }
         if (zero_grad) *reinterpret_cast<float4*>(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
         for (int k = 0; k < cnt; ++k) {
             m[i + k] = mi[k]; v[i + k] = vi[k]; p[i + k] = pi[k];
             if (W16) w16[i + k] = T16::one(pi[k]);
+            if constexpr (PAIR) {
+                const int64_t t = i + k - po.n_net;
+                if (t >= 0) reinterpret_cast<uint16_t*>(po.pair)[((t >> 1) * 2 + po.field) * 2 + (t & 1)] = T16::one(pi[k]);
+            }
             if (zero_grad) g[i + k] = 0.f;
         }
     }
@@ -311,18 +334,47 @@ static int adam_launch(float* p, float* m, float* v, float* g, void* w16, int64_
                             reinterpret_cast<uintptr_t>(g) | (reinterpret_cast<uintptr_t>(w16) << 1);
     if ((align & 15) == 0 && n >= 1024) {       // four elements per thread
         dim3 g4((unsigned)div_up(div_up(n, 4), 256));
-        if (!w16) hipLaunchKernelGGL((adam4_kernel<BF16, false>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)nullptr, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag);
-        else if (dtype == PERF_DTYPE_BF16) hipLaunchKernelGGL((adam4_kernel<BF16, true>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag);
-        else if (dtype == PERF_DTYPE_FP16) hipLaunchKernelGGL((adam4_kernel<FP16, true>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag);
+        if (!w16) hipLaunchKernelGGL((adam4_kernel<BF16, false>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)nullptr, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, NoPairOut{});
+        else if (dtype == PERF_DTYPE_BF16) hipLaunchKernelGGL((adam4_kernel<BF16, true>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, NoPairOut{});
+        else if (dtype == PERF_DTYPE_FP16) hipLaunchKernelGGL((adam4_kernel<FP16, true>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, NoPairOut{});
         else { set_error("perf_adam_step: bad dtype %d", dtype); return PERF_E_INVALID; }
         PERF_LAUNCH_CHECK("perf_adam_step");
         return PERF_OK;
     }
-    if (!w16) hipLaunchKernelGGL((adam_kernel<BF16, false>), gr, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)nullptr, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag);
-    else if (dtype == PERF_DTYPE_BF16) hipLaunchKernelGGL((adam_kernel<BF16, true>), gr, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag);
-    else if (dtype == PERF_DTYPE_FP16) hipLaunchKernelGGL((adam_kernel<FP16, true>), gr, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag);
+    if (!w16) hipLaunchKernelGGL((adam_kernel<BF16, false>), gr, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)nullptr, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, NoPairOut{});
+    else if (dtype == PERF_DTYPE_BF16) hipLaunchKernelGGL((adam_kernel<BF16, true>), gr, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, NoPairOut{});
+    else if (dtype == PERF_DTYPE_FP16) hipLaunchKernelGGL((adam_kernel<FP16, true>), gr, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, step_size, inv_bc2_sqrt, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, NoPairOut{});
     else { set_error("perf_adam_step: bad dtype %d", dtype); return PERF_E_INVALID; }
     PERF_LAUNCH_CHECK("perf_adam_step");
+    return PERF_OK;
+}
+
+extern "C" int perf_adam_step_dev_pair(float* p, float* m, float* v, float* g, void* w16, int64_t n, int dtype, const int32_t* step_dev,
+                                       const float* lr_dev, const int64_t* gate_dev, float beta1, float beta2, float eps, int zero_grad,
+                                       int32_t* clear_flag, void* pair, int field, int64_t n_net, void* stream) {
+    PERF_REQUIRE(step_dev && lr_dev, "perf_adam_step_dev_pair: NULL scalar pointers");
+    PERF_REQUIRE(n > 0, "perf_adam_step_dev_pair: n < 1");
+    PERF_REQUIRE(p && m && v && g && w16 && pair, "perf_adam_step_dev_pair: NULL pointer");
+    PERF_REQUIRE(field == 0 || field == 1, "perf_adam_step_dev_pair: field %d is neither 0 nor 1", field);
+    PERF_REQUIRE(n_net >= 0 && n_net <= n && (n_net & 1) == 0 && ((n - n_net) & 1) == 0, "perf_adam_step_dev_pair: n_net and n - n_net must be even, 0 <= n_net <= n");
+    PERF_REQUIRE(((uintptr_t)pair & 7u) == 0, "perf_adam_step_dev_pair: the pair table must be 8-byte aligned");
+    PERF_REQUIRE(dtype == PERF_DTYPE_BF16 || dtype == PERF_DTYPE_FP16, "perf_adam_step_dev_pair: bad dtype %d", dtype);
+    const float omb1 = 1.0f - beta1, omb2 = 1.0f - beta2;
+    const PairOut po{(uint32_t*)pair, n_net, field};
+    const uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+                            reinterpret_cast<uintptr_t>(g) | (reinterpret_cast<uintptr_t>(w16) << 1);
+    dim3 b(256);
+    // (the scalars come from the device: the host-side step size and bias correction of adam_launch are not used)
+    if ((align & 15) == 0 && n >= 1024) {       // four elements per thread, as adam_launch
+        dim3 g4((unsigned)div_up(div_up(n, 4), 256));
+        if (dtype == PERF_DTYPE_BF16) hipLaunchKernelGGL((adam4_kernel<BF16, true, true>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, 0.f, 1.f, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, po);
+        else hipLaunchKernelGGL((adam4_kernel<FP16, true, true>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, 0.f, 1.f, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, po);
+    } else {
+        dim3 gr((unsigned)div_up(n, 256));
+        if (dtype == PERF_DTYPE_BF16) hipLaunchKernelGGL((adam_kernel<BF16, true, true>), gr, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, 0.f, 1.f, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, po);
+        else hipLaunchKernelGGL((adam_kernel<FP16, true, true>), gr, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, 0.f, 1.f, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, po);
+    }
+    PERF_LAUNCH_CHECK("perf_adam_step_dev_pair");
     return PERF_OK;
 }
 

@@ -199,13 +199,20 @@ struct FusedIn {
     uint32_t* feat_out;
 };
 struct NoFusedIn {};
+// ROWS: the features of sample i are row index[i] of `stride` rows per level (ops.IndexedFeat: the kept samples of a batch as rows of
+// the marched samples' feature array -- no compacted copy is made); feat's own stride n is not used then
+struct RowsIn {
+    const int32_t* index;
+    int64_t stride;
+};
 
-template <typename T16, int NH, int KS, bool FUSED>
+template <typename T16, int NH, int KS, bool FUSED, bool ROWS = false>
 __global__ __launch_bounds__(256) void mlp_fwd_kernel(MlpParams mp, const uint16_t* __restrict__ w,
                                                       const uint32_t* __restrict__ feat,
                                                       const uint8_t* __restrict__ sel, float* __restrict__ out,
                                                       int64_t n, const int64_t* __restrict__ n_dev,
-                                                      std::conditional_t<FUSED, FusedIn, NoFusedIn> fz) {
+                                                      std::conditional_t<FUSED, FusedIn, std::conditional_t<ROWS, RowsIn, NoFusedIn>> fz) {
+    static_assert(!(FUSED && ROWS), "the fused kernel forms its features itself");
     using L = Layout<NH, KS>;
     const int64_t n_live = live_count(n, n_dev);        // n stays the stride of the level-major features
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -288,6 +295,66 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(MlpParams mp, const uint16
                     b1[s][i] = pair;
                 }
             layers(si, valid, b1, (valid && sel) ? (float)sel[si] : 1.0f);
+        }
+    } else if constexpr (ROWS) {
+        if (tile >= n_tiles) return;
+        const int64_t last_tile = n_tiles - 1;
+        auto row_of = [&](int64_t tile_unclamped) {
+            const int64_t tl = tile_unclamped < last_tile ? tile_unclamped : last_tile;
+            const int64_t si = tl * kTile + c;
+            return fz.index[si < n_live ? si : n_live - 1];
+        };
+        if (fz.stride <= kMaxFastStride && mp.n_levels == 8 * KS) {      // (uniform)
+            // as the plain fast path below, one tile ahead on alternating register sets; the ROW of a request is fetched one request
+            // earlier still, so that no request waits for its row
+            auto request = [&](int64_t tile_unclamped, int32_t row, TileIn& t) {
+                const int64_t tl = tile_unclamped < last_tile ? tile_unclamped : last_tile;
+                const int64_t si = tl * kTile + c;
+                const int64_t sc = si < n_live ? si : n_live - 1;
+                const uint32_t off = 4u * (uint32_t)((int64_t)row + (int64_t)h * fz.stride);
+#pragma unroll
+                for (int s = 0; s < KS; ++s)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const unsigned char* base = reinterpret_cast<const unsigned char*>(feat) + (int64_t)(8 * s + 2 * i) * fz.stride * 4;
+                        t.b1[s][i] = *reinterpret_cast<const uint32_t*>(base + off);
+                    }
+                t.sv = *(sel ? sel + sc : reinterpret_cast<const uint8_t*>(feat));
+            };
+            auto process = [&](int64_t tl, const TileIn& t) __attribute__((always_inline)) {
+                const int64_t si = tl * kTile + c;
+                layers(si, si < n_live, t.b1, sel ? (float)t.sv : 1.0f);
+            };
+            TileIn ta, tb;
+            request(tile, row_of(tile), ta);
+            int32_t row = row_of(tile + tile_step);
+            for (;;) {
+                request(tile + tile_step, row, tb);
+                row = row_of(tile + 2 * tile_step);
+                process(tile, ta);
+                tile += tile_step;
+                if (tile >= n_tiles) break;
+                request(tile + tile_step, row, ta);
+                row = row_of(tile + 2 * tile_step);
+                process(tile, tb);
+                tile += tile_step;
+                if (tile >= n_tiles) break;
+            }
+        } else {
+            for (; tile < n_tiles; tile += tile_step) {
+                const int64_t si = tile * kTile + c;
+                const bool valid = si < n_live;
+                const int64_t row = row_of(tile);
+                u32x4 b1[KS];
+#pragma unroll
+                for (int s = 0; s < KS; ++s)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int level = 8 * s + 2 * i + h;
+                        b1[s][i] = (valid && level < mp.n_levels) ? feat[(int64_t)level * fz.stride + row] : 0u;
+                    }
+                layers(si, valid, b1, (valid && sel) ? (float)sel[si] : 1.0f);
+            }
         }
     } else if (n <= kMaxFastStride && mp.n_levels == 8 * KS) {      // (uniform) see kMaxFastStride
         // one tile ahead on alternating register sets, as in mlp_bwd_kernel: a request is unconditional, issues a fixed number
@@ -769,6 +836,13 @@ static void launch_fwd(int blocks, hipStream_t st, MlpParams mp, const uint16_t*
 }
 
 template <typename T16, int NH, int KS>
+static void launch_fwd_rows(int blocks, hipStream_t st, MlpParams mp, const uint16_t* w, const uint32_t* feat, const int32_t* feat_index,
+                            int64_t feat_stride, const uint8_t* sel, float* out, int64_t n, const int64_t* n_dev) {
+    constexpr int lds_bytes = Layout<NH, KS>::n_fwd * 1024;
+    mlp_fwd_kernel<T16, NH, KS, false, true><<<dim3(blocks), dim3(256), lds_bytes, st>>>(mp, w, feat, sel, out, n, n_dev, RowsIn{feat_index, feat_stride});
+}
+
+template <typename T16, int NH, int KS>
 static void launch_fused(int blocks, hipStream_t st, MlpParams mp, const uint16_t* w, const uint8_t* sel, float* out, int64_t n,
                          const int64_t* n_dev, FusedIn fz) {
     constexpr int lds_bytes = Layout<NH, KS>::n_fwd * 1024;
@@ -809,6 +883,16 @@ static void dispatch_fwd(int nh, int ks, Args... a) {
     else if (ks == 1) launch_fwd<T16, 2, 1>(a...);
     else if (ks == 2) launch_fwd<T16, 2, 2>(a...);
     else launch_fwd<T16, 2, 3>(a...);
+}
+
+template <typename T16, typename... Args>
+static void dispatch_fwd_rows(int nh, int ks, Args... a) {
+    if (nh == 1 && ks == 1) launch_fwd_rows<T16, 1, 1>(a...);
+    else if (nh == 1 && ks == 2) launch_fwd_rows<T16, 1, 2>(a...);
+    else if (nh == 1) launch_fwd_rows<T16, 1, 3>(a...);
+    else if (ks == 1) launch_fwd_rows<T16, 2, 1>(a...);
+    else if (ks == 2) launch_fwd_rows<T16, 2, 2>(a...);
+    else launch_fwd_rows<T16, 2, 3>(a...);
 }
 
 template <typename T16, typename... Args>

@@ -5,6 +5,7 @@ The arithmetic of the two tcnn networks is in perf_amd.tcnn; what this file adds
 (ngp_nerf.py:136-176): aabb normalisation, the 0<x<1 selector, trunc_exp on the density logit -- fused here
 into the position and MLP-epilogue kernels (PERF_ACT_EXP + selector), so a density query is three launches.
 """
+import weakref
 from typing import List, Union
 
 import numpy as np
@@ -96,6 +97,34 @@ def unit_normals(g):
     return torch.where(ok, -u / nrm, torch.zeros_like(u))
 
 
+class PairTable:
+    """The pair table of two fields over ONE grid geometry (include/perf_hip_pair.h): entry e = {field 0's packed features, field 1's}, so
+    that one gather per corner encodes both fields (ops.hashgrid_fwd_pair).  A half is current when it was written from the working copy
+    its network holds now: keyed like tcnn.NetworkWithInputEncoding.working_copy (master's data_ptr, _version, dtype) plus the network
+    itself.  A stale half is refilled (ops.pair_fill) before use, never read; the fused Adam of a network bound to a half refreshes it
+    in its own launch (ops.adam_step_dev(pair=...)) and marks it current (adopted).  The plain working copies stay what every other
+    consumer reads."""
+
+    def __init__(self, grid, device):
+        self.buf = ops.pair_table(grid, device)
+        self.keys = [None, None]
+
+    @staticmethod
+    def _key(net):
+        return (weakref.ref(net), net._w16_key)
+
+    def refresh(self, field, net):
+        w16 = net.working_copy()
+        key = self._key(net)
+        if self.keys[field] != key:
+            ops.pair_fill(self.buf, field, w16[net.mlp.n_params:])
+            self.keys[field] = key
+
+    def adopted(self, field, net):
+        """The launch that refreshed net's working copy wrote this half as well (call after net.set_working_copy)."""
+        self.keys[field] = self._key(net)
+
+
 class _DensityNet(tcnn.NetworkWithInputEncoding):
     """geo network whose kernel epilogue applies trunc_exp(y - shift) * selector."""
 
@@ -162,6 +191,45 @@ class NGPNeRF(nn.Module):
         net = self.geo_mlp
         sig, feat = ops.field_infer(net.grid, net.mlp, x01, sel, net.working_copy(), n_dev=n_dev, want_features=True)
         return sig[:, 0], feat
+
+    # -- the pair table: both fields' grids have one geometry, a training step encodes the same positions through both ------------
+    def pair_supported(self):
+        """Both grids equal, in tcnn's layout, at most 16 levels, one 16-bit type: what ops.hashgrid_fwd_pair is built for."""
+        ga, gb = self.geo_mlp.grid, self.app_mlp.grid
+        key = lambda g: (g.n_levels, g.log2_hashmap_size, g.base_resolution, g.per_level_scale, g.interpolation, g.layout)
+        return key(ga) == key(gb) and ga.layout == 'tcnn' and ga.n_levels <= 16 and self.geo_mlp.dtype_name == self.app_mlp.dtype_name
+
+    def use_pair(self, on):
+        """Bind (or unbind) the two networks to the halves of this field's pair table: a bound network's fused Adam keeps its half
+        current.  -> the PairTable with both halves current, or None.  Whether a half is refilled (ops.pair_fill) is decided HERE, on
+        the host, like the re-cast of a working copy: a captured step graph contains a fill only if a half was stale at capture, so a
+        captured step assumes both halves current at capture time and kept current by the bound networks' Adam launches alone; a
+        working copy re-cast outside the graph (reset_geo, load_state_dict) needs a new capture, as it does for the working copy."""
+        if not on:
+            self.geo_mlp._pair_half = self.app_mlp._pair_half = None
+            return None
+        pt = self.__dict__.get('_pair')
+        if pt is None or pt.buf.shape[0] != self.geo_mlp.grid.total or pt.buf.device != self.geo_mlp.params.device:
+            pt = self.__dict__['_pair'] = PairTable(self.geo_mlp.grid, self.geo_mlp.params.device)
+        for field, net in enumerate((self.geo_mlp, self.app_mlp)):
+            net._pair_half = (pt, field)
+            pt.refresh(field, net)
+        return pt
+
+    @torch.no_grad()
+    def density_with_pair_features(self, x01, sel, pair, n_dev=None):
+        """density_with_features by ONE pair encode: -> (sigma [n], ops.PairFeat(density features, colour features)), each to the bit
+        what the field's own encode gives."""
+        net = self.geo_mlp
+        fa, fb = ops.hashgrid_fwd_pair(net.grid, x01, pair.buf, net.dtype_name, n_dev=n_dev)
+        sig = ops.mlp_fwd(net.mlp, net.working_copy()[:net.mlp.n_params], fa, sel, n_dev=n_dev)
+        return sig[:, 0], ops.PairFeat(fa, fb)
+
+    @torch.no_grad()
+    def rgb_from_features(self, feat, sel, n_dev=None):
+        """The colour network on already encoded colour features ([L, n, 2] or an ops.IndexedFeat), without gradient."""
+        net = self.app_mlp
+        return ops.mlp_fwd(net.mlp, net.working_copy()[:net.mlp.n_params], feat, sel, n_dev=n_dev)
 
     def _inv_extent(self):
         a = self._aabb_host

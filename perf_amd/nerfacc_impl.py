@@ -116,7 +116,7 @@ _UPDATE_CALLS = {}
 
 class Samples:
     """Packed samples of one ray batch (see OccGridEstimator.sampling_ex)."""
-    __slots__ = ('ray_indices', 't_starts', 't_ends', 'packed', 'sig', 'x01', 'sel', 'n_dev', 'n_marched_dev', 'feat')
+    __slots__ = ('ray_indices', 't_starts', 't_ends', 'packed', 'sig', 'x01', 'sel', 'n_dev', 'n_marched_dev', 'feat', 'feat_b')
 
     def __init__(self):
         for k in self.__slots__:
@@ -254,10 +254,16 @@ class OccGridEstimator(nn.Module):
             sig = None
             if compacts:
                 sig, feat = _sig_feat(sigma_points_fn(x01, sel, total))
+                feat_b = None
+                if isinstance(feat, ops.PairFeat):        # (a pair encode: the second field's features ride on the same rows)
+                    feat, feat_b = feat.a, feat.b
                 new_counts = ops.visibility_count(sig, ts, te, packed, early_stop_eps)
-                out = ops.compact_prefix(packed, new_counts, ts, te, sig, capacity=capacity, x01=x01, sel=sel, feat=feat)
+                out = ops.compact_prefix(packed, new_counts, ts, te, sig, capacity=capacity, x01=x01, sel=sel, feat=feat,
+                                         index_features=True if feat_b is not None else None)
                 ri, ts, te, sig, packed, total, x01, sel = out[:8]
                 sm.feat = out[8] if feat is not None else None
+                if feat_b is not None:
+                    sm.feat_b = ops.IndexedFeat(feat_b, sm.feat.index)
             sm.n_dev = total
         else:
             out = ops.occ_march(rays_o, rays_d, t0, self.occ_bits(), res, aabb, float(far_plane), float(render_step_size), max_steps,

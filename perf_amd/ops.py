@@ -110,10 +110,21 @@ def adam_step(p, m, v, g, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, w16=None, 
               _stream())
 
 
-def adam_step_dev(p, m, v, g, step_dev, lr_dev, beta1=0.9, beta2=0.999, eps=1e-8, w16=None, zero_grad=False, gate=None, clear_flag=None):
+def adam_step_dev(p, m, v, g, step_dev, lr_dev, beta1=0.9, beta2=0.999, eps=1e-8, w16=None, zero_grad=False, gate=None, clear_flag=None,
+                  pair=None):
     """gate: device int64 [1]; the update is skipped when it holds 0 (a batch without samples).  clear_flag (device int32 [1]): zeroed by
-    the launch, taken or not -- how the overflow flag is consumed when the bookkeeping rode in the repair launch (field_bwd(book=...))."""
+    the launch, taken or not -- how the overflow flag is consumed when the bookkeeping rode in the repair launch (field_bwd(book=...)).
+    pair = (pair table, field, n_net): p is [network (n_net) | table] and the step keeps that field's half of the pair table current too."""
     code = dtype_code(w16.dtype) if w16 is not None else 0
+    if pair is not None:
+        # (perf_adam_step_dev_pair: the same step, which also stores every table entry into its field's half of the pair table)
+        table, field, n_net = pair
+        if w16 is None or table.dtype != torch.int32 or table.numel() != p.numel() - n_net:
+            raise _lib.PerfError('adam_step_dev: pair = (int32 [entries, 2] pair table, field, n_net) needs w16 and a pair table of (n - n_net) / 2 entries')
+        _call('perf_adam_step_dev_pair', _p(_f32(p, 'p')), _p(_f32(m, 'm')), _p(_f32(v, 'v')), _p(_f32(g, 'g')), _p(w16),
+              p.numel(), code, _p(step_dev), _p(lr_dev), _nd(gate), float(beta1), float(beta2), float(eps), int(bool(zero_grad)),
+              _p(clear_flag), _p(table), int(field), int(n_net), _stream())
+        return
     _call('perf_adam_step_dev', _p(_f32(p, 'p')), _p(_f32(m, 'm')), _p(_f32(v, 'v')), _p(_f32(g, 'g')), _p(w16),
           p.numel(), code, _p(step_dev), _p(lr_dev), _nd(gate), float(beta1), float(beta2), float(eps), int(bool(zero_grad)),
           _p(clear_flag), _stream())
@@ -210,6 +221,41 @@ def hashgrid_fwd2(grid: GridConfig, x01, table16_a, table16_b):
     d = grid.desc()
     _call('perf_hashgrid_fwd2', ctypes.byref(d), _p(_f32(x01, 'x01')), _p(table16_a), _p(table16_b), _p(fa), _p(fb), n,
           dtype_code(table16_a.dtype), _stream())
+    return fa, fb
+
+
+def pair_table(grid: GridConfig, device):
+    """An (uninitialised) pair table of two fields over `grid` (include/perf_hip_pair.h): int32 [total, 2], entry e = {field 0's packed
+    2 x 16-bit features, field 1's}."""
+    return torch.empty(grid.total, 2, dtype=torch.int32, device=device)
+
+
+def pair_fill(pair, field, table16, n_entries=None):
+    """pair[:n_entries, field] = the first n_entries entries (pairs of 16-bit features) of table16; the other field's half stays."""
+    n_entries = table16.numel() // 2 if n_entries is None else int(n_entries)
+    if pair.dtype != torch.int32 or pair.numel() < 2 * n_entries or table16.numel() < 2 * n_entries:
+        raise _lib.PerfError('pair_fill: pair must be int32 [>= n_entries, 2] and table16 hold 2 * n_entries features')
+    dtype_code(table16.dtype)
+    _call('perf_pair_fill', _p(pair), int(field), _p(table16), n_entries, _stream())
+    return pair
+
+
+def hashgrid_fwd_pair(grid: GridConfig, x01, pair, dtype, n_dev=None, out=None):
+    """Both fields of a pair table at the same points -> (feat_a, feat_b), each [L, n, 2] of `dtype`, bit-identical to hashgrid_fwd on
+    that field's own table.  n_dev as in hashgrid_fwd.  out: the two feature arrays to write into (rows beyond the count stay)."""
+    n = x01.shape[0]
+    code = dtype_code(dtype)
+    if pair.dtype != torch.int32 or pair.numel() != 2 * grid.total:
+        raise _lib.PerfError('hashgrid_fwd_pair: pair must be the int32 [total, 2] pair table of this grid')
+    if out is not None:
+        fa, fb = out
+        if any(f.dtype != _T16[code] or f.shape != (grid.n_levels, n, 2) for f in out):
+            raise _lib.PerfError('hashgrid_fwd_pair: out must be two [L, n, 2] arrays of the table dtype')
+    else:
+        fa = torch.empty(grid.n_levels, n, 2, dtype=_T16[code], device=x01.device)
+        fb = torch.empty(grid.n_levels, n, 2, dtype=_T16[code], device=x01.device)
+    d = grid.desc()
+    _call('perf_hashgrid_fwd_pair', ctypes.byref(d), _p(_f32(x01, 'x01')), _p(pair), _p(fa), _p(fb), n, _nd(n_dev), code, _stream())
     return fa, fb
 
 
@@ -476,6 +522,17 @@ def hashgrid_bwd_bwd_param(grid: GridConfig, x01, dfeat, ggx):
 
 # ---- MLP -----------------------------------------------------------------------------------------
 def mlp_fwd(mlp: MlpConfig, w16, feat16, sel=None, n_dev=None):
+    """feat16: [L, n, 2], or an IndexedFeat (n = its index's length): the rows are read in place, no compacted copy is made
+    (perf_mlp_fwd_rows; bit-identical to the forward on the materialised rows)."""
+    if isinstance(feat16, IndexedFeat):
+        feat, index = feat16.feat, feat16.index
+        assert index.dtype == torch.int32 and index.is_contiguous() and feat.is_contiguous()
+        n = index.shape[0]
+        out = torch.empty(n, mlp.n_output_dims, dtype=torch.float32, device=feat.device)
+        d = mlp.desc()
+        _call('perf_mlp_fwd_rows', ctypes.byref(d), _p(w16), _p(feat), _p(index), feat.shape[1], _p(sel), _p(out), n, _nd(n_dev),
+              dtype_code(w16.dtype), _stream())
+        return out
     n = feat16.shape[1]
     out = torch.empty(n, mlp.n_output_dims, dtype=torch.float32, device=feat16.device)
     d = mlp.desc()
@@ -604,6 +661,12 @@ def normal_composite(weights, grad, packed):
     out = torch.empty(R, 3, dtype=torch.float32, device=weights.device)
     _call('perf_normal_composite', _p(_f32(weights, 'weights')), _p(_f32(grad, 'grad')), _p(packed), R, _p(out), _stream())
     return out
+
+
+class PairFeat(NamedTuple):
+    """The two level-major feature arrays [L, n, 2] of one pair encode (hashgrid_fwd_pair): field 0's and field 1's, same samples."""
+    a: torch.Tensor
+    b: torch.Tensor
 
 
 class IndexedFeat(NamedTuple):

@@ -72,17 +72,24 @@ class NeRFOCCRenderer(nn.Module):
     # The render is cut in two stages so that a data-parallel trainer can overlap the gradient all-reduce of step k
     # with everything of step k+1 that does not depend on the parameters being updated (scene.py).
     def stage_sample(self, nerf: NGPNeRF, estimator: OccGridEstimator, rays_o, rays_d, rand=None, with_rgb=False,
-                     keep_features=False):
+                     keep_features=False, pair=None):
         """Sampling (marching, the no-grad density pass and visibility compaction of nerf_renderer.py:145-155), sample
         positions and -- with_rgb -- the colour field without gradient.  Returns a dict consumed by stage_composite, or
         None when the batch has no sample.  With self.sample_capacity set every per-sample array has that many rows and
         st['n_dev'] (device int64 [1]) holds the live count: no host read-back, hipGraph-capturable.
         keep_features (sync-free mode): st['feat0'] = the density field's encoded features of the KEPT samples, compacted from
-        the sampler's own density pass."""
+        the sampler's own density pass.
+        pair (a fields.PairTable with both halves current; one-phase sync-free sampler): the density pass encodes BOTH fields with one
+        gather per table entry; st['feat0'] as with keep_features, st['feat0_b'] = the colour field's features of the kept samples (rows
+        of the marched samples' array), and -- with_rgb -- the colour render is computed from them without a second encode."""
         rays_o = rays_o.contiguous().float(); rays_d = rays_d.contiguous().float()
         rand = rand or {}
+        if pair is not None and (self.sample_capacity is None or self.head_samples is not None or self.early_stop_eps <= 0):
+            pair = None
 
         def sigma_points_fn(x01, sel, n_dev):
+            if pair is not None:
+                return nerf.density_with_pair_features(x01, sel, pair, n_dev)
             if keep_features:
                 return nerf.density_with_features(x01, sel, n_dev)
             return nerf.density_at(x01, sel, n_dev)
@@ -99,10 +106,10 @@ class NeRFOCCRenderer(nn.Module):
             x01, sel = nerf.sample_points(rays_o, rays_d, sm.ray_indices, sm.t_starts, sm.t_ends)
         st = {'ray_indices': sm.ray_indices, 't_starts': sm.t_starts, 't_ends': sm.t_ends, 'packed': sm.packed, 'sig0': sm.sig,
               'x01': x01, 'sel': sel, 'n_rays': rays_o.shape[0], 'rgbs': None, 'n_dev': sm.n_dev,
-              'n_marched_dev': sm.n_marched_dev, 'feat0': sm.feat}
+              'n_marched_dev': sm.n_marched_dev, 'feat0': sm.feat, 'feat0_b': sm.feat_b}
         if with_rgb:
             with torch.no_grad():
-                st['rgbs'] = nerf.rgb_at(x01, sel, sm.n_dev)
+                st['rgbs'] = nerf.rgb_from_features(sm.feat_b, sel, sm.n_dev) if sm.feat_b is not None else nerf.rgb_at(x01, sel, sm.n_dev)
         return st
 
     def stage_composite(self, nerf: NGPNeRF, st, geo_inference=False, app_inference=False, rand=None, with_normal=False):
@@ -116,8 +123,10 @@ class NeRFOCCRenderer(nn.Module):
         dev = x01.device
         grad_geo = torch.is_grad_enabled() and not geo_inference
         grad_app = torch.is_grad_enabled() and not app_inference
-        # (A shared-index pass over both grids -- perf_hashgrid_fwd2 -- measured 2x SLOWER than two passes: the
-        #  per-XCD working set doubles to 4 MiB = the whole L2.  The fields are therefore queried one after the other.)
+        # (A shared-index pass over both grids' OWN tables -- perf_hashgrid_fwd2 -- measured 2x SLOWER than two passes: twice the misses,
+        #  and the per-XCD working set doubles to 4 MiB = the whole L2.  The fields are therefore queried one after the other here.  The
+        #  fused training steps encode both fields from a PAIR table instead -- one 8-byte gather per corner, one hashed level per XCD
+        #  at a time: stage_sample(pair=...), csrc/hashgrid_pair.hip.)
         n_dev = st.get('n_dev')
         if grad_geo:
             sigmas = nerf.density_at(x01, sel, n_dev)

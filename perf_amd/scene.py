@@ -406,10 +406,14 @@ class FusedAdam:
             ops.step_bookkeeping(self.step_dev, gate, counters, n_marched, n_kept if n_kept is not None else gate, capacity=capacity,
                                  overflow=flag, remote_flags=remote_flags, eff_gate=self.eff_gate, schedule=self.schedule_args(),
                                  overflow_redone=fixed and getattr(self.net, 'redo_supported', False))
+        half = getattr(self.net, '_pair_half', None)        # (fields.NGPNeRF.use_pair: this network's half of a pair table)
         ops.adam_step_dev(p.data, self.exp_avg, self.exp_avg_sq, p.grad[:p.numel()], self.step_dev, self.lr_dev, g['betas'][0],
-                          g['betas'][1], g['eps'], w16=self.w16, zero_grad=False, gate=self.eff_gate, clear_flag=flag if rode else None)
+                          g['betas'][1], g['eps'], w16=self.w16, zero_grad=False, gate=self.eff_gate, clear_flag=flag if rode else None,
+                          pair=(half[0].buf, half[1], self.net.mlp.n_params) if half is not None else None)
         p.grad = None                              # the next backward installs a fresh gradient (no accumulate pass)
         self.net.set_working_copy(self.w16)        # the kernel wrote the refreshed 16-bit copy
+        if half is not None:
+            half[0].adopted(half[1], self.net)
 
 
 class _HipStepKernels:
@@ -504,6 +508,14 @@ class NeRFScene:
         # encoding and evaluating again: bit-identical parameters (tests/test_gpu_counts.py), one encode and one MLP forward fewer.  On by default; False is the strict two-encode order of the reference
         # (bench.py reports both).
         self.reuse_sampling_features = True
+        # Both fields' grids have one geometry and a fused training step encodes the same positions through both.  True: the sampler's
+        # density pass encodes both from the pair table (fields.PairTable: one gather per table entry serves both fields) and the
+        # colour field reads its features as rows of that pass -- no second encode; bit-identical parameters and colours
+        # (tests/test_gpu_pair_step.py).  Effective with equal tcnn-layout grids of at most 16 levels, renderer.sample_capacity set, the
+        # one-phase sampler (renderer.head_samples None) and one process; otherwise the two encodes as before.  With
+        # reuse_sampling_features False (the strict two-evaluation order) the geometry step's two encodes of the KEPT samples are the pair
+        # encode; the colour step has one evaluation of each field in either order and always pairs in the sampler's pass.
+        self.pair_encode = True
         self._geo_pre = None
         self._ratio_dev = torch.zeros((), dtype=torch.float32, device='cuda')   # distortion-loss ramp min(2*progress, 1)
         # device-side statistics of perf_step_bookkeeping (int64 [8]): {marched, kept, steps, largest batch, steps skipped for
@@ -1077,6 +1089,15 @@ class NeRFScene:
             if ex is not None and self._dist()[0] is not None:
                 ex.gather_master(net.params.data)
 
+    def _pair_table(self, dist_info, used=True):
+        """The field's pair table (both halves current) when this step encodes through it (see pair_encode), else None.  used=False:
+        the step has no reader for the second field's features (a geometry step without its colour render): the networks are not
+        bound either, so their Adam launches do not pay for a pair table nobody reads."""
+        r = self.renderer
+        on = (used and self.pair_encode and self.fused_adam and dist_info[0] is None and r.sample_capacity is not None
+              and r.head_samples is None and r.early_stop_eps > 0 and self.nerf.pair_supported())
+        return self.nerf.use_pair(on)
+
     @torch.no_grad()
     def _geo_step_fused(self, optimizer, sup_pool, progress, rand, generator, prefetch_next=True):
         """train_one_step_geo (nerf.py:186-257) as an explicit chain: sampling (marching + no-grad density pass + visibility
@@ -1092,9 +1113,17 @@ class NeRFScene:
         rand_in, rand = rand, pre['rand']
         if st is None:
             # (under data parallelism the colour render is deferred until the gradient all-reduce is in flight, see below)
-            st = self.renderer.stage_sample(self.nerf, self.estimator, rays.o, rays.d, rand,
-                                            with_rgb=not (self.skip_unused_color or (dist_info[0] is not None and self.overlap_comm)),
-                                            keep_features=self.reuse_sampling_features and self.renderer.sample_capacity is not None)
+            with_rgb = not (self.skip_unused_color or (dist_info[0] is not None and self.overlap_comm))
+            pair = self._pair_table(dist_info, used=with_rgb)
+            # pair_encode with reuse_sampling_features: the sampler's density pass encodes both fields.  In the strict two-evaluation
+            # order the sampler's pass stays what it is and the TWO encodes of the kept samples (density with gradient, colour) become
+            # one pair encode below.
+            strict_pair = pair if not self.reuse_sampling_features else None
+            st = self.renderer.stage_sample(self.nerf, self.estimator, rays.o, rays.d, rand, with_rgb=with_rgb and strict_pair is None,
+                                            keep_features=self.reuse_sampling_features and self.renderer.sample_capacity is not None,
+                                            pair=pair if strict_pair is None else None)
+        else:
+            strict_pair = None
         geo = self.nerf.geo_mlp
         if not st:                             # (None, or False from the prefetch: no samples on this rank)
             return self._backward_and_step(geo, optimizer, dist_info, None, None, None, None)
@@ -1110,7 +1139,10 @@ class NeRFScene:
             # the second forward launch is dropped (bit-identical parameters, tests/test_gpu_counts.py).
             sig = st['sig0'].reshape(-1, 1)
         else:
-            if feat is None:
+            if feat is None and strict_pair is not None:
+                feat, feat_b = ops.hashgrid_fwd_pair(geo.grid, x01, strict_pair.buf, geo.dtype_name, n_dev=n_dev)
+                st['rgbs'] = self.nerf.rgb_from_features(feat_b, sel, n_dev)
+            elif feat is None:
                 feat = ops.hashgrid_fwd(geo.grid, x01, w16[n_net:], n_dev=n_dev)
             elif isinstance(feat, ops.IndexedFeat):       # (features without densities: no caller does that today)
                 feat = feat.materialize()
@@ -1167,7 +1199,7 @@ class NeRFScene:
             rays, gt_colors, gt_depths, bs, dist_info, rand = self._draw(sup_pool, want_bg=self.renderer.bg_color == 'rand_noise')
         else:
             rays, gt_colors, gt_depths, bs, dist_info = self._batch(sup_pool, generator)
-        st = self.renderer.stage_sample(self.nerf, self.estimator, rays.o, rays.d, rand)
+        st = self.renderer.stage_sample(self.nerf, self.estimator, rays.o, rays.d, rand, pair=self._pair_table(dist_info))
         app = self.nerf.app_mlp
         if st is None:
             return self._backward_and_step(app, optimizer, dist_info, None, None, None, None)
@@ -1176,7 +1208,9 @@ class NeRFScene:
         sig = st['sig0'] if st['sig0'] is not None else self.nerf.density_at(x01, sel, n_dev)
         n_net = app.mlp.n_params
         w16 = app.working_copy()
-        feat = ops.hashgrid_fwd(app.grid, x01, w16[n_net:], n_dev=n_dev)
+        feat = st.get('feat0_b')             # (pair_encode: the sampler's pass encoded the colour field too; rows of its feature array)
+        if feat is None:
+            feat = ops.hashgrid_fwd(app.grid, x01, w16[n_net:], n_dev=n_dev)
         rgbs = ops.mlp_fwd(app.mlp, w16[:n_net], feat, sel, n_dev=n_dev)
         n_rays = packed.shape[0]
         bg = None

@@ -15,8 +15,9 @@ namespace perf {
 // L16/T18) is cut into 128 KiB tiles of 16384 entries and each tile is OWNED by one workgroup that
 // keeps it in LDS (the multi-tile levels' 192 + 12 tiles plus the replicated coarse ones <= 256 CUs: the whole
 // table is resident in the chip's aggregate LDS).  Every owner walks all samples of its level and applies only the
-// corner updates that fall in its tile with LDS atomics -- multi-tile levels through a 4-byte tile code per sample
-// that a pre-pass computes once for all owners (bwd_stream_codes), single-tile levels from positions (bwd_stream);
+// corner updates that fall in its tile with LDS atomics -- multi-tile levels through a tile code per sample that a
+// pre-pass computes once for all owners (hashed levels of up to 16 tiles: a 16-bit tile mask, bwd_stream_masks; others:
+// 4 bytes, bwd_stream_codes), single-tile levels from positions (bwd_stream);
 // at the end the tile is written back with plain coalesced stores.  No global atomics, no zero-fill pass, every
 // table entry written exactly once.
 constexpr int kTileEntries = 16384;
@@ -31,7 +32,7 @@ constexpr int kCus = 248;                  // MI355X has 256 CUs and an owner wo
 // sample; a coarse dense level has only 1..8 tiles receiving the same total.  Coarse tiles are therefore
 // REPLICATED (R_l copies, each streaming 1/R_l of the samples) so that every workgroup takes about as long as
 // a hashed-tile owner; replicas are summed by a small second kernel.  L16/T18, fixed-point mode:
-// 8 + 8 + 4x3 + 8x3 + 12x16 = 244 workgroups (round 6: the third replica of level 3 from the CUs left over, see plan_tiles).
+// 8 + 8 + 4x4 + 8x3 + 12x16 = 248 workgroups (the third replica of level 3 and the fourth of level 2 from the CUs left over, see plan_tiles).
 struct TileParams {
     int32_t tiles_of[PERF_MAX_LEVELS];     // tiles per level
     int32_t replicas_of[PERF_MAX_LEVELS];  // replicas per tile
@@ -124,9 +125,25 @@ static void plan_tiles(const GridParams& gp, bool fixed, TileParams* tp, int* n_
                 nb += nt * (want - r);
                 tp->replicas_of[l] = want;
             }
-        // (a fourth replica for the 4 tiles of level 2 -- 336 -> 269 us per workgroup, 248 workgroups -- made the launch SLOWER in an A/B on
-        //  one box: 357.0 against 352.5 us, three runs each, call r06dd: the hashed owners end the launch and lose more to four more
-        //  neighbours than level 2 gains)
+        // ---- and then to the dense levels of 2..4 tiles.  With the hashed owners on 16-bit tile masks (bwd_stream_masks: 283-306 us per
+        // workgroup, were 297-335) the 4 tiles x 3 replicas of level 2 of L16 / T18 ended the launch at 342 us; a fourth replica brings
+        // them to 268 and the launch from 331 to 316 us on one box (profiles/bwd_tile_masks.json; 248 workgroups = kCus).  (Round 6
+        // measured the same replica as a LOSS, 357.0 against 352.5 us: the hashed owners ended the launch then, and four more neighbours
+        // cost them more than level 2 gained.)  Only while its slab fits the room the fp32 plan's slabs take anyway (16 / tiles replicas):
+        // the workspace a grid asks for stays what it was.
+        int64_t ws_fixed = 0, ws_fp32 = 0;
+        for (int l = 0; l < gp.n_levels; ++l) {
+            const int nt = tp->tiles_of[l];
+            if (tp->replicas_of[l] > 1) ws_fixed += (int64_t)tp->replicas_of[l] * gp.size[l];
+            if (!gp.hashed[l] && nt > 0 && kMaxReplicas / nt > 1) ws_fp32 += (int64_t)(kMaxReplicas / nt) * gp.size[l];
+        }
+        for (int l = 0; l < gp.n_levels; ++l) {
+            const int nt = tp->tiles_of[l], r = tp->replicas_of[l];
+            if (gp.hashed[l] || nt < 2 || nt > 4 || r != rs[1] || nb + nt > kCus || ws_fixed + (int64_t)gp.size[l] > ws_fp32) continue;
+            nb += nt;
+            ws_fixed += gp.size[l];
+            tp->replicas_of[l] = r + 1;
+        }
         ws = 0;                                              // (slab offsets again)
         for (int l = 0; l < gp.n_levels; ++l) {
             tp->ws_off[l] = 0;
@@ -321,6 +338,12 @@ constexpr int kCodeSamplesPerBlock = 256;
 //  What an owner costs is the drain: gather 20 B per queued sample, ~95 instructions and two 64-bit LDS atomics per
 //  combination; tests, gathers and LDS are within 2x of each other, so removing one of them moves little.)
 
+// Hashed levels of at most 16 tiles (log2_hashmap_size <= 18) keep a 16-bit mask per sample instead of the four bytes: bit t is set
+// when any of the sample's four (y,z) combinations names tile t.  The row lives in the first half of the level's code slot
+// (stride n_pad elements of two bytes); its owners are bwd_stream_masks.
+constexpr int kMaskTiles = 16;
+__device__ __forceinline__ bool mask_level(const TileParams& tp, int l) { return tp.tiles_of[l] <= kMaskTiles; }     // (of a hashed level)
+
 // The tile code of sample (x, y, z) at level l (see tile_codes_kernel); bad: the premise of the code does not hold.
 __device__ __forceinline__ uint32_t tile_code_of(const GridParams& gp, const TileParams& tp, int l, float x, float y, float z, bool& bad) {
     const float py = grid_pos(y, gp.scale[l]), pz = grid_pos(z, gp.scale[l]);
@@ -330,8 +353,12 @@ __device__ __forceinline__ uint32_t tile_code_of(const GridParams& gp, const Til
     if (gp.hashed[l]) {
         const uint32_t ay0 = gy * kPrimeY, ay1 = ay0 + kPrimeY, az0 = gz * kPrimeZ, az1 = az0 + kPrimeZ;
         const uint32_t m = gp.size[l] - 1u;
-        code = (((ay0 ^ az0) & m) / (uint32_t)kTileEntries) | ((((ay1 ^ az0) & m) / (uint32_t)kTileEntries) << 8) |
-               ((((ay0 ^ az1) & m) / (uint32_t)kTileEntries) << 16) | ((((ay1 ^ az1) & m) / (uint32_t)kTileEntries) << 24);
+        const uint32_t t0 = ((ay0 ^ az0) & m) / (uint32_t)kTileEntries, t1 = ((ay1 ^ az0) & m) / (uint32_t)kTileEntries,
+                       t2 = ((ay0 ^ az1) & m) / (uint32_t)kTileEntries, t3 = ((ay1 ^ az1) & m) / (uint32_t)kTileEntries;
+        // up to kMaskTiles tiles: a 16-bit MASK of the tiles the four combinations name (the caller stores two bytes per sample);
+        // beyond that one byte per combination
+        if (mask_level(tp, l)) code = (1u << t0) | (1u << t1) | (1u << t2) | (1u << t3);
+        else code = t0 | (t1 << 8) | (t2 << 16) | (t3 << 24);
         // a position so far outside the unit cube that its x-corners leave the first 16384 columns breaks
         // "(y,z) decides the tile"
         bad = gx >= (uint32_t)(kTileEntries - 1);
@@ -368,7 +395,8 @@ __device__ __forceinline__ void tile_codes_block(const GridParams& gp, const Til
             if (slot < 0) continue;
             bool bad;       // the premise of the code does not hold for this sample
             const uint32_t code = tile_code_of(gp, tp, l, x, y, z, bad);
-            codes[(int64_t)slot * tp.n_pad + i] = code;
+            if (gp.hashed[l] && mask_level(tp, l)) reinterpret_cast<uint16_t*>(codes + (int64_t)slot * tp.n_pad)[i] = (uint16_t)code;
+            else codes[(int64_t)slot * tp.n_pad + i] = code;
             if (bad && gp.hashed[l]) {      // harmless without gradient; with gradient the level's owners take the generic path
                                             // (dense: the owners apply such a sample corner by corner, see bwd_stream_codes)
                 const float2 g = dfeat[(int64_t)l * n + i];
@@ -441,7 +469,16 @@ __global__ __launch_bounds__(256) void tile_codes4_kernel(GridParams gp, TilePar
 #pragma unroll
             for (int k = 0; k < 4; ++k) code[k] = tile_code_of(gp, tp, l, p[3 * k], p[3 * k + 1], p[3 * k + 2], bad[k]);
             uint32_t* row = codes + (int64_t)slot * tp.n_pad + i0;
-            if (cnt == 4) {
+            if (gp.hashed[l] && mask_level(tp, l)) {          // four masks: one 8-byte store
+                uint16_t* row16 = reinterpret_cast<uint16_t*>(codes + (int64_t)slot * tp.n_pad) + i0;
+                if (cnt == 4) {
+                    *reinterpret_cast<uint2*>(row16) = make_uint2(code[0] | (code[1] << 16), code[2] | (code[3] << 16));
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (k < cnt) row16[k] = (uint16_t)code[k];
+                }
+            } else if (cnt == 4) {
                 *reinterpret_cast<uint4*>(row) = make_uint4(code[0], code[1], code[2], code[3]);
             } else {
 #pragma unroll
@@ -689,6 +726,140 @@ __device__ __forceinline__ void bwd_stream_codes(const BwdCtx& cx, float* lds_ti
     }
     asm volatile("" : : "v"(ld_c0), "v"(ld_c1));       // (the last code loads landed with the vmcnt(0) above)
 #undef PERF_WAIT_BATCH
+}
+
+// ---- hashed owners of a mask level (at most 16 tiles: see mask_level) ------------------------------------------------
+// The same loop over a 16-bit mask per sample: the test of a sample is ONE AND against this owner's bit and the compare that is
+// the ballot (the byte codes take five instructions for the zero-byte marks and a dot product on the lanes that hit), and a lane's four
+// samples arrive in one 8-byte load.  What the mask does not say is WHICH of the sample's four (y,z) combinations name the tile: a
+// fresh queue entry carries cm = 0 and the apply works the combinations out from the (y,z) it gathered anyway, with the pre-pass's own
+// four tile expressions (tile_code_of); re-queued entries carry their remaining combinations as before.
+// In flight at the head of an iteration, oldest first: [masks: 1][gather batch: 3], so "vmcnt(3)" = the masks have landed; every pop
+// issues 3 loads and every iteration 1, whatever the queue holds.  The queue bound is bwd_stream_codes' (kQueueCap).
+// (A SECOND gather batch in flight per wave -- two register sets taking turns, the main loop unrolled by two, bursts drained in pairs,
+//  the batch popped in one iteration applied in the one after the next -- was built and measured beside this loop: per-workgroup times
+//  of the hashed owners equal within 1 us, the step 0.846 ms either way; DESIGN.md 5.1, profiles/bwd_tile_masks.json.  Not kept.)
+struct GatherBatch {
+    float ld_x; f32x2 ld_yz, ld_g;      // written by loads in flight: only ever read through PERF_WAIT_APPLY
+    uint32_t cm, i;                     // combinations (0: not known yet) and sample index of the lane's entry
+    bool live;                          // this lane holds an entry
+};
+
+template <bool FIXED>
+__device__ __forceinline__ void bwd_stream_masks(const BwdCtx& cx, float* lds_tile, uint32_t* queue,
+                                                 const uint32_t* __restrict__ masks_l, const float* __restrict__ x01,
+                                                 const float2* __restrict__ g_l, int64_t n, int rep, int R) {
+    __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0), see bwd_stream_codes
+    constexpr int kPer = 4;                             // samples of a lane per iteration (= per mask load)
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t qn = 0;                                    // wave-uniform queue fill
+    const int64_t n_full = n / kPer;
+    const int64_t g_lo = n_full * rep / R, g_hi = n_full * (rep + 1) / R;       // this replica's groups of kPer samples
+    u32x2 ld_m = {0u, 0u};                              // written by the load in flight
+    GatherBatch A = {0.f, {0.f, 0.f}, {0.f, 0.f}, 0u, 0u, false};               // the batch in flight
+    const uint32_t bit2 = (1u << cx.t) * 0x00010001u;   // this owner's bit in both halves of a word of two masks
+    const uint32_t t_hi = cx.t * (uint32_t)kTileEntries, m_hi = cx.mask & ~(uint32_t)(kTileEntries - 1);
+    auto enqueue_hit = [&](bool hit, uint32_t e) __attribute__((always_inline)) {     // fresh entry: combinations not known yet
+        const unsigned long long b = __ballot(hit);
+        if (b) {
+            const uint32_t pos = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+            if (hit) queue[pos] = e;
+            qn += (uint32_t)__popcll(b);
+        }
+    };
+    auto requeue = [&](uint32_t cm, uint32_t i) __attribute__((always_inline)) {
+        const unsigned long long b = __ballot(cm != 0u);
+        if (b) {
+            const uint32_t pos = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+            if (cm) queue[pos] = (i << 4) | cm;
+            qn += (uint32_t)__popcll(b);
+        }
+    };
+    auto load_masks = [&](int64_t grp) __attribute__((always_inline)) {                // 1 load
+        const uint32_t off = (uint32_t)(grp < g_hi ? grp : g_hi - 1) * 8u;
+        asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(ld_m) : "v"(off), "s"(masks_l) : "memory");
+    };
+    auto pop_and_gather = [&]() __attribute__((always_inline)) {                       // up to 64 queued samples: 3 loads
+        const uint32_t take = qn < 64u ? qn : 64u;
+        __builtin_amdgcn_wave_barrier();
+        uint32_t e = 0;
+        if (lane < take) e = queue[qn - take + lane];
+        __builtin_amdgcn_wave_barrier();
+        qn -= take;
+        A.live = lane < take;
+        A.cm = e & 15u;
+        A.i = e >> 4;
+        const uint32_t ox = A.i * 12u, og = A.i * 8u;
+        asm volatile("global_load_dword %0, %3, %4\n\tglobal_load_dwordx2 %1, %3, %4 offset:4\n\tglobal_load_dwordx2 %2, %5, %6"
+                     : "=&v"(A.ld_x), "=&v"(A.ld_yz), "=&v"(A.ld_g) : "v"(ox), "s"(x01), "v"(og), "s"(g_l) : "memory");
+    };
+    // Every lane applies ONE combination; the samples that name this tile with two or more go back into the queue with the rest.
+    auto apply_batch = [&](float bx, f32x2 byz, f32x2 bg) __attribute__((always_inline)) {
+        const float px = grid_pos(bx, cx.scale), py = grid_pos(byz.x, cx.scale), pz = grid_pos(byz.y, cx.scale);
+        const float flx = floorf(px), fly = floorf(py), flz = floorf(pz);
+        const uint32_t gx = (uint32_t)(int32_t)flx;
+        const uint32_t ay0 = (uint32_t)(int32_t)fly * kPrimeY, az0 = (uint32_t)(int32_t)flz * kPrimeZ;
+        const uint32_t ay1 = ay0 + kPrimeY, az1 = az0 + kPrimeZ;
+        // (tile == t, with the tile's bits of the index compared in place)
+        const uint32_t derived = ((((ay0 ^ az0) & m_hi) == t_hi) ? 1u : 0u) | ((((ay1 ^ az0) & m_hi) == t_hi) ? 2u : 0u) |
+                                 ((((ay0 ^ az1) & m_hi) == t_hi) ? 4u : 0u) | ((((ay1 ^ az1) & m_hi) == t_hi) ? 8u : 0u);
+        uint32_t cm = A.cm ? A.cm : derived;
+        if (!A.live || gx >= (uint32_t)(kTileEntries - 1)) cm = 0u;     // (idle lane; or zero gradient, see tile_codes_kernel)
+        const uint32_t rest = cm & (cm - 1u);
+        cm &= 0u - cm;
+        if (cm) apply_pairs<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, py - fly, pz - flz, ay0, az0, cm);
+        requeue(rest, A.i);
+    };
+    // wait until at most `younger` loads are in flight, then copy the landed registers of the batch (the copy is part of the asm
+    // statement: the compiler must not move a read of those registers above the wait) and apply it.
+    // (The batch must keep its registers from pop to apply on every path: a compiler-made copy of a register that a load in flight
+    //  is still to write reads it too early.  After a change to this loop, compare the registers of the loads with those of the copies
+    //  in the assembly.)
+#define PERF_WAIT_APPLY(younger)                                                                                        \
+    {                                                                                                                   \
+        float bx; f32x2 byz, bg;                                                                                        \
+        asm volatile("s_waitcnt vmcnt(" #younger ")\n\tv_mov_b32 %0, %3\n\tv_mov_b64 %1, %4\n\tv_mov_b64 %2, %5"       \
+                     : "=&v"(bx), "=&v"(byz), "=&v"(bg) : "v"(A.ld_x), "v"(A.ld_yz), "v"(A.ld_g) : "memory");           \
+        apply_batch(bx, byz, bg);                                                                                       \
+    }
+    if (g_hi > g_lo) {
+        int64_t grp = g_lo + threadIdx.x;
+        load_masks(grp);
+        pop_and_gather();               // empty queue: dummy gather, keeps the in-flight count of the loop static
+        for (int64_t base = g_lo + (int64_t)(threadIdx.x & ~63u); base < g_hi; base += kBwdThreads) {   // wave-uniform trip count
+            u32x2 m;
+            asm volatile("s_waitcnt vmcnt(3)\n\tv_mov_b64 %0, %1" : "=&v"(m) : "v"(ld_m) : "memory");
+            const int64_t g0 = grp;
+            const uint32_t vb = g0 < g_hi ? bit2 : 0u;      // a lane without a group of its own in the last iteration hits nothing
+            grp += kBwdThreads;
+            load_masks(grp);
+            const uint32_t b_lo = vb & 0xffffu, b_hi = vb & 0xffff0000u, e0 = (uint32_t)(4 * g0) << 4;
+            enqueue_hit((m.x & b_lo) != 0u, e0);
+            enqueue_hit((m.x & b_hi) != 0u, e0 + 16u);
+            enqueue_hit((m.y & b_lo) != 0u, e0 + 32u);
+            enqueue_hit((m.y & b_hi) != 0u, e0 + 48u);
+            PERF_WAIT_APPLY(1)              // all but the mask load
+            pop_and_gather();
+            while (qn >= 128u) {            // bursts (ray-coherent samples at coarse hashed levels)
+                PERF_WAIT_APPLY(0)
+                pop_and_gather();
+            }
+        }
+    }
+    if (threadIdx.x < 64 && rep == 0) {                 // ragged tail (n % kPer samples)
+        const int64_t i = n_full * kPer + lane;
+        bool hit = false;
+        if (i < n) hit = ((reinterpret_cast<const uint16_t*>(masks_l)[i] >> cx.t) & 1u) != 0u;
+        enqueue_hit(hit, (uint32_t)i << 4);
+    }
+    for (;;) {
+        PERF_WAIT_APPLY(0)
+        A.live = false;
+        if (qn == 0u) break;
+        pop_and_gather();
+    }
+    asm volatile("" : : "v"(ld_m));                     // (the last mask load landed with a vmcnt(0) above)
+#undef PERF_WAIT_APPLY
 }
 
 // inclusive prefix sum over the 64 lanes of a wave (DPP: shifts inside rows of 16, then row broadcasts)
@@ -1007,6 +1178,7 @@ __global__ __launch_bounds__(kBwdThreads) void hashgrid_bwd_kernel(GridParams gp
     uint32_t* queue = reinterpret_cast<uint32_t*>(lds_tile + 2 * kTileEntries) + (threadIdx.x >> 6) * kQueueCap;
     if (by_bitmap && hashed) bwd_stream_bitmap<FIXED, false>(cx, lds_tile, queue, bitmaps + (int64_t)(tp.bm_row[l] + (int)t) * tp.bm_row_words, x01, g_l, n_live);
     else if (by_bitmap) bwd_stream_bitmap<FIXED, true>(cx, lds_tile, queue, bitmaps + (int64_t)(tp.bm_row[l] + (int)t) * tp.bm_row_words, x01, g_l, n_live);
+    else if (coded && hashed && n_tiles <= (uint32_t)kMaskTiles) bwd_stream_masks<FIXED>(cx, lds_tile, queue, codes + (int64_t)tp.code_slot[l] * tp.n_pad, x01, g_l, n_live, rep, R);
     else if (coded && hashed) bwd_stream_codes<FIXED, false>(cx, lds_tile, queue, codes + (int64_t)tp.code_slot[l] * tp.n_pad, x01, g_l, n_live, rep, R);
     else if (coded) bwd_stream_codes<FIXED, true>(cx, lds_tile, queue, codes + (int64_t)tp.code_slot[l] * tp.n_pad, x01, g_l, n_live, rep, R);
     else if (hashed) bwd_stream<FIXED, true>(cx, lds_tile, x01, g_l, n_live, rep, R);

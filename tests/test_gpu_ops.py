@@ -151,6 +151,16 @@ def test_hashgrid_bwd_input(ops):
         dx = ops.hashgrid_bwd_input(cfg, x.detach().cuda(), dfeat.cuda(), table.reshape(-1).cuda()).cpu()
         scale = x.grad.abs().max()
         assert (dx - x.grad).abs().max() < 1e-4 * scale
+        # the same with the edge rows of test_hashgrid_fwd in front (cube faces and corners: the dense levels' last cells, f = 1/2 at
+        # level 0) and points up to the faces; per level and block by block: tests/test_gpu_encoding_second_order.py
+        xe = torch.rand(500, 3, generator=g)
+        xe[:7] = torch.tensor([[0., 0, 0], [1, 1, 1], [0.5, 0.5, 0.5], [1e-7, 1 - 1e-7, 0.25], [0.999999, 0, 1],
+                               [1.0, 0.0, 0.3], [0.3, 1.0, 0.0]])
+        xe.requires_grad_(True)
+        (O.hashgrid_encode(xe, table, lv, interpolation=interp) * dfeat.permute(1, 0, 2).reshape(500, -1)).sum().backward()
+        dxe = ops.hashgrid_bwd_input(cfg, xe.detach().cuda(), dfeat.cuda(), table.reshape(-1).cuda()).cpu()
+        assert (dxe - xe.grad).abs().max() < 1e-4 * xe.grad.abs().max()
+        assert (dxe[:7] - xe.grad[:7]).abs().max() < 1e-4 * xe.grad[:7].abs().max()
 
 
 def _mlp_case(ops, dt, nh, n_out, act, n, n_levels=16, seed=0):

@@ -465,12 +465,15 @@ def _pad_net(params, spec):
     return params
 
 
-def test_encoding_double_backward():
-    """next-1: tcnn.Encoding (Smoothstep) with input gradient and double backward, as SphereDistanceField uses it
-    (pano_joint_predictor.py:22-71): d/dtheta and d/dx of a loss on the input gradient vs autograd through the oracle."""
+@pytest.mark.parametrize('interp', ['Linear', 'Smoothstep'])
+def test_encoding_double_backward(interp):
+    """next-1: tcnn.Encoding with input gradient and double backward, as SphereDistanceField uses it (Smoothstep;
+    pano_joint_predictor.py:22-71): d/dtheta and d/dx of a loss on the input gradient vs autograd through the oracle.  Linear: the
+    interpolation's second derivative is zero and d/dx of the input gradient consists of the mixed terms alone.  (One scalar loss,
+    whole-tensor norms: the pieces one by one and level by level are tests/test_gpu_encoding_second_order.py's.)"""
     from perf_amd import tcnn
     cfg = {"otype": "HashGrid", "n_levels": 8, "n_features_per_level": 2, "log2_hashmap_size": 15, "base_resolution": 16,
-           "per_level_scale": 1.5, "interpolation": "Smoothstep"}
+           "per_level_scale": 1.5, "interpolation": interp}
     enc = tcnn.Encoding(3, cfg, dtype='fp32')      # fp32 output: a half cast would overflow the second-order gradients
     with torch.no_grad():
         enc.params.mul_(1e4)
@@ -490,7 +493,7 @@ def test_encoding_double_backward():
     # oracle
     table = enc.params.detach().cpu().view(-1, 2).clone().requires_grad_(True)
     xr = x.clone().requires_grad_(True)
-    yr = O.hashgrid_encode(xr, table, lv, interpolation='Smoothstep')
+    yr = O.hashgrid_encode(xr, table, lv, interpolation=interp)
     outr = torch.tanh(yr @ proj)
     (gxr,) = torch.autograd.grad(outr.sum(), xr, create_graph=True)
     l2r = (gxr ** 2).sum() + outr.sum()

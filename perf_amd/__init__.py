@@ -52,6 +52,70 @@ def uninstall_sphere_field_shims():
         sys.modules.pop(name, None)
 
 
+def install_joint_predictor_shim():
+    """Opt-in, separate from install_shims: lets `modules.geo_predictors.pano_joint_predictor` load from its REAL file and rebinds
+    `PanoJointPredictor.__call__` of that module to perf_amd.joint_align.PanoJointPredictor.__call__ -- the alignment loop on the kernels
+    of include/perf_hip_joint.h.  The class keeps the reference's __init__ (its two Omnidata predictors), its name and its module;
+    core_exp_runner.py's `PanoJointPredictor()(img, distance, mask, ...)` then runs view generation, predictors, alignment and the
+    final panorama query through this package.  A module that is already imported is rebound on the spot.  Idempotent.  The finder
+    goes to the FRONT of sys.meta_path and hands the module on to install_shims(sphere_field=True)'s finder when that is installed, so
+    both rebindings hold; call this after install_shims (a later install_shims(sphere_field=True) would put its own finder in front,
+    which answers for the same module name without this rebinding)."""
+    import sys
+    sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, _JointPredictorFinder)]
+    sys.meta_path.insert(0, _JointPredictorFinder())
+    module = sys.modules.get(_JointPredictorFinder.SERVED)
+    if module is not None:
+        _rebind_joint_predictor(module)
+
+
+def uninstall_joint_predictor_shim():
+    import sys
+    sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, _JointPredictorFinder)]
+    sys.modules.pop(_JointPredictorFinder.SERVED, None)
+
+
+def _rebind_joint_predictor(module):
+    cls = module.__dict__.get('PanoJointPredictor')
+    if isinstance(cls, type):
+        from .joint_align import PanoJointPredictor
+        cls.__call__ = PanoJointPredictor.__call__
+
+
+class _JointPredictorFinder:
+    """importlib finder for the one reference module that defines PanoJointPredictor (install_joint_predictor_shim): the module is found
+    and executed by the ordinary path machinery (through _SphereFieldFinder when that is installed); its loader is wrapped so that ONE
+    method is rebound afterwards."""
+    SERVED = 'modules.geo_predictors.pano_joint_predictor'
+
+    def find_spec(self, fullname, path=None, target=None):
+        if fullname != self.SERVED:
+            return None
+        import sys
+        from importlib.machinery import PathFinder
+        inner = next((f for f in sys.meta_path if isinstance(f, _SphereFieldFinder)), PathFinder)
+        spec = inner.find_spec(fullname, path)
+        if spec is None or spec.loader is None:
+            return None
+        spec.loader = _JointRebindLoader(spec.loader)
+        return spec
+
+
+class _JointRebindLoader:
+    def __init__(self, inner):
+        self._inner = inner
+
+    def create_module(self, spec):
+        return self._inner.create_module(spec)
+
+    def exec_module(self, module):
+        self._inner.exec_module(module)
+        _rebind_joint_predictor(module)
+
+    def __getattr__(self, name):             # (get_code, get_source, is_package, ...: the real loader's)
+        return getattr(self._inner, name)
+
+
 class _SphereFieldFinder:
     """importlib finder for the two reference modules that define a SphereDistanceField (install_shims(sphere_field=True)): the module
     is found and executed by the ordinary path machinery; its loader is wrapped so that ONE global is rebound afterwards."""

@@ -14,6 +14,7 @@ ABI_VERSION = 16         # PERF_ABI_VERSION of include/perf_hip.h this binding w
 EXT_ABI_VERSION = 1      # PERF_EXT_ABI_VERSION of include/perf_hip_ext.h (entry points added after perf_hip.h was frozen)
 SPHERE_ABI_VERSION = 1   # PERF_SPHERE_ABI_VERSION of include/perf_hip_sphere.h (the sphere distance field)
 PAIR_ABI_VERSION = 1     # PERF_PAIR_ABI_VERSION of include/perf_hip_pair.h (the pair table of two fields with one grid geometry)
+JOINT_ABI_VERSION = 1    # PERF_JOINT_ABI_VERSION of include/perf_hip_joint.h (the joint predictor's alignment step)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -163,6 +164,19 @@ _SIGS_PAIR = {
     'perf_mlp_fwd_rows': (c_int, [POINTER(MlpDesc), P, P, P, c_int64, P, P, c_int64, P, c_int, P]),
 }
 
+# include/perf_hip_joint.h: the joint predictor's alignment step, exported from the same library, versioned on its own (perf_joint_version)
+JOINT_RECORD = 12        # PERF_JOINT_RECORD
+JOINT_LOSSES = 8         # PERF_JOINT_LOSSES
+_SIGS_JOINT = {
+    'perf_joint_version': (c_int, []),
+    'perf_joint_sample': (c_int, [P, P, P, P, P, P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, P, P, P]),
+    'perf_joint_loss_workspace_bytes': (c_int64, [c_int32, c_int64]),
+    'perf_joint_loss': (c_int, [P, P, P, P, P, P, P, c_int32, c_int64, c_int32, c_int32, c_float, c_float, c_float, c_float, P, P, P, P, P, P, P, P,
+                                c_int64, P]),
+    'perf_joint_tv_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    'perf_joint_tv': (c_int, [P, c_int64, c_int32, c_int32, c_int32, c_float, P, P, P, c_int64, P]),
+}
+
 _lib = None
 
 
@@ -178,7 +192,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
@@ -196,6 +210,9 @@ def load():
                         'rebuild with `python -m perf_amd.build --force`')
     if lib.perf_pair_version() != PAIR_ABI_VERSION:
         raise PerfError(f'{LIB_PATH} has pair-table ABI version {lib.perf_pair_version()}, this binding expects {PAIR_ABI_VERSION}: '
+                        'rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_joint_version() != JOINT_ABI_VERSION:
+        raise PerfError(f'{LIB_PATH} has joint-alignment ABI version {lib.perf_joint_version()}, this binding expects {JOINT_ABI_VERSION}: '
                         'rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):

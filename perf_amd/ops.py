@@ -655,6 +655,89 @@ def sphere_field_bwd(grid: GridConfig, table, net, dirs, draw=None, dgrad=None, 
     return grad
 
 
+# ---- the joint predictor's alignment step (include/perf_hip_joint.h) -------------------------------------------------------------------
+def _joint_dims(who, P, R, bias_d, bias_n, coords):
+    if bias_d.shape != (P, 1, R, R) or bias_n.dim() != 4 or bias_n.shape[:2] != (P, 3) or bias_n.shape[2] != bias_n.shape[3]:
+        raise _lib.PerfError(f'{who}: bias_d must be [{P}, 1, {R}, {R}] and bias_n [{P}, 3, Rn, Rn], got {tuple(bias_d.shape)} and {tuple(bias_n.shape)}')
+    if coords.shape[0] != P or coords.shape[-1] != 2 or coords.numel() != P * coords.shape[1] * 2:
+        raise _lib.PerfError(f'{who}: coords must be [{P}, B, 2] (or [{P}, B, 1, 2]), got {tuple(coords.shape)}')
+    return coords.shape[1], bias_n.shape[2]
+
+
+def joint_sample(sup, bias_d, bias_n, ref, coords, u=None):
+    """The sampling of one alignment step in one kernel (perf_joint_sample): sup [P,7,R,R], bias_d [P,1,R,R], bias_n [P,3,Rn,Rn],
+    ref [2,H,W] (panorama distance, mask), coords [P,B,2] or [P,B,1,2] in [-1,1] -> (u [P*B,3], rec [P*B, JOINT_RECORD]) with
+    rec = [sd | db | sn (3) | nb (3) | pr | pm | 0 | 0].  u: None (the kernel forms the directions) or fp32 [P*B,3], the directions the
+    caller formed from the same maps and coordinates: taken as they are and returned.  No graph is recorded."""
+    if sup.dim() != 4 or sup.shape[1] != 7 or sup.shape[2] != sup.shape[3] or ref.dim() != 3 or ref.shape[0] != 2:
+        raise _lib.PerfError(f'joint_sample: sup must be [P, 7, R, R] and ref [2, H, W], got {tuple(sup.shape)} and {tuple(ref.shape)}')
+    P, R = sup.shape[0], sup.shape[2]
+    B, Rn = _joint_dims('joint_sample', P, R, bias_d, bias_n, coords)
+    if u is not None and u.shape != (P * B, 3):
+        raise _lib.PerfError(f'joint_sample: u must be [{P * B}, 3], got {tuple(u.shape)}')
+    given = u
+    if u is None:
+        u = torch.empty(P * B, 3, dtype=torch.float32, device=sup.device)
+    rec = torch.empty(P * B, _lib.JOINT_RECORD, dtype=torch.float32, device=sup.device)
+    _call('perf_joint_sample', _p(_f32(sup, 'sup')), _p(_f32(bias_d, 'bias_d')), _p(_f32(bias_n, 'bias_n')), _p(_f32(ref, 'ref')),
+          _p(_f32(coords, 'coords')), _p(None if given is None else _f32(given, 'u')), P, B, R, Rn, ref.shape[1], ref.shape[2], _p(u), _p(rec),
+          _stream())
+    return u, rec
+
+
+def joint_loss(rec, coords, scale, u, d, g, o, R, Rn, w_ref, w_reg, w_n, w_ntv=0.0, tv=None, gbias_d=None, gbias_n=None, ws=None):
+    """The losses of one alignment step and the gradients the head owns (perf_joint_loss) -> (losses [JOINT_LOSSES] = [L_d, L_n, L_reg,
+    L_ref, TV_d, TV_n, total, 0], dd [N] = d total/d d, dg [N,3] = d total/d g, dscale [P]); deterministic.  tv: two device floats
+    (TV_d, TV_n) or None.  gbias_d [P,1,R,R], gbias_n [P,3,Rn,Rn] (both or neither): d total/d db and d total/d nb are scattered ON
+    TOP of their contents with fp32 atomics (order-dependent in the last bits); None: the maps get nothing.  ws: a Workspace."""
+    P = scale.numel()
+    N = rec.shape[0]
+    if P < 1 or N % P or coords.numel() != 2 * N or u.shape != (N, 3) or g.shape != (N, 3) or o.numel() != 3 * N or d.numel() != N:
+        raise _lib.PerfError(f'joint_loss: {N} records do not go with scale {tuple(scale.shape)}, coords {tuple(coords.shape)}, u {tuple(u.shape)}, '
+                             f'd {tuple(d.shape)}, g {tuple(g.shape)}, o {tuple(o.shape)}')
+    if (gbias_d is None) != (gbias_n is None) or (gbias_d is not None and (gbias_d.shape != (P, 1, R, R) or gbias_n.shape != (P, 3, Rn, Rn))):
+        raise _lib.PerfError('joint_loss: gbias_d [P,1,R,R] and gbias_n [P,3,Rn,Rn] come together, in these shapes')
+    if tv is not None and tv.numel() != 2:
+        raise _lib.PerfError('joint_loss: tv holds two values (TV_d, TV_n)')
+    B = N // P
+    dev = rec.device
+    losses = torch.empty(_lib.JOINT_LOSSES, dtype=torch.float32, device=dev)
+    dd = torch.empty(N, dtype=torch.float32, device=dev)
+    dg = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    dscale = torch.empty(P, dtype=torch.float32, device=dev)
+    nbytes = _lib.load().perf_joint_loss_workspace_bytes(P, B)
+    if nbytes < 0:
+        _lib.check(-1, 'perf_joint_loss_workspace_bytes')
+    block = (ws or Workspace()).get(nbytes, dev)
+    _call('perf_joint_loss', _p(_f32(rec, 'rec')), _p(_f32(coords, 'coords')), _p(_f32(scale, 'scale')), _p(_f32(u, 'u')), _p(_f32(d, 'd')),
+          _p(_f32(g, 'g')), _p(_f32(o, 'o')), P, B, int(R), int(Rn), float(w_ref), float(w_reg), float(w_n), float(w_ntv),
+          _p(None if tv is None else _f32(tv, 'tv')), _p(losses), _p(dd), _p(dg), _p(dscale),
+          _p(None if gbias_d is None else _f32(gbias_d, 'gbias_d')), _p(None if gbias_n is None else _f32(gbias_n, 'gbias_n')), _p(block),
+          block.numel() * 4, _stream())
+    return losses, dd, dg, dscale
+
+
+def joint_tv(m, weight=1.0, grad=None, value=None, ws=None):
+    """Total variation of a map [n,C,H,W] with smooth-L1(beta=0.01) (perf_joint_tv) -> (value [1], the unweighted TV; grad [n,C,H,W] =
+    weight * dTV/dm, WRITTEN in full, gather form: deterministic).  grad / value: buffers to write into (value: one float)."""
+    if m.dim() != 4:
+        raise _lib.PerfError(f'joint_tv: the map must be [n, C, H, W], got {tuple(m.shape)}')
+    n, C, H, W = m.shape
+    if grad is None:
+        grad = torch.empty_like(m, memory_format=torch.contiguous_format)
+    if value is None:
+        value = torch.empty(1, dtype=torch.float32, device=m.device)
+    if grad.shape != m.shape or value.numel() != 1:
+        raise _lib.PerfError('joint_tv: grad has the map\'s shape and value one element')
+    nbytes = _lib.load().perf_joint_tv_workspace_bytes(n, C, H, W)
+    if nbytes < 0:
+        _lib.check(-1, 'perf_joint_tv_workspace_bytes')
+    block = (ws or Workspace()).get(nbytes, m.device)
+    _call('perf_joint_tv', _p(_f32(m, 'map')), n, C, H, W, float(weight), _p(_f32(grad, 'grad')), _p(_f32(value, 'value')), _p(block),
+          block.numel() * 4, _stream())
+    return value, grad
+
+
 def normal_composite(weights, grad, packed):
     """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
     R = packed.shape[0]

@@ -2,7 +2,8 @@
 """Digest of the C ABI declared in include/perf_hip.h (`--ext`: of its extension, include/perf_hip_ext.h, versioned by
 PERF_EXT_ABI_VERSION and recorded in include/perf_hip_ext.abi.json; `--sphere`: of the sphere distance field's header,
 include/perf_hip_sphere.h, PERF_SPHERE_ABI_VERSION, include/perf_hip_sphere.abi.json; `--pair`: of the pair table's header,
-include/perf_hip_pair.h, PERF_PAIR_ABI_VERSION, include/perf_hip_pair.abi.json): sha256 over the comment-free, whitespace-normalised text of every
+include/perf_hip_pair.h, PERF_PAIR_ABI_VERSION, include/perf_hip_pair.abi.json; `--joint`: of the joint predictor's alignment step,
+include/perf_hip_joint.h, PERF_JOINT_ABI_VERSION, include/perf_hip_joint.abi.json): sha256 over the comment-free, whitespace-normalised text of every
 `perf_*` prototype, struct and #define, in file order.  `python tools/abi_digest.py` prints {version, digest};
 `--write` records it in include/perf_hip.abi.json.  tests/test_cpu_oracle.py fails when the digest of the header differs
 from the recorded one while PERF_ABI_VERSION is unchanged: every signature change must bump the version (the load-time
@@ -22,6 +23,8 @@ SPHERE_HEADER = os.path.join(ROOT, 'include', 'perf_hip_sphere.h')
 SPHERE_RECORD = os.path.join(ROOT, 'include', 'perf_hip_sphere.abi.json')
 PAIR_HEADER = os.path.join(ROOT, 'include', 'perf_hip_pair.h')
 PAIR_RECORD = os.path.join(ROOT, 'include', 'perf_hip_pair.abi.json')
+JOINT_HEADER = os.path.join(ROOT, 'include', 'perf_hip_joint.h')
+JOINT_RECORD = os.path.join(ROOT, 'include', 'perf_hip_joint.abi.json')
 
 
 def digest(path=HEADER, macro='PERF_ABI_VERSION'):
@@ -35,9 +38,9 @@ def digest(path=HEADER, macro='PERF_ABI_VERSION'):
 
 
 if __name__ == '__main__':
-    ext, sphere, pair = '--ext' in sys.argv, '--sphere' in sys.argv, '--pair' in sys.argv
-    d = digest(PAIR_HEADER, 'PERF_PAIR_ABI_VERSION') if pair else digest(SPHERE_HEADER, 'PERF_SPHERE_ABI_VERSION') if sphere else digest(EXT_HEADER, 'PERF_EXT_ABI_VERSION') if ext else digest()
-    record = PAIR_RECORD if pair else SPHERE_RECORD if sphere else EXT_RECORD if ext else RECORD
+    ext, sphere, pair, joint = '--ext' in sys.argv, '--sphere' in sys.argv, '--pair' in sys.argv, '--joint' in sys.argv
+    d = digest(JOINT_HEADER, 'PERF_JOINT_ABI_VERSION') if joint else digest(PAIR_HEADER, 'PERF_PAIR_ABI_VERSION') if pair else digest(SPHERE_HEADER, 'PERF_SPHERE_ABI_VERSION') if sphere else digest(EXT_HEADER, 'PERF_EXT_ABI_VERSION') if ext else digest()
+    record = JOINT_RECORD if joint else PAIR_RECORD if pair else SPHERE_RECORD if sphere else EXT_RECORD if ext else RECORD
     if '--write' in sys.argv:
         json.dump(d, open(record, 'w'), indent=1)
         open(record, 'a').write('\n')

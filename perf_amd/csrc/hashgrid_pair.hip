@@ -56,60 +56,49 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_pair_kernel(GridParams gp, P
         lv[0] = plan.level[part][slot][0]; lv[1] = plan.level[part][slot][1];
         if (lv[0] < 0 && lv[1] < 0) continue;                    // (a padding slot)
         const float x = x01[3 * ii], y = x01[3 * ii + 1], z = x01[3 * ii + 2];
-        Corners c[2];
-        bool head[2], share[2];
-        uint32_t src[2];
-        uint2 v[2][8];
-#pragma unroll
+        // one level at a time, the loop kept rolled: corners, run-sharing state and the eight words of ONE level are live at once, which
+        // is what holds the kernel to 64 VGPRs (eight waves per SIMD); the joint two-level body took 114 (four)
+#pragma unroll 1
         for (int pass = 0; pass < 2; ++pass) {
-            head[pass] = lv[pass] >= 0; share[pass] = false; src[pass] = lane;
-            if (lv[pass] < 0) continue;
             const int l = lv[pass];
-            c[pass] = corners_of(x, y, z, gp.scale[l], gp.res[l], gp.size[l], gp.hashed[l] != 0);
+            if (l < 0) continue;
+            const Corners c = corners_of(x, y, z, gp.scale[l], gp.res[l], gp.size[l], gp.hashed[l] != 0);
             // lane - 1's cell through DPP (wave_shr:1; lane 0 keeps the `old` operand)
-            const uint32_t px = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)c[pass].cell[0], 0x138, 0xf, 0xf, false);
-            const uint32_t py = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)c[pass].cell[1], 0x138, 0xf, 0xf, false);
-            const uint32_t pz = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)c[pass].cell[2], 0x138, 0xf, 0xf, false);
-            const bool same = lane != 0u && px == c[pass].cell[0] && py == c[pass].cell[1] && pz == c[pass].cell[2];
+            const uint32_t px = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)c.cell[0], 0x138, 0xf, 0xf, false);
+            const uint32_t py = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)c.cell[1], 0x138, 0xf, 0xf, false);
+            const uint32_t pz = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)c.cell[2], 0x138, 0xf, 0xf, false);
+            const bool same = lane != 0u && px == c.cell[0] && py == c.cell[1] && pz == c.cell[2];
             const unsigned long long heads = __ballot(!same);
-            share[pass] = __popcll(heads) <= kPairShareMaxHeads;      // wave-uniform
-            if (share[pass]) {
-                head[pass] = !same;
-                src[pass] = 63u - (uint32_t)__clzll((long long)(heads & below));     // the head of my run
+            const bool share = __popcll(heads) <= kPairShareMaxHeads;      // wave-uniform
+            const bool head = share ? !same : true;
+            const uint32_t src = share ? 63u - (uint32_t)__clzll((long long)(heads & below)) : lane;     // the head of my run
+            uint2 v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = make_uint2(0u, 0u);
+            if (head) {
+                const uint2* t = pair + gp.offset[l];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = t[c.idx[k]];
             }
-        }
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[pass][k] = make_uint2(0u, 0u);
-            if (head[pass]) {
-                const uint2* t = pair + gp.offset[lv[pass]];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) v[pass][k] = t[c[pass].idx[k]];
-            }
-        }
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            if (lv[pass] < 0) continue;
-            if (share[pass]) {
+            if (share) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    v[pass][k].x = (uint32_t)__shfl((int)v[pass][k].x, (int)src[pass]);
-                    v[pass][k].y = (uint32_t)__shfl((int)v[pass][k].y, (int)src[pass]);
+                    v[k].x = (uint32_t)__shfl((int)v[k].x, (int)src);
+                    v[k].y = (uint32_t)__shfl((int)v[k].y, (int)src);
                 }
             }
             float w[8];
-            corner_weights(c[pass].f, smooth, w);
+            corner_weights(c.f, smooth, w);
             float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                a0 = fmaf(w[k], T16::lo(v[pass][k].x), a0);
-                a1 = fmaf(w[k], T16::hi(v[pass][k].x), a1);
-                b0 = fmaf(w[k], T16::lo(v[pass][k].y), b0);
-                b1 = fmaf(w[k], T16::hi(v[pass][k].y), b1);
+                a0 = fmaf(w[k], T16::lo(v[k].x), a0);
+                a1 = fmaf(w[k], T16::hi(v[k].x), a1);
+                b0 = fmaf(w[k], T16::lo(v[k].y), b0);
+                b1 = fmaf(w[k], T16::hi(v[k].y), b1);
             }
             if (live) {
-                const int64_t o = (int64_t)lv[pass] * n + i;
+                const int64_t o = (int64_t)l * n + i;
                 feat_a[o] = T16::pack(a0, a1);
                 feat_b[o] = T16::pack(b0, b1);
             }
@@ -128,6 +117,8 @@ __global__ __launch_bounds__(256) void pair_fill_kernel(uint32_t* __restrict__ p
 // single encodes (tools/exp/pair_encode.py, profiles/pair_encode.json): this grouping 0.218 ms; every level alone in two halves of eight
 // 0.235; the single encode's {g, 15 - g} (two hashed levels, 4 MiB, on half the XCDs) 0.234 -- on uniform points 0.382, where this grouping
 // takes 0.321; non-temporal feature stores change nothing (0.218).  The retired switches: tools/exp/pair_encode_variants.diff.
+// Measured again with the level-at-a-time body at eight waves per SIMD (profiles/pair_levels.json): this grouping 0.205, every level alone
+// 0.221 (uniform points 0.322 either way); held to five waves 0.207, two samples per thread 0.223: tools/exp/pair_levels_variants.diff.
 static void pair_plan(const GridParams& gp, PairPlan* plan) {
     int slot[16][2], n_slots = 0;
     const int L = gp.n_levels;

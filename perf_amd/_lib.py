@@ -15,6 +15,7 @@ EXT_ABI_VERSION = 1      # PERF_EXT_ABI_VERSION of include/perf_hip_ext.h (entry
 SPHERE_ABI_VERSION = 1   # PERF_SPHERE_ABI_VERSION of include/perf_hip_sphere.h (the sphere distance field)
 PAIR_ABI_VERSION = 1     # PERF_PAIR_ABI_VERSION of include/perf_hip_pair.h (the pair table of two fields with one grid geometry)
 JOINT_ABI_VERSION = 1    # PERF_JOINT_ABI_VERSION of include/perf_hip_joint.h (the joint predictor's alignment step)
+MESH_ABI_VERSION = 1     # PERF_MESH_ABI_VERSION of include/perf_hip_mesh.h (surface nets on a dense lattice)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -177,6 +178,15 @@ _SIGS_JOINT = {
     'perf_joint_tv': (c_int, [P, c_int64, c_int32, c_int32, c_int32, c_float, P, P, P, c_int64, P]),
 }
 
+# include/perf_hip_mesh.h: surface nets on a dense lattice, exported from the same library, versioned on its own (perf_mesh_version)
+MESH_MAX_CELLS = 1 << 30     # PERF_MESH_MAX_CELLS
+_SIGS_MESH = {
+    'perf_mesh_version': (c_int, []),
+    'perf_mesh_workspace_bytes': (c_int64, [c_int32, c_int32, c_int32]),
+    'perf_mesh_count': (c_int, [P, c_int32, c_int32, c_int32, c_float, P, c_int64, P, P]),
+    'perf_mesh_write': (c_int, [P, c_int32, c_int32, c_int32, c_float, POINTER(c_float), POINTER(c_float), P, c_int64, P, c_int64, P, c_int64, P]),
+}
+
 _lib = None
 
 
@@ -192,7 +202,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
@@ -213,6 +223,9 @@ def load():
                         'rebuild with `python -m perf_amd.build --force`')
     if lib.perf_joint_version() != JOINT_ABI_VERSION:
         raise PerfError(f'{LIB_PATH} has joint-alignment ABI version {lib.perf_joint_version()}, this binding expects {JOINT_ABI_VERSION}: '
+                        'rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_mesh_version() != MESH_ABI_VERSION:
+        raise PerfError(f'{LIB_PATH} has mesh ABI version {lib.perf_mesh_version()}, this binding expects {MESH_ABI_VERSION}: '
                         'rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):

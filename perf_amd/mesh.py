@@ -1,0 +1,126 @@
+"""A triangle mesh of the trained density: the field is evaluated on a dense lattice over the scene's aabb and meshed on the device by
+naive surface nets (include/perf_hip_mesh.h: no case tables, no atomics, bit-identical from run to run).  Not the reference's: PeRF
+writes a point cloud of its input panorama (modules/dataset/dataset.py:110-114) and leaves a trimesh export commented out
+(pano_geo_refiner.py:155-157).
+
+    mesh = scene.extract_mesh(resolution=256, colors=True, normals=True)
+    write_ply('room.ply', mesh)
+"""
+import math
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+
+class Mesh(NamedTuple):
+    vertices: torch.Tensor                       # [V, 3] fp32, world units
+    faces: torch.Tensor                          # [F, 3] int32; normals point from high density to low
+    colors: Optional[torch.Tensor] = None        # [V, 3] fp32 in [0, 1]
+    normals: Optional[torch.Tensor] = None       # [V, 3] fp32, unit or zero
+
+
+def surface_nets(field, thr, lo, hi) -> Mesh:
+    """field: CUDA fp32 [nx+1, ny+1, nz+1] corner values (z fastest); a corner is inside iff field >= thr; lo, hi: the box the lattice
+    spans, three values each.  Two kernels around ONE host read of the two counts (count -> allocate -> write)."""
+    field = field.contiguous()
+    counts, ws = ops.mesh_count(field, thr)
+    n_vertices, n_faces = (int(v) for v in counts.tolist())          # the one host synchronisation of an extraction
+    vertices, faces = ops.mesh_write(field, thr, lo, hi, ws, n_vertices, n_faces)
+    return Mesh(vertices, faces)
+
+
+@torch.no_grad()
+def density_lattice(scene, resolution, use_occupancy=True, chunk=1 << 22):
+    """sigma at the (resolution + 1)^3 corners of the scene's aabb -> fp32 [res+1, res+1, res+1].  Corner i sits at x01 = i / res; the
+    border corners fail the field's strict 0 < x01 < 1 selector and are exactly 0, which closes every surface at the box.
+    use_occupancy: sigma is zeroed where the estimator's `binaries` cell of the point is empty (the cell of a point by the rule the
+    grid was built with, sup_info.py:318: int(clip(x01, 0.0005, 0.9995) * res_occ) per axis) -- the field is untrained outside the
+    shell the occupancy marks.  chunk: corners per density_at call."""
+    res = int(resolution)
+    if res < 1 or res ** 3 > _lib.MESH_MAX_CELLS:
+        raise _lib.PerfError(f'density_lattice: resolution {resolution} is outside 1 .. 1024')
+    nerf, est = scene.nerf, scene.estimator
+    dev = nerf.aabb.device
+    n1 = res + 1
+    total = n1 ** 3
+    out = torch.empty(total, dtype=torch.float32, device=dev)
+    occ = est.binaries.reshape(-1) if use_occupancy else None
+    occ_res = int(est._res)
+    for start in range(0, total, int(chunk)):
+        idx = torch.arange(start, min(start + int(chunk), total), dtype=torch.int64, device=dev)
+        ijk = torch.stack([idx // (n1 * n1), (idx // n1) % n1, idx % n1], dim=1)
+        x01 = (ijk.float() / float(res)).contiguous()
+        sel = ((x01 > 0) & (x01 < 1)).all(dim=1).to(torch.uint8)
+        sigma = nerf.density_at(x01, sel).float()
+        if occ is not None:
+            cell = (x01.clamp(0.0005, 0.9995) * occ_res).long()
+            sigma = torch.where(occ[(cell[:, 0] * occ_res + cell[:, 1]) * occ_res + cell[:, 2]], sigma, torch.zeros_like(sigma))
+        out[start:start + idx.numel()] = sigma
+    return out.view(n1, n1, n1)
+
+
+@torch.no_grad()
+def vertex_colors(scene, vertices, chunk=1 << 22):
+    """query_rgb at world positions [V, 3] -> fp32 [V, 3]."""
+    if not len(vertices):
+        return vertices.new_zeros(0, 3)
+    return torch.cat([scene.nerf.query_rgb(v).float() for v in vertices.split(chunk)])
+
+
+@torch.no_grad()
+def vertex_normals(scene, vertices, chunk=1 << 22):
+    """query_normal at world positions [V, 3] -> fp32 [V, 3], unit or zero."""
+    if not len(vertices):
+        return vertices.new_zeros(0, 3)
+    return torch.cat([scene.nerf.query_normal(v)[1].float() for v in vertices.split(chunk)])
+
+
+@torch.no_grad()
+def extract_mesh(scene, resolution=256, threshold=None, use_occupancy=True, colors=False, normals=False) -> Mesh:
+    """The iso-surface sigma = threshold of the scene's density over its aabb.  threshold None: ln 2 / renderer.render_step_size, the
+    density at which one render step is half opaque.  colors: query_rgb at the vertices; normals: query_normal at the vertices
+    (-grad sigma, unit or zero: the side the density falls towards, as the faces' orientation)."""
+    if threshold is None:
+        threshold = math.log(2.0) / float(scene.renderer.render_step_size)
+    aabb = scene.nerf._aabb_host
+    field = density_lattice(scene, resolution, use_occupancy)
+    vertices, faces, _, _ = surface_nets(field, threshold, aabb[:3], aabb[3:])
+    rgb = nrm = None
+    if colors:
+        rgb = vertex_colors(scene, vertices)
+    if normals:
+        nrm = vertex_normals(scene, vertices)
+    return Mesh(vertices, faces, rgb, nrm)
+
+
+def write_ply(path, mesh):
+    """Binary little-endian PLY: x y z [nx ny nz] [red green blue as uchar] per vertex, a uchar-counted int list per face."""
+    v = mesh.vertices.detach().cpu().numpy().astype('<f4')
+    f = mesh.faces.detach().cpu().numpy().astype('<i4')
+    fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+    if mesh.normals is not None:
+        fields += [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
+    if mesh.colors is not None:
+        fields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+    rows = np.empty(len(v), dtype=fields)
+    rows['x'], rows['y'], rows['z'] = v[:, 0], v[:, 1], v[:, 2]
+    if mesh.normals is not None:
+        n = mesh.normals.detach().cpu().numpy().astype('<f4')
+        rows['nx'], rows['ny'], rows['nz'] = n[:, 0], n[:, 1], n[:, 2]
+    if mesh.colors is not None:
+        c = np.rint(np.clip(mesh.colors.detach().cpu().numpy(), 0.0, 1.0) * 255.0).astype('u1')
+        rows['red'], rows['green'], rows['blue'] = c[:, 0], c[:, 1], c[:, 2]
+    tris = np.empty(len(f), dtype=[('n', 'u1'), ('i', '<i4', (3,))])
+    tris['n'] = 3
+    tris['i'] = f
+    names = {'<f4': 'float', 'u1': 'uchar'}
+    header = ['ply', 'format binary_little_endian 1.0', f'element vertex {len(v)}']
+    header += [f'property {names[t]} {k}' for k, t in fields]
+    header += [f'element face {len(f)}', 'property list uchar int vertex_indices', 'end_header']
+    with open(path, 'wb') as out:
+        out.write(('\n'.join(header) + '\n').encode('ascii'))
+        out.write(rows.tobytes())
+        out.write(tris.tobytes())

@@ -738,6 +738,42 @@ def joint_tv(m, weight=1.0, grad=None, value=None, ws=None):
     return value, grad
 
 
+# ---- surface nets on a dense lattice (include/perf_hip_mesh.h) -------------------------------------------------------------------------
+def _mesh_cells(who, field):
+    if field.dim() != 3 or min(field.shape) < 2:
+        raise _lib.PerfError(f'{who}: the field must be [nx+1, ny+1, nz+1] corner values with at least one cell per axis, got {tuple(field.shape)}')
+    return tuple(int(s) - 1 for s in field.shape)
+
+
+def mesh_count(field, thr, ws=None):
+    """Classify the cells of a lattice of fp32 corner values [nx+1, ny+1, nz+1] against thr (perf_mesh_count) -> (counts, ws): counts =
+    int64 [2] ON THE DEVICE (vertices, triangles), ws = the int64 workspace that mesh_write needs (pass one back in to reuse it)."""
+    nx, ny, nz = _mesh_cells('mesh_count', field)
+    nbytes = _lib.load().perf_mesh_workspace_bytes(nx, ny, nz)
+    if nbytes < 0:
+        _lib.check(-1, 'perf_mesh_workspace_bytes')
+    if ws is None or ws.numel() * 8 < nbytes or ws.device != field.device:
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=field.device)
+    counts = torch.empty(2, dtype=torch.int64, device=field.device)
+    _call('perf_mesh_count', _p(_f32(field, 'field')), nx, ny, nz, float(thr), _p(ws), ws.numel() * 8, _p(counts), _stream())
+    return counts, ws
+
+
+def mesh_write(field, thr, lo, hi, ws, n_vertices, n_faces):
+    """The vertices [n_vertices, 3] fp32 and faces [n_faces, 3] int32 of the lattice mesh_count classified into ws (perf_mesh_write); the
+    same field and thr.  lo, hi: the box's bounds, three values each.  The two counts are what the caller read from mesh_count's totals:
+    smaller ones are refused."""
+    nx, ny, nz = _mesh_cells('mesh_write', field)
+    lo3, hi3 = [float(v) for v in lo], [float(v) for v in hi]
+    if len(lo3) != 3 or len(hi3) != 3:
+        raise _lib.PerfError('mesh_write: lo and hi hold three values each')
+    vertices = torch.empty(int(n_vertices), 3, dtype=torch.float32, device=field.device)
+    faces = torch.empty(int(n_faces), 3, dtype=torch.int32, device=field.device)
+    _call('perf_mesh_write', _p(_f32(field, 'field')), nx, ny, nz, float(thr), (ctypes.c_float * 3)(*lo3), (ctypes.c_float * 3)(*hi3), _p(ws),
+          ws.numel() * 8, _p(vertices) if n_vertices else None, int(n_vertices), _p(faces) if n_faces else None, int(n_faces), _stream())
+    return vertices, faces
+
+
 def normal_composite(weights, grad, packed):
     """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
     R = packed.shape[0]

@@ -1570,6 +1570,11 @@ class NeRFScene:
     def set_eval(self):
         self.nerf.eval(); self.estimator.eval(); self.renderer.eval()
 
+    def extract_mesh(self, **kw):
+        """A triangle mesh of the trained density (perf_amd/mesh.py: extract_mesh's keywords) -> mesh.Mesh."""
+        from .mesh import extract_mesh
+        return extract_mesh(self, **kw)
+
 
 def psnr(pred, gt):
     """-10 log10(mean((pred-gt)^2))  (the reference never computes it)."""

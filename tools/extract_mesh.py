@@ -1,0 +1,47 @@
+"""Write the trained density as a triangle mesh (binary PLY): trains the synthetic room, or loads a checkpoint of NeRFScene.state_dict().
+
+  python tools/extract_mesh.py --out room.ply [--resolution 256] [--threshold T] [--no-occupancy] [--no-colors] [--no-normals]
+                               [--checkpoint scene.pt | --geo 3000 --app 1500] [--dtype fp16]
+
+Prints one JSON line: the counts, the threshold and the seconds of training and extraction."""
+import argparse, json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from perf_amd import synthetic
+from perf_amd.mesh import write_ply
+from perf_amd.scene import NeRFScene, SupInfoPool, gen_pano_rays
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--out', required=True)
+ap.add_argument('--resolution', type=int, default=256)
+ap.add_argument('--threshold', type=float, default=None, help='default: ln 2 / render_step_size')
+ap.add_argument('--no-occupancy', action='store_true', help='keep the density where the occupancy grid is empty (the field is untrained there)')
+ap.add_argument('--no-colors', action='store_true')
+ap.add_argument('--no-normals', action='store_true')
+ap.add_argument('--checkpoint', default=None, help='a torch.save of NeRFScene.state_dict()')
+ap.add_argument('--geo', type=int, default=3000)
+ap.add_argument('--app', type=int, default=1500)
+ap.add_argument('--batch', type=int, default=4096)
+ap.add_argument('--dtype', default='fp16')
+args = ap.parse_args()
+
+torch.manual_seed(0); np.random.seed(0)
+scene = NeRFScene(dtype=args.dtype)
+t0 = time.perf_counter()
+if args.checkpoint:
+    scene.load_state_dict(torch.load(args.checkpoint, map_location='cuda'))
+else:
+    rays = gen_pano_rays(torch.eye(4), 256, 512)
+    dist, rgb = synthetic.room(rays.d)
+    pool = SupInfoPool(); pool.register_rays(rays.o, rays.d, rgb, dist)
+    scene.train_conf.pixel_loss_batch_size = args.batch
+    scene.train_one_episode(pool, args.geo, args.app)
+scene.set_eval()
+torch.cuda.synchronize(); t1 = time.perf_counter()
+mesh = scene.extract_mesh(resolution=args.resolution, threshold=args.threshold, use_occupancy=not args.no_occupancy, colors=not args.no_colors,
+                          normals=not args.no_normals)
+torch.cuda.synchronize(); t2 = time.perf_counter()
+write_ply(args.out, mesh)
+print(json.dumps({'out': args.out, 'vertices': len(mesh.vertices), 'faces': len(mesh.faces), 'resolution': args.resolution,
+                  'threshold': args.threshold, 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'bytes': os.path.getsize(args.out)}))

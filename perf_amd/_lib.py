@@ -16,6 +16,7 @@ SPHERE_ABI_VERSION = 1   # PERF_SPHERE_ABI_VERSION of include/perf_hip_sphere.h 
 PAIR_ABI_VERSION = 1     # PERF_PAIR_ABI_VERSION of include/perf_hip_pair.h (the pair table of two fields with one grid geometry)
 JOINT_ABI_VERSION = 1    # PERF_JOINT_ABI_VERSION of include/perf_hip_joint.h (the joint predictor's alignment step)
 MESH_ABI_VERSION = 1     # PERF_MESH_ABI_VERSION of include/perf_hip_mesh.h (surface nets on a dense lattice)
+BRICKMESH_ABI_VERSION = 1    # PERF_BRICKMESH_ABI_VERSION of include/perf_hip_brickmesh.h (surface nets on the live bricks of a lattice)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -187,6 +188,21 @@ _SIGS_MESH = {
     'perf_mesh_write': (c_int, [P, c_int32, c_int32, c_int32, c_float, POINTER(c_float), POINTER(c_float), P, c_int64, P, c_int64, P, c_int64, P]),
 }
 
+# include/perf_hip_brickmesh.h: surface nets on the live 8^3 bricks of a lattice, versioned on its own (perf_brickmesh_version)
+BRICKMESH_EDGE = 8                   # PERF_BRICKMESH_EDGE
+BRICKMESH_MAX_DIM = 4096             # PERF_BRICKMESH_MAX_DIM
+BRICKMESH_MAX_BRICKS = 1 << 21       # PERF_BRICKMESH_MAX_BRICKS
+_SIGS_BRICKMESH = {
+    'perf_brickmesh_version': (c_int, []),
+    'perf_brickmesh_workspace_bytes': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    'perf_brickmesh_select': (c_int, [P, c_int32, c_int32, c_int32, c_int32, P, P, P, c_int64, P]),
+    'perf_brickmesh_list': (c_int, [P, c_int32, c_int32, c_int32, P, c_int32, P]),
+    'perf_brickmesh_corners': (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, P, c_int32, P, P, P, P]),
+    'perf_brickmesh_count': (c_int, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, P, c_int64, P, P]),
+    'perf_brickmesh_write': (c_int, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, POINTER(c_float), POINTER(c_float), P, c_int64, P, c_int64,
+                                     P, c_int64, P, P]),
+}
+
 _lib = None
 
 
@@ -202,7 +218,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
@@ -226,6 +242,9 @@ def load():
                         'rebuild with `python -m perf_amd.build --force`')
     if lib.perf_mesh_version() != MESH_ABI_VERSION:
         raise PerfError(f'{LIB_PATH} has mesh ABI version {lib.perf_mesh_version()}, this binding expects {MESH_ABI_VERSION}: '
+                        'rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_brickmesh_version() != BRICKMESH_ABI_VERSION:
+        raise PerfError(f'{LIB_PATH} has brick-mesh ABI version {lib.perf_brickmesh_version()}, this binding expects {BRICKMESH_ABI_VERSION}: '
                         'rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):

@@ -7,6 +7,7 @@
 // rows of i + 1 are read again by the wave of i + 1 (through the caches); they are not staged in LDS.  The write pass touches the field
 // only where a cell is active.
 #include "common.hpp"
+#include "mesh_device.hpp"
 #include "../../include/perf_hip_mesh.h"
 
 namespace perf {
@@ -121,10 +122,6 @@ __global__ void __launch_bounds__(kScanItems) mesh_scan_add_kernel(uint64_t* __r
     if (idx < n) data[idx] += prefix[blockIdx.x];
 }
 
-struct MeshBox {
-    double lo[3], scale[3];          // world = lo + p * scale, scale = (hi - lo) / n
-};
-
 __device__ __forceinline__ int32_t rank_of(const uint64_t* __restrict__ masks, const uint64_t* __restrict__ ranks, const MeshDims& d, int32_t i, int32_t j, int32_t k) {
     const int64_t ch = ((int64_t)i * d.ny + j) * d.cz + (k >> 6);
     return (int32_t)(ranks[ch] & 0xffffffffull) + __popcll(masks[ch] & ((1ull << (k & 63)) - 1));
@@ -151,33 +148,13 @@ __device__ __forceinline__ void write_chunk(const float* __restrict__ field, con
         v[0] = c0[0]; v[1] = c0[1]; v[2] = c0[row_stride]; v[3] = c0[row_stride + 1];
         v[4] = c1[0]; v[5] = c1[1]; v[6] = c1[row_stride]; v[7] = c1[row_stride + 1];
         bool in[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) in[c] = v[c] >= thr;
-        // the 12 edges: pairs a < b of corners that differ in one offset, in lexicographic order of (a, b)
-        constexpr int ea[12] = {0, 0, 0, 1, 1, 2, 2, 3, 4, 4, 5, 6};
-        constexpr int eb[12] = {1, 2, 4, 3, 5, 3, 6, 7, 5, 6, 7, 7};
-        double sum[3] = {0.0, 0.0, 0.0};
-        int crossings = 0;
-#pragma unroll
-        for (int e = 0; e < 12; ++e) {
-            const int a = ea[e], b = eb[e];
-            if (in[a] != in[b]) {
-                double t = ((double)thr - (double)v[a]) / ((double)v[b] - (double)v[a]);
-                if (t != t) t = 0.5;
-                t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
-                const int axis = (b - a) == 4 ? 0 : ((b - a) == 2 ? 1 : 2);
-                sum[0] += (axis == 0) ? t : (double)((a >> 2) & 1);
-                sum[1] += (axis == 1) ? t : (double)((a >> 1) & 1);
-                sum[2] += (axis == 2) ? t : (double)(a & 1);
-                ++crossings;
-            }
-        }
+        float w[3];
+        mesh_cell_vertex(v, thr, i, j, k, box, in, w);          // (mesh_device.hpp: the arithmetic the brick unit shares)
         const int64_t rank = (int64_t)(packed & 0xffffffffull) + __popcll(active & below);
         if (rank < vertex_capacity) {
-            const double px = (double)i + sum[0] / (double)crossings, py = (double)j + sum[1] / (double)crossings, pz = (double)k + sum[2] / (double)crossings;
-            vertices[3 * rank + 0] = (float)(box.lo[0] + px * box.scale[0]);
-            vertices[3 * rank + 1] = (float)(box.lo[1] + py * box.scale[1]);
-            vertices[3 * rank + 2] = (float)(box.lo[2] + pz * box.scale[2]);
+            vertices[3 * rank + 0] = w[0];
+            vertices[3 * rank + 1] = w[1];
+            vertices[3 * rank + 2] = w[2];
         }
         in0 = in[0];
         qx = (in[0] != in[4]) && j >= 1 && k >= 1;

@@ -96,6 +96,82 @@ def extract_mesh(scene, resolution=256, threshold=None, use_occupancy=True, colo
     return Mesh(vertices, faces, rgb, nrm)
 
 
+# ---- only the occupied bricks of the lattice (include/perf_hip_brickmesh.h) ---------------------------------------------------------------
+def _brick_shape(n):
+    shape = (int(n),) * 3 if isinstance(n, (int, np.integer)) else tuple(int(v) for v in n)
+    if len(shape) != 3 or any(v < _lib.BRICKMESH_EDGE or v % _lib.BRICKMESH_EDGE or v > _lib.BRICKMESH_MAX_DIM for v in shape):
+        raise _lib.PerfError(f'a brick lattice has three dimensions, each a multiple of {_lib.BRICKMESH_EDGE} in {_lib.BRICKMESH_EDGE} .. {_lib.BRICKMESH_MAX_DIM}: got {n!r}')
+    return shape
+
+
+def select_bricks(binaries, n):
+    """The 8 x 8 x 8-corner bricks of a lattice of n (or (nx, ny, nz)) cells that touch a set cell of the occupancy grid `binaries`
+    (bool [R, R, R]) by the box rule of include/perf_hip_brickmesh.h -> (ids int32 [M] ascending linear brick indices, table int32
+    [Bx, By, Bz]: each brick's position in ids, or -1).  One host read: the live count, to allocate ids."""
+    shape = _brick_shape(n)
+    table, n_live = ops.brickmesh_select(binaries, shape)
+    m = int(n_live.item())
+    if m > _lib.BRICKMESH_MAX_BRICKS:
+        raise _lib.PerfError(f'select_bricks: {m} live bricks of a lattice of {shape} cells are more than 2^21: lower the resolution')
+    return ops.brickmesh_list(table, m), table
+
+
+@torch.no_grad()
+def density_bricks(scene, n, chunk_bricks=8192):
+    """sigma at the stored corners of the live bricks of the scene's lattice of n^3 cells -> (ids, table, values fp32 [M, 8, 8, 8]): at
+    every stored corner the value density_lattice(scene, n) has there, to the bit; every corner that is not stored is 0 there.  The
+    coordinates of a chunk of bricks are generated on the device.  The occupancy stays a select of its own behind the field (as in
+    density_lattice): the field multiplies by its selector, which would turn an overflowed sigma into a NaN instead of 0."""
+    shape = _brick_shape(n)
+    nerf, est = scene.nerf, scene.estimator
+    ids, table = select_bricks(est.binaries, shape)
+    m = int(ids.numel())
+    values = torch.empty(m, 8, 8, 8, dtype=torch.float32, device=ids.device)
+    flat = values.view(m, 512)
+    step = max(int(chunk_bricks), 1)
+    for first in range(0, m, step):
+        count = min(step, m - first)
+        x01, sel, interior = ops.brickmesh_corners(ids, first, count, shape, est.binaries)
+        sigma = nerf.density_at(x01, interior).float()
+        flat[first:first + count] = torch.where(sel.bool(), sigma, torch.zeros_like(sigma)).view(count, 512)
+    return ids, table, values
+
+
+def surface_nets_bricks(values, ids, table, shape, thr, fill, lo, hi):
+    """The mesh of the virtual field that is `fill` (< thr) everywhere but at the stored corners `values` [M, 8, 8, 8] of the bricks
+    (ids, table) of a lattice of `shape` cells -> (Mesh, cells int64 [V]: each vertex's linear cell (i ny + j) nz + k).  Vertices are
+    ordered by (brick slot, cell within the brick).  Raises when the set is not closed: a stored corner >= thr whose eight cells are not
+    all in live bricks."""
+    shape = _brick_shape(shape)
+    values = values.contiguous()
+    counts, ws = ops.brickmesh_count(values, ids, table, shape, thr, fill)
+    n_vertices, n_faces, violations = (int(v) for v in counts.tolist())          # the one host synchronisation of a meshing
+    if violations:
+        raise _lib.PerfError(f'surface_nets_bricks: {violations} quads need the vertex of a cell in a brick that is not in the set: the bricks of all eight cells around a '
+                             'stored corner >= thr must be live')
+    vertices, faces, cells = ops.brickmesh_write(values, ids, table, shape, thr, fill, lo, hi, ws, n_vertices, n_faces)
+    return Mesh(vertices, faces), cells
+
+
+@torch.no_grad()
+def extract_mesh_sparse(scene, resolution=1024, threshold=None, colors=False, normals=False) -> Mesh:
+    """extract_mesh with the occupancy, evaluated and meshed only on the 8^3 bricks of the lattice that touch the occupancy shell: the
+    same vertices (to the bit) and faces in another order, at resolutions up to 4096 (a multiple of 8) as long as at most 2^21 bricks
+    are live.  threshold None: ln 2 / renderer.render_step_size; it must be positive (the lattice outside the bricks is 0)."""
+    if threshold is None:
+        threshold = math.log(2.0) / float(scene.renderer.render_step_size)
+    aabb = scene.nerf._aabb_host
+    shape = _brick_shape(resolution)
+    ids, table, values = density_bricks(scene, shape)
+    mesh, _ = surface_nets_bricks(values, ids, table, shape, threshold, 0.0, aabb[:3], aabb[3:])
+    rgb = nrm = None
+    if colors:
+        rgb = vertex_colors(scene, mesh.vertices)
+    if normals:
+        nrm = vertex_normals(scene, mesh.vertices)
+    return Mesh(mesh.vertices, mesh.faces, rgb, nrm)
+
+
 def write_ply(path, mesh):
     """Binary little-endian PLY: x y z [nx ny nz] [red green blue as uchar] per vertex, a uchar-counted int list per face."""
     v = mesh.vertices.detach().cpu().numpy().astype('<f4')

@@ -774,6 +774,118 @@ def mesh_write(field, thr, lo, hi, ws, n_vertices, n_faces):
     return vertices, faces
 
 
+# ---- surface nets on the live bricks of a lattice (include/perf_hip_brickmesh.h) -------------------------------------------------------
+def _brick_shape(who, shape):
+    n = tuple(int(v) for v in shape)
+    if len(n) != 3:
+        raise _lib.PerfError(f'{who}: the lattice has three dimensions, got {shape!r}')
+    return n
+
+
+def _brick_dev(who, **tensors):
+    for name, t in tensors.items():
+        if not t.is_cuda:
+            raise _lib.PerfError(f'{who}: {name} must be a CUDA tensor (there is no CPU path)')
+
+
+def _brick_i32(t, name):
+    if t.dtype != torch.int32 or not t.is_contiguous():
+        raise _lib.PerfError(f'{name} must be a contiguous int32 tensor')
+    return t
+
+
+def _brick_occ(who, binaries):
+    """binaries: bool or uint8 [..., R, R, R] -> (uint8 view, R)."""
+    if binaries.dtype not in (torch.bool, torch.uint8) or binaries.dim() < 3 or len(set(binaries.shape[-3:])) != 1 or binaries.numel() != binaries.shape[-1] ** 3:
+        raise _lib.PerfError(f'{who}: binaries must be bool or uint8 [R, R, R], got {binaries.dtype} {tuple(binaries.shape)}')
+    b = binaries.contiguous()
+    return (b.view(torch.uint8) if b.dtype == torch.bool else b), int(b.shape[-1])
+
+
+def _brick_ws(shape, n_bricks, ws, device):
+    nbytes = _lib.load().perf_brickmesh_workspace_bytes(*shape, int(n_bricks))
+    if nbytes < 0:
+        _lib.check(-1, 'perf_brickmesh_workspace_bytes')
+    if ws is None or ws.numel() * 8 < nbytes or ws.device != device:
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+    return ws
+
+
+def brickmesh_select(binaries, shape, ws=None):
+    """Which 8^3 bricks of a lattice of `shape` cells touch a set cell of the occupancy grid (perf_brickmesh_select) -> (table int32
+    [Bx, By, Bz]: slot or -1, n_live: int64 [1] ON THE DEVICE)."""
+    n = _brick_shape('brickmesh_select', shape)
+    _brick_dev('brickmesh_select', binaries=binaries)
+    occ, res = _brick_occ('brickmesh_select', binaries)
+    ws = _brick_ws(n, 0, ws, occ.device)
+    table = torch.empty(tuple(v // 8 for v in n), dtype=torch.int32, device=occ.device)
+    n_live = torch.empty(1, dtype=torch.int64, device=occ.device)
+    _call('perf_brickmesh_select', _p(occ), res, *n, _p(table), _p(n_live), _p(ws), ws.numel() * 8, _stream())
+    return table, n_live
+
+
+def brickmesh_list(table, n_bricks):
+    """The ascending linear indices int32 [n_bricks] of the bricks a table holds (perf_brickmesh_list)."""
+    _brick_dev('brickmesh_list', table=table)
+    if table.dim() != 3:
+        raise _lib.PerfError(f'brickmesh_list: the table must be [Bx, By, Bz], got {tuple(table.shape)}')
+    ids = torch.empty(int(n_bricks), dtype=torch.int32, device=table.device)
+    _call('perf_brickmesh_list', _p(_brick_i32(table, 'table')), *(8 * int(s) for s in table.shape), _p(ids) if n_bricks else None, int(n_bricks), _stream())
+    return ids
+
+
+def brickmesh_corners(ids, first, m, shape, binaries):
+    """The stored corners of the slots first .. first + m - 1 (perf_brickmesh_corners) -> (x01 fp32 [m * 512, 3], sel uint8 [m * 512]:
+    strictly inside the box AND in a set occupancy cell, interior uint8 [m * 512]: strictly inside the box)."""
+    n = _brick_shape('brickmesh_corners', shape)
+    _brick_dev('brickmesh_corners', ids=ids, binaries=binaries)
+    occ, res = _brick_occ('brickmesh_corners', binaries)
+    m = int(m)
+    x01 = torch.empty(max(m, 0) * 512, 3, dtype=torch.float32, device=ids.device)
+    sel = torch.empty(max(m, 0) * 512, dtype=torch.uint8, device=ids.device)
+    interior = torch.empty_like(sel)
+    _call('perf_brickmesh_corners', _p(_brick_i32(ids, 'ids')) if ids.numel() else None, ids.numel(), int(first), m, *n, _p(occ), res, _p(x01) if m > 0 else None,
+          _p(sel) if m > 0 else None, _p(interior) if m > 0 else None, _stream())
+    return x01, sel, interior
+
+
+def _brick_set(who, values, ids, table, shape):
+    n = _brick_shape(who, shape)
+    _brick_dev(who, values=values, ids=ids, table=table)
+    m = int(ids.numel())
+    if values.numel() != m * 512 or tuple(table.shape) != tuple(v // 8 for v in n):
+        raise _lib.PerfError(f'{who}: values {tuple(values.shape)}, ids {tuple(ids.shape)} and table {tuple(table.shape)} do not describe bricks of a lattice of {n} cells')
+    return n, m
+
+
+def brickmesh_count(values, ids, table, shape, thr, fill, ws=None):
+    """Classify the cells of the live bricks (perf_brickmesh_count) -> (counts, ws): counts = int64 [3] ON THE DEVICE (vertices, triangles,
+    violations of the closure rule), ws = the int64 workspace brickmesh_write needs."""
+    n, m = _brick_set('brickmesh_count', values, ids, table, shape)
+    ws = _brick_ws(n, m, ws, table.device)
+    counts = torch.empty(3, dtype=torch.int64, device=table.device)
+    _call('perf_brickmesh_count', _p(_f32(values, 'values')) if m else None, _p(_brick_i32(ids, 'ids')) if m else None, _p(_brick_i32(table, 'table')), m, *n, float(thr),
+          float(fill), _p(ws), ws.numel() * 8, _p(counts), _stream())
+    return counts, ws
+
+
+def brickmesh_write(values, ids, table, shape, thr, fill, lo, hi, ws, n_vertices, n_faces):
+    """The vertices [n_vertices, 3] fp32, faces [n_faces, 3] int32 and cells [n_vertices] int64 (each vertex's linear cell of the virtual
+    lattice) of what brickmesh_count classified into ws (perf_brickmesh_write).  Counts below the counted totals are refused."""
+    n, m = _brick_set('brickmesh_write', values, ids, table, shape)
+    lo3, hi3 = [float(v) for v in lo], [float(v) for v in hi]
+    if len(lo3) != 3 or len(hi3) != 3:
+        raise _lib.PerfError('brickmesh_write: lo and hi hold three values each')
+    nv, nf = int(n_vertices), int(n_faces)
+    vertices = torch.empty(nv, 3, dtype=torch.float32, device=table.device)
+    faces = torch.empty(nf, 3, dtype=torch.int32, device=table.device)
+    cells = torch.empty(nv, dtype=torch.int64, device=table.device)
+    _call('perf_brickmesh_write', _p(_f32(values, 'values')) if m else None, _p(_brick_i32(ids, 'ids')) if m else None, _p(_brick_i32(table, 'table')), m, *n, float(thr),
+          float(fill), (ctypes.c_float * 3)(*lo3), (ctypes.c_float * 3)(*hi3), _p(ws), ws.numel() * 8, _p(vertices) if nv else None, nv, _p(faces) if nf else None, nf,
+          _p(cells) if nv else None, _stream())
+    return vertices, faces, cells
+
+
 def normal_composite(weights, grad, packed):
     """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
     R = packed.shape[0]

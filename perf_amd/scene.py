@@ -1575,6 +1575,12 @@ class NeRFScene:
         from .mesh import extract_mesh
         return extract_mesh(self, **kw)
 
+    def extract_mesh_sparse(self, **kw):
+        """The same mesh from only the lattice bricks that touch the occupancy shell, at resolutions up to 4096 (perf_amd/mesh.py:
+        extract_mesh_sparse's keywords) -> mesh.Mesh."""
+        from .mesh import extract_mesh_sparse
+        return extract_mesh_sparse(self, **kw)
+
 
 def psnr(pred, gt):
     """-10 log10(mean((pred-gt)^2))  (the reference never computes it)."""

@@ -1,6 +1,6 @@
 """Write the trained density as a triangle mesh (binary PLY): trains the synthetic room, or loads a checkpoint of NeRFScene.state_dict().
 
-  python tools/extract_mesh.py --out room.ply [--resolution 256] [--threshold T] [--no-occupancy] [--no-colors] [--no-normals]
+  python tools/extract_mesh.py --out room.ply [--resolution 256] [--threshold T] [--no-occupancy] [--no-colors] [--no-normals] [--sparse]
                                [--checkpoint scene.pt | --geo 3000 --app 1500] [--dtype fp16]
 
 Prints one JSON line: the counts, the threshold and the seconds of training and extraction."""
@@ -17,6 +17,7 @@ ap.add_argument('--out', required=True)
 ap.add_argument('--resolution', type=int, default=256)
 ap.add_argument('--threshold', type=float, default=None, help='default: ln 2 / render_step_size')
 ap.add_argument('--no-occupancy', action='store_true', help='keep the density where the occupancy grid is empty (the field is untrained there)')
+ap.add_argument('--sparse', action='store_true', help='evaluate and mesh only the lattice bricks that touch the occupancy shell (resolutions up to 4096, a multiple of 8)')
 ap.add_argument('--no-colors', action='store_true')
 ap.add_argument('--no-normals', action='store_true')
 ap.add_argument('--checkpoint', default=None, help='a torch.save of NeRFScene.state_dict()')
@@ -39,9 +40,14 @@ else:
     scene.train_one_episode(pool, args.geo, args.app)
 scene.set_eval()
 torch.cuda.synchronize(); t1 = time.perf_counter()
-mesh = scene.extract_mesh(resolution=args.resolution, threshold=args.threshold, use_occupancy=not args.no_occupancy, colors=not args.no_colors,
-                          normals=not args.no_normals)
+if args.sparse:
+    if args.no_occupancy:
+        ap.error('--sparse meshes the occupancy shell: it cannot go with --no-occupancy')
+    mesh = scene.extract_mesh_sparse(resolution=args.resolution, threshold=args.threshold, colors=not args.no_colors, normals=not args.no_normals)
+else:
+    mesh = scene.extract_mesh(resolution=args.resolution, threshold=args.threshold, use_occupancy=not args.no_occupancy, colors=not args.no_colors,
+                              normals=not args.no_normals)
 torch.cuda.synchronize(); t2 = time.perf_counter()
 write_ply(args.out, mesh)
-print(json.dumps({'out': args.out, 'vertices': len(mesh.vertices), 'faces': len(mesh.faces), 'resolution': args.resolution,
+print(json.dumps({'out': args.out, 'vertices': len(mesh.vertices), 'faces': len(mesh.faces), 'resolution': args.resolution, 'sparse': args.sparse,
                   'threshold': args.threshold, 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'bytes': os.path.getsize(args.out)}))

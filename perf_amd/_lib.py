@@ -17,6 +17,7 @@ PAIR_ABI_VERSION = 1     # PERF_PAIR_ABI_VERSION of include/perf_hip_pair.h (the
 JOINT_ABI_VERSION = 1    # PERF_JOINT_ABI_VERSION of include/perf_hip_joint.h (the joint predictor's alignment step)
 MESH_ABI_VERSION = 1     # PERF_MESH_ABI_VERSION of include/perf_hip_mesh.h (surface nets on a dense lattice)
 BRICKMESH_ABI_VERSION = 1    # PERF_BRICKMESH_ABI_VERSION of include/perf_hip_brickmesh.h (surface nets on the live bricks of a lattice)
+MESHCC_ABI_VERSION = 1       # PERF_MESHCC_ABI_VERSION of include/perf_hip_meshcc.h (connected components of a triangle mesh)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -203,6 +204,18 @@ _SIGS_BRICKMESH = {
                                      P, c_int64, P, P]),
 }
 
+# include/perf_hip_meshcc.h: connected components of a triangle mesh, versioned on its own (perf_meshcc_version)
+MESHCC_MAX_VERTICES = 1 << 30        # PERF_MESHCC_MAX_VERTICES
+MESHCC_MAX_FACES = 1 << 38           # PERF_MESHCC_MAX_FACES
+_SIGS_MESHCC = {
+    'perf_meshcc_version': (c_int, []),
+    'perf_meshcc_workspace_bytes': (c_int64, [c_int64, c_int64]),
+    'perf_meshcc_label': (c_int, [P, c_int64, c_int64, P, P, P, c_int64, P]),
+    'perf_meshcc_stats': (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, P]),
+    'perf_meshcc_filter_count': (c_int, [P, c_int64, P, c_int64, P, c_int64, P, c_int64, P, P]),
+    'perf_meshcc_filter_write': (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, c_int64, P, P, c_int64, P, c_int64, P]),
+}
+
 _lib = None
 
 
@@ -218,7 +231,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
@@ -245,6 +258,9 @@ def load():
                         'rebuild with `python -m perf_amd.build --force`')
     if lib.perf_brickmesh_version() != BRICKMESH_ABI_VERSION:
         raise PerfError(f'{LIB_PATH} has brick-mesh ABI version {lib.perf_brickmesh_version()}, this binding expects {BRICKMESH_ABI_VERSION}: '
+                        'rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_meshcc_version() != MESHCC_ABI_VERSION:
+        raise PerfError(f'{LIB_PATH} has mesh-component ABI version {lib.perf_meshcc_version()}, this binding expects {MESHCC_ABI_VERSION}: '
                         'rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):

@@ -172,6 +172,89 @@ def extract_mesh_sparse(scene, resolution=1024, threshold=None, colors=False, no
     return Mesh(mesh.vertices, mesh.faces, rgb, nrm)
 
 
+# ---- the pieces of a mesh: connected components, selection, compaction (include/perf_hip_meshcc.h) ---------------------------------------
+class Components(NamedTuple):
+    vertex_component: torch.Tensor               # [V] int32: the id of each vertex's component, ids ordered by smallest vertex index
+    faces: torch.Tensor                          # [C] int64: faces per component
+    vertices: torch.Tensor                       # [C] int32: vertices per component
+    signed_volume: Optional[torch.Tensor] = None     # [C] float64: > 0 for a closed surface with outward normals; None without positions
+
+
+def connected_components(mesh_or_faces, n_vertices=None, vertices=None) -> Components:
+    """The pieces of a mesh that share no vertex index, labelled on the device.  mesh_or_faces: a Mesh, or faces int32 [F, 3] with
+    n_vertices (and vertices fp32 [V, 3] for the signed volumes).  One host read: the component count with the flag of a face index
+    outside [0, V), which is refused."""
+    if isinstance(mesh_or_faces, Mesh):
+        faces, vertices = mesh_or_faces.faces, mesh_or_faces.vertices
+        n_vertices = int(vertices.shape[0])
+    else:
+        faces = mesh_or_faces
+        if n_vertices is None:
+            if vertices is None:
+                raise _lib.PerfError('connected_components: faces alone do not say how many vertices there are: pass n_vertices or vertices')
+            n_vertices = int(vertices.shape[0])
+    if not torch.is_tensor(faces) or not faces.is_cuda:
+        raise _lib.PerfError('connected_components: faces must be a CUDA tensor (there is no CPU path)')
+    faces = faces.contiguous()
+    if vertices is not None:
+        vertices = vertices.contiguous()
+    vertex_component, counts, _ = ops.meshcc_label(faces, n_vertices)
+    n_components, bad = (int(v) for v in counts.tolist())          # the one host synchronisation of a labelling
+    if bad >= 0:
+        raise _lib.PerfError(f'connected_components: face {bad} = {faces[bad].tolist()} has an index outside [0, {int(n_vertices)})')
+    per_faces, per_vertices, volume = ops.meshcc_stats(faces, vertex_component, n_components, vertices)
+    return Components(vertex_component, per_faces, per_vertices, volume)
+
+
+def select_components(components, min_faces=0, keep_largest=None, orientation=None) -> torch.Tensor:
+    """bool [C]: component c is kept iff faces[c] >= min_faces, and keep_largest is None or the rank of c by (more faces first, then
+    lower id) is below keep_largest, and orientation is None, or 'inward' and signed_volume[c] < 0, or 'outward' and > 0."""
+    if not components.faces.is_cuda:
+        raise _lib.PerfError('select_components: the components must be CUDA tensors (there is no CPU path)')
+    if orientation not in (None, 'inward', 'outward'):
+        raise _lib.PerfError(f"select_components: orientation is None, 'inward' or 'outward', got {orientation!r}")
+    faces = components.faces
+    keep = faces >= int(min_faces)
+    if keep_largest is not None:
+        if int(keep_largest) < 0:
+            raise _lib.PerfError(f'select_components: keep_largest {keep_largest} is negative')
+        order = torch.sort(faces, descending=True, stable=True).indices          # (stable: ties stay in ascending id)
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(order.numel(), dtype=order.dtype, device=order.device)
+        keep &= rank < int(keep_largest)
+    if orientation is not None:
+        if components.signed_volume is None:
+            raise _lib.PerfError('select_components: an orientation needs signed volumes: label the components with the vertices')
+        keep &= (components.signed_volume < 0) if orientation == 'inward' else (components.signed_volume > 0)
+    return keep
+
+
+def filter_mesh(mesh, components, keep):
+    """The mesh of the components keep [C] selects -> (Mesh, kept_vertex_index int32 [V']): kept vertices and faces in their old
+    relative order, faces re-indexed, colors and normals gathered.  One host read: the two kept counts."""
+    if not mesh.faces.is_cuda or not mesh.vertices.is_cuda:
+        raise _lib.PerfError('filter_mesh: the mesh must hold CUDA tensors (there is no CPU path)')
+    if keep.numel() != components.faces.numel():
+        raise _lib.PerfError(f'filter_mesh: keep holds {keep.numel()} entries, there are {components.faces.numel()} components')
+    faces, vertices = mesh.faces.contiguous(), mesh.vertices.contiguous()
+    counts, ws = ops.meshcc_filter_count(faces, components.vertex_component, keep)
+    n_vertices, n_faces = (int(v) for v in counts.tolist())          # the one host synchronisation of a filtering
+    new_vertices, new_faces, index = ops.meshcc_filter_write(faces, components.vertex_component, keep, ws, n_vertices, n_faces, vertices)
+    gather = index.long()
+    colors = mesh.colors[gather] if mesh.colors is not None else None
+    normals = mesh.normals[gather] if mesh.normals is not None else None
+    return Mesh(new_vertices, new_faces, colors, normals), index
+
+
+def clean_mesh(mesh, min_faces=0, keep_largest=None, orientation=None) -> Mesh:
+    """mesh without its floaters / without one of its two skins: the components select_components keeps.  A thresholded density is a
+    thin shell, so its iso-surface is the skin the cameras saw (orientation='inward' for a room seen from inside: normals point into
+    the volume the surface encloses, the signed volume is negative) AND the shell's back."""
+    components = connected_components(mesh)
+    keep = select_components(components, min_faces=min_faces, keep_largest=keep_largest, orientation=orientation)
+    return filter_mesh(mesh, components, keep)[0]
+
+
 def write_ply(path, mesh):
     """Binary little-endian PLY: x y z [nx ny nz] [red green blue as uchar] per vertex, a uchar-counted int list per face."""
     v = mesh.vertices.detach().cpu().numpy().astype('<f4')

@@ -886,6 +886,113 @@ def brickmesh_write(values, ids, table, shape, thr, fill, lo, hi, ws, n_vertices
     return vertices, faces, cells
 
 
+# ---- connected components of a triangle mesh (include/perf_hip_meshcc.h) ---------------------------------------------------------------
+def _cc_faces(who, faces, n_vertices):
+    if not faces.is_cuda:
+        raise _lib.PerfError(f'{who}: faces must be a CUDA tensor (there is no CPU path)')
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
+        raise _lib.PerfError(f'{who}: faces must be a contiguous int32 [F, 3] tensor, got {faces.dtype} {tuple(faces.shape)}')
+    n = int(n_vertices)
+    if n < 0 or n > _lib.MESHCC_MAX_VERTICES:
+        raise _lib.PerfError(f'{who}: {n} vertices are outside 0 .. 2^30')
+    return n, int(faces.shape[0])
+
+
+def _cc_ws(n_vertices, n_faces, ws, device):
+    nbytes = _lib.load().perf_meshcc_workspace_bytes(n_vertices, n_faces)
+    if nbytes < 0:
+        _lib.check(-1, 'perf_meshcc_workspace_bytes')
+    if ws is None or ws.numel() * 8 < nbytes or ws.device != device:
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+    return ws
+
+
+def _cc_labels(who, vertex_component, n, device):
+    if not vertex_component.is_cuda or vertex_component.device != device:
+        raise _lib.PerfError(f'{who}: vertex_component must be a CUDA tensor on the faces\' device')
+    if vertex_component.dtype != torch.int32 or tuple(vertex_component.shape) != (n,) or not vertex_component.is_contiguous():
+        raise _lib.PerfError(f'{who}: vertex_component must be a contiguous int32 [{n}] tensor, got {vertex_component.dtype} {tuple(vertex_component.shape)}')
+    return vertex_component
+
+
+def _cc_vertices(who, vertices, n, device):
+    if vertices is None:
+        return None
+    if not vertices.is_cuda or vertices.device != device:
+        raise _lib.PerfError(f'{who}: vertices must be a CUDA tensor on the faces\' device')
+    if tuple(vertices.shape) != (n, 3) or not vertices.is_contiguous():
+        raise _lib.PerfError(f'{who}: vertices must be a contiguous fp32 [{n}, 3] tensor, got {tuple(vertices.shape)}')
+    return _f32(vertices, 'vertices')
+
+
+def meshcc_label(faces, n_vertices, ws=None):
+    """Label the connected components of faces int32 [F, 3] over n_vertices vertices (perf_meshcc_label) -> (vertex_component int32 [V],
+    counts, ws): counts = int64 [2] ON THE DEVICE (C, the first face with an index outside [0, V) or -1)."""
+    n, f = _cc_faces('meshcc_label', faces, n_vertices)
+    ws = _cc_ws(n, f, ws, faces.device)
+    vertex_component = torch.empty(n, dtype=torch.int32, device=faces.device)
+    counts = torch.empty(2, dtype=torch.int64, device=faces.device)
+    _call('perf_meshcc_label', _p(faces) if f else None, f, n, _p(vertex_component) if n else None, _p(counts), _p(ws), ws.numel() * 8, _stream())
+    return vertex_component, counts, ws
+
+
+def meshcc_stats(faces, vertex_component, n_components, vertices=None):
+    """faces int64 [C], vertices int32 [C] and, with vertices fp32 [V, 3], signed volume float64 [C] (else None) of the components
+    (perf_meshcc_stats)."""
+    n = int(vertex_component.numel())
+    _, f = _cc_faces('meshcc_stats', faces, n)
+    _cc_labels('meshcc_stats', vertex_component, n, faces.device)
+    vertices = _cc_vertices('meshcc_stats', vertices, n, faces.device)
+    c = int(n_components)
+    faces_per = torch.empty(c, dtype=torch.int64, device=faces.device)
+    vertices_per = torch.empty(c, dtype=torch.int32, device=faces.device)
+    volume = torch.empty(c, dtype=torch.float64, device=faces.device) if vertices is not None else None
+    _call('perf_meshcc_stats', _p(faces) if f else None, f, _p(vertices) if vertices is not None and n else None, n, _p(vertex_component) if n else None, c,
+          _p(faces_per) if c else None, _p(vertices_per) if c else None, _p(volume) if volume is not None and c else None, _stream())
+    return faces_per, vertices_per, volume
+
+
+def _cc_keep(who, keep, device):
+    if not keep.is_cuda or keep.device != device:
+        raise _lib.PerfError(f'{who}: keep must be a CUDA tensor on the faces\' device')
+    if keep.dtype not in (torch.bool, torch.uint8) or keep.dim() != 1:
+        raise _lib.PerfError(f'{who}: keep must be bool or uint8 [C], got {keep.dtype} {tuple(keep.shape)}')
+    k = keep.contiguous()
+    return k.view(torch.uint8) if k.dtype == torch.bool else k
+
+
+def meshcc_filter_count(faces, vertex_component, keep, ws=None):
+    """Rank the vertices and faces of the components keep [C] selects (perf_meshcc_filter_count) -> (counts, ws): counts = int64 [2] ON
+    THE DEVICE (kept vertices, kept faces), ws = the workspace meshcc_filter_write needs."""
+    n = int(vertex_component.numel())
+    _, f = _cc_faces('meshcc_filter_count', faces, n)
+    _cc_labels('meshcc_filter_count', vertex_component, n, faces.device)
+    k = _cc_keep('meshcc_filter_count', keep, faces.device)
+    ws = _cc_ws(n, f, ws, faces.device)
+    counts = torch.empty(2, dtype=torch.int64, device=faces.device)
+    _call('perf_meshcc_filter_count', _p(faces) if f else None, f, _p(vertex_component) if n else None, n, _p(k) if k.numel() else None, k.numel(), _p(ws),
+          ws.numel() * 8, _p(counts), _stream())
+    return counts, ws
+
+
+def meshcc_filter_write(faces, vertex_component, keep, ws, n_vertices_kept, n_faces_kept, vertices=None):
+    """The kept faces int32 [F', 3] re-indexed, kept_vertex_index int32 [V'] and, with vertices, the kept vertices fp32 [V', 3] (else
+    None) of what meshcc_filter_count ranked into ws (perf_meshcc_filter_write).  Counts below the counted totals are refused."""
+    n = int(vertex_component.numel())
+    _, f = _cc_faces('meshcc_filter_write', faces, n)
+    _cc_labels('meshcc_filter_write', vertex_component, n, faces.device)
+    k = _cc_keep('meshcc_filter_write', keep, faces.device)
+    vertices = _cc_vertices('meshcc_filter_write', vertices, n, faces.device)
+    nv, nf = int(n_vertices_kept), int(n_faces_kept)
+    vertices_out = torch.empty(nv, 3, dtype=torch.float32, device=faces.device) if vertices is not None else None
+    index = torch.empty(nv, dtype=torch.int32, device=faces.device)
+    faces_out = torch.empty(nf, 3, dtype=torch.int32, device=faces.device)
+    _call('perf_meshcc_filter_write', _p(faces) if f else None, f, _p(vertex_component) if n else None, n, _p(k) if k.numel() else None, k.numel(),
+          _p(vertices) if vertices is not None and n else None, _p(ws), ws.numel() * 8, _p(vertices_out) if vertices_out is not None and nv else None,
+          _p(index) if nv else None, nv, _p(faces_out) if nf else None, nf, _stream())
+    return vertices_out, faces_out, index
+
+
 def normal_composite(weights, grad, packed):
     """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
     R = packed.shape[0]

@@ -1581,6 +1581,11 @@ class NeRFScene:
         from .mesh import extract_mesh_sparse
         return extract_mesh_sparse(self, **kw)
 
+    def clean_mesh(self, mesh, **kw):
+        """mesh without its floaters or without one of its two skins (perf_amd/mesh.py: clean_mesh's keywords) -> mesh.Mesh."""
+        from .mesh import clean_mesh
+        return clean_mesh(mesh, **kw)
+
 
 def psnr(pred, gt):
     """-10 log10(mean((pred-gt)^2))  (the reference never computes it)."""

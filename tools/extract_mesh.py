@@ -1,6 +1,7 @@
 """Write the trained density as a triangle mesh (binary PLY): trains the synthetic room, or loads a checkpoint of NeRFScene.state_dict().
 
   python tools/extract_mesh.py --out room.ply [--resolution 256] [--threshold T] [--no-occupancy] [--no-colors] [--no-normals] [--sparse]
+                               [--min-component-faces N] [--keep-largest K] [--orientation inward|outward]
                                [--checkpoint scene.pt | --geo 3000 --app 1500] [--dtype fp16]
 
 Prints one JSON line: the counts, the threshold and the seconds of training and extraction."""
@@ -20,6 +21,10 @@ ap.add_argument('--no-occupancy', action='store_true', help='keep the density wh
 ap.add_argument('--sparse', action='store_true', help='evaluate and mesh only the lattice bricks that touch the occupancy shell (resolutions up to 4096, a multiple of 8)')
 ap.add_argument('--no-colors', action='store_true')
 ap.add_argument('--no-normals', action='store_true')
+ap.add_argument('--min-component-faces', type=int, default=0, help='drop the connected components with fewer faces (floaters)')
+ap.add_argument('--keep-largest', type=int, default=None, help='keep only this many components, the ones with the most faces')
+ap.add_argument('--orientation', choices=['inward', 'outward'], default=None,
+                help='keep the closed components whose normals point into (inward: a room seen from inside) or out of the volume they enclose')
 ap.add_argument('--checkpoint', default=None, help='a torch.save of NeRFScene.state_dict()')
 ap.add_argument('--geo', type=int, default=3000)
 ap.add_argument('--app', type=int, default=1500)
@@ -48,6 +53,10 @@ else:
     mesh = scene.extract_mesh(resolution=args.resolution, threshold=args.threshold, use_occupancy=not args.no_occupancy, colors=not args.no_colors,
                               normals=not args.no_normals)
 torch.cuda.synchronize(); t2 = time.perf_counter()
+extracted = (len(mesh.vertices), len(mesh.faces))
+if args.min_component_faces > 0 or args.keep_largest is not None or args.orientation is not None:          # after either extraction path
+    mesh = scene.clean_mesh(mesh, min_faces=args.min_component_faces, keep_largest=args.keep_largest, orientation=args.orientation)
+torch.cuda.synchronize(); t3 = time.perf_counter()
 write_ply(args.out, mesh)
 print(json.dumps({'out': args.out, 'vertices': len(mesh.vertices), 'faces': len(mesh.faces), 'resolution': args.resolution, 'sparse': args.sparse,
-                  'threshold': args.threshold, 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'bytes': os.path.getsize(args.out)}))
+                  'threshold': args.threshold, 'extracted_vertices': extracted[0], 'extracted_faces': extracted[1], 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'clean_s': t3 - t2, 'bytes': os.path.getsize(args.out)}))

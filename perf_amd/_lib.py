@@ -18,6 +18,7 @@ JOINT_ABI_VERSION = 1    # PERF_JOINT_ABI_VERSION of include/perf_hip_joint.h (t
 MESH_ABI_VERSION = 1     # PERF_MESH_ABI_VERSION of include/perf_hip_mesh.h (surface nets on a dense lattice)
 BRICKMESH_ABI_VERSION = 1    # PERF_BRICKMESH_ABI_VERSION of include/perf_hip_brickmesh.h (surface nets on the live bricks of a lattice)
 MESHCC_ABI_VERSION = 1       # PERF_MESHCC_ABI_VERSION of include/perf_hip_meshcc.h (connected components of a triangle mesh)
+MESHVIS_ABI_VERSION = 1      # PERF_MESHVIS_ABI_VERSION of include/perf_hip_meshvis.h (cull the mesh faces no registered panorama saw)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -216,6 +217,21 @@ _SIGS_MESHCC = {
     'perf_meshcc_filter_write': (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, c_int64, P, P, c_int64, P, c_int64, P]),
 }
 
+# include/perf_hip_meshvis.h: cull the faces of a mesh no registered panorama saw, versioned on its own (perf_meshvis_version)
+MESHVIS_MAX_VIEWS = 64               # PERF_MESHVIS_MAX_VIEWS
+MESHVIS_MAX_VERTICES = 1 << 30       # PERF_MESHVIS_MAX_VERTICES
+MESHVIS_MAX_FACES = 1 << 38          # PERF_MESHVIS_MAX_FACES
+MESHVIS_VIEW_BYTES = 64              # sizeof(perf_meshvis_view): rt [9], t [3] fp32, height, width int32, the map's device pointer
+_SIGS_MESHVIS = {
+    'perf_meshvis_version': (c_int, []),
+    'perf_meshvis_sizeof_view': (c_int64, []),
+    'perf_meshvis_workspace_bytes': (c_int64, [c_int64, c_int64]),
+    'perf_meshvis_vertex_bits': (c_int, [P, c_int64, P, POINTER(c_int32), c_int32, c_float, c_float, P, P, P]),
+    'perf_meshvis_face_keep': (c_int, [P, c_int64, P, c_int64, P, P, P, c_int32, c_int32, c_int32, c_int32, P, P, P]),
+    'perf_meshvis_filter_count': (c_int, [P, c_int64, c_int64, P, P, c_int64, P, P]),
+    'perf_meshvis_filter_write': (c_int, [P, c_int64, c_int64, P, P, P, c_int64, P, P, c_int64, P, c_int64, P]),
+}
+
 _lib = None
 
 
@@ -231,7 +247,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()) + list(_SIGS_MESHVIS.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
@@ -262,6 +278,9 @@ def load():
     if lib.perf_meshcc_version() != MESHCC_ABI_VERSION:
         raise PerfError(f'{LIB_PATH} has mesh-component ABI version {lib.perf_meshcc_version()}, this binding expects {MESHCC_ABI_VERSION}: '
                         'rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_meshvis_version() != MESHVIS_ABI_VERSION or lib.perf_meshvis_sizeof_view() != MESHVIS_VIEW_BYTES:
+        raise PerfError(f'{LIB_PATH} has visibility-cull ABI version {lib.perf_meshvis_version()} and a view of {lib.perf_meshvis_sizeof_view()} bytes, this binding '
+                        f'expects {MESHVIS_ABI_VERSION} and {MESHVIS_VIEW_BYTES}: rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):
         raise PerfError('descriptor layout mismatch between perf_amd/_lib.py and include/perf_hip.h')

@@ -255,6 +255,128 @@ def clean_mesh(mesh, min_faces=0, keep_largest=None, orientation=None) -> Mesh:
     return filter_mesh(mesh, components, keep)[0]
 
 
+# ---- the faces no registered panorama saw (include/perf_hip_meshvis.h) -----------------------------------------------------------------
+class Visibility(NamedTuple):
+    visible: torch.Tensor                        # [V] int64: bit k set iff view k saw the vertex (dist < stored + tol)
+    free: torch.Tensor                           # [V] int64: bit k set iff the vertex lies in view k's observed free space (dist < stored - free_tol)
+    n_views: int
+
+
+class _Views(NamedTuple):
+    table: torch.Tensor                          # [K, 16] int32: the device array of perf_meshvis_view
+    centres: torch.Tensor                        # [K, 3] fp32
+    sizes: list                                  # K (height, width)
+    maps: list                                   # the masked distance maps the table points into
+
+
+def _views(who, views) -> _Views:
+    """views: a SupInfoPool, or a list of dicts with 'pose' [4, 4] or [3, 4], 'distance_map' [H, W, 1] or [H, W] and optionally 'mask' of
+    the map's shape (what SupInfoPool.sup_infos holds).  The map a view is tested against is distance_map * mask, as the reprojection
+    tests of perf_amd/visibility.py form it."""
+    if isinstance(views, _Views):
+        return views
+    infos = views.sup_infos if hasattr(views, 'sup_infos') else views
+    poses, maps = [], []
+    for info in infos:
+        dmap = info['distance_map']
+        if not torch.is_tensor(dmap) or not dmap.is_cuda:
+            raise _lib.PerfError(f'{who}: a view\'s distance_map must be a CUDA tensor (there is no CPU path)')
+        if info.get('mask') is not None:
+            dmap = dmap * info['mask'].reshape(dmap.shape).float()
+        if dmap.dim() == 3 and dmap.shape[2] == 1:
+            dmap = dmap[..., 0]
+        if dmap.dim() != 2:
+            raise _lib.PerfError(f'{who}: a view\'s distance_map is [H, W, 1] or [H, W], got {tuple(info["distance_map"].shape)}')
+        maps.append(dmap.float().contiguous())
+        poses.append(info['pose'])
+    return _Views(*ops.meshvis_views(poses, maps))
+
+
+def _tolerances(tol, free_tol):
+    tol = float(tol)
+    return tol, tol if free_tol is None else float(free_tol)
+
+
+def vertex_visibility(vertices, views, tol=1 / 256, free_tol=None) -> Visibility:
+    """Which registered panoramas saw each vertex, all of them in ONE launch: bit k of `visible` is the depth test of
+    NeRFScene.get_pano_visibility_mask against view k (the distance of the vertex from the view's centre < the distance the view stored
+    along that direction + tol), bit k of `free` the stricter dist < stored - free_tol (free_tol None: tol): the vertex floats in front
+    of what the view stored.  vertices: CUDA fp32 [V, 3]; at most 64 views."""
+    if not torch.is_tensor(vertices) or not vertices.is_cuda:
+        raise _lib.PerfError('vertex_visibility: vertices must be a CUDA tensor (there is no CPU path)')
+    tol, free_tol = _tolerances(tol, free_tol)
+    v = _views('vertex_visibility', views)
+    visible, free = ops.meshvis_vertex_bits(vertices.contiguous(), v.table, v.sizes, tol, free_tol)
+    return Visibility(visible, free, len(v.sizes))
+
+
+def _check_mesh(who, mesh):
+    if not torch.is_tensor(mesh.faces) or not torch.is_tensor(mesh.vertices) or not mesh.faces.is_cuda or not mesh.vertices.is_cuda:
+        raise _lib.PerfError(f'{who}: the mesh must hold CUDA tensors (there is no CPU path)')
+
+
+def _raise_bad_face(who, faces, bad, n_vertices):
+    raise _lib.PerfError(f'{who}: face {bad} = {faces[bad].tolist()} has an index outside [0, {int(n_vertices)})')
+
+
+def _face_keep(who, mesh, visibility, v, facing, min_views, carve, flag=None):
+    if int(min_views) < 1:
+        raise _lib.PerfError(f'{who}: min_views {min_views} is below 1')
+    if visibility.n_views != len(v.sizes):
+        raise _lib.PerfError(f'{who}: the visibility holds bits of {visibility.n_views} views, {len(v.sizes)} views are given')
+    return ops.meshvis_face_keep(mesh.faces.contiguous(), mesh.vertices.contiguous(), visibility.visible, visibility.free, v.centres, facing, min_views, carve, flag)
+
+
+def visible_faces(mesh, visibility, views, facing=True, min_views=1, carve=False) -> torch.Tensor:
+    """uint8 [F]: a face is kept iff at least min_views views saw all three of its vertices and (facing) the face points at the view --
+    surface-nets normals point from the dense side to the empty side, so the skin a camera saw points at it and the back of the density
+    shell does not -- and (carve) none of its vertices lies in a view's observed free space.  One host read: the flag of a face index
+    outside [0, V), which is refused."""
+    _check_mesh('visible_faces', mesh)
+    keep, flag = _face_keep('visible_faces', mesh, visibility, _views('visible_faces', views), facing, min_views, carve)
+    bad = int(flag.item())
+    if bad >= 0:
+        _raise_bad_face('visible_faces', mesh.faces, bad, mesh.vertices.shape[0])
+    return keep
+
+
+def _filter_faces(mesh, face_keep, counts, who):
+    faces, vertices = mesh.faces.contiguous(), mesh.vertices.contiguous()
+    _, ws = ops.meshvis_filter_count(faces, vertices.shape[0], face_keep, counts=counts[:2])
+    n_vertices, n_faces, bad = (int(c) for c in counts.tolist())          # the one host synchronisation
+    if bad >= 0:
+        _raise_bad_face(who, faces, bad, vertices.shape[0])
+    new_vertices, new_faces, index = ops.meshvis_filter_write(faces, vertices.shape[0], face_keep, ws, n_vertices, n_faces, vertices)
+    gather = index.long()
+    colors = mesh.colors[gather] if mesh.colors is not None else None
+    normals = mesh.normals[gather] if mesh.normals is not None else None
+    return Mesh(new_vertices, new_faces, colors, normals), index
+
+
+def filter_faces(mesh, face_keep):
+    """The mesh of the faces face_keep (bool or uint8 [F]) selects -> (Mesh, kept_vertex_index int32 [V']): a vertex is kept iff a kept face
+    names it; kept vertices and faces keep their relative order, faces are re-indexed, colors and normals gathered.  A face with an index
+    outside [0, V) is dropped.  One host read: the two kept counts."""
+    _check_mesh('filter_faces', mesh)
+    if not torch.is_tensor(face_keep) or not face_keep.is_cuda:
+        raise _lib.PerfError('filter_faces: face_keep must be a CUDA tensor (there is no CPU path)')
+    counts = torch.full((3,), -1, dtype=torch.int64, device=mesh.faces.device)
+    return _filter_faces(mesh, face_keep, counts, 'filter_faces')
+
+
+def cull_unseen(mesh, views, tol=1 / 256, free_tol=None, facing=True, min_views=1, carve=False) -> Mesh:
+    """mesh without the faces no registered panorama saw: vertex_visibility -> visible_faces -> filter_faces with ONE host
+    synchronisation.  It separates the skin the cameras saw from the back of the density shell where the two are ONE connected component
+    (clean_mesh(orientation='inward') keeps nothing of it).  There is no occlusion test against the mesh itself, no colours are taken from
+    the panoramas, and more than 64 views are refused."""
+    _check_mesh('cull_unseen', mesh)
+    v = _views('cull_unseen', views)
+    visibility = vertex_visibility(mesh.vertices, v, tol, free_tol)
+    counts = torch.empty(3, dtype=torch.int64, device=mesh.faces.device)
+    keep, _ = _face_keep('cull_unseen', mesh, visibility, v, facing, min_views, carve, counts[2:])
+    return _filter_faces(mesh, keep, counts, 'cull_unseen')[0]
+
+
 def write_ply(path, mesh):
     """Binary little-endian PLY: x y z [nx ny nz] [red green blue as uchar] per vertex, a uchar-counted int list per face."""
     v = mesh.vertices.detach().cpu().numpy().astype('<f4')

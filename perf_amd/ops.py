@@ -993,6 +993,129 @@ def meshcc_filter_write(faces, vertex_component, keep, ws, n_vertices_kept, n_fa
     return vertices_out, faces_out, index
 
 
+# ---- cull the faces no registered panorama saw (include/perf_hip_meshvis.h) ------------------------------------------------------------
+def _vis_ws(n_vertices, n_faces, ws, device):
+    nbytes = _lib.load().perf_meshvis_workspace_bytes(n_vertices, n_faces)
+    if nbytes < 0:
+        _lib.check(-1, 'perf_meshvis_workspace_bytes')
+    if ws is None or ws.numel() * 8 < nbytes or ws.device != device:
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+    return ws
+
+
+def _vis_bits(who, name, bits, n, device):
+    if not bits.is_cuda or bits.device != device:
+        raise _lib.PerfError(f'{who}: {name} must be a CUDA tensor on the mesh\'s device')
+    if bits.dtype != torch.int64 or tuple(bits.shape) != (n,) or not bits.is_contiguous():
+        raise _lib.PerfError(f'{who}: {name} must be a contiguous int64 [{n}] tensor, got {bits.dtype} {tuple(bits.shape)}')
+    return bits
+
+
+def meshvis_views(poses, maps):
+    """The device array of perf_meshvis_view of K panoramas -> (views int32 [K, 16] on the device, centres fp32 [K, 3], sizes: the host
+    (height, width) pairs, maps: the tensors the descriptors point into, to be kept alive with them).  poses: K [4, 4] or [3, 4]
+    camera-to-world matrices, on any device (they are not read back); maps: K CUDA fp32 [H, W] masked distance maps, any sizes."""
+    if len(poses) != len(maps):
+        raise _lib.PerfError(f'meshvis_views: {len(poses)} poses and {len(maps)} maps')
+    k = len(maps)
+    if k > _lib.MESHVIS_MAX_VIEWS:
+        raise _lib.PerfError(f'meshvis_views: {k} views are more than {_lib.MESHVIS_MAX_VIEWS} (a vertex has one bit per view in a 64-bit word)')
+    for m in maps:
+        if not torch.is_tensor(m) or not m.is_cuda:
+            raise _lib.PerfError('meshvis_views: the distance maps must be CUDA tensors (there is no CPU path)')
+        if m.dim() != 2 or m.shape[0] < 1 or m.shape[1] < 1 or m.shape[0] >= 1 << 31 or m.shape[1] >= 1 << 31:
+            raise _lib.PerfError(f'meshvis_views: a distance map is [H, W] with both at least 1, got {tuple(m.shape)}')
+    dev = maps[0].device if k else torch.device('cuda')
+    maps = [_f32(m, 'distance_map') for m in maps]
+    sizes = [(int(m.shape[0]), int(m.shape[1])) for m in maps]
+    if k == 0:
+        return torch.zeros(0, 16, dtype=torch.int32, device=dev), torch.zeros(0, 3, dtype=torch.float32, device=dev), sizes, maps
+    pose = torch.stack([torch.as_tensor(p, dtype=torch.float32).to(dev)[:3, :4] for p in poses])            # [K, 3, 4]
+    rt = pose[:, :, :3].transpose(1, 2).reshape(k, 9)
+    centres = pose[:, :, 3].contiguous()
+    tail = []
+    for (h, w), m in zip(sizes, maps):
+        ptr = m.data_ptr()
+        tail.append([h, w] + [v - (1 << 32) if v >= 1 << 31 else v for v in (ptr & 0xffffffff, ptr >> 32)])          # (the words of the pointer, low first)
+    tail = torch.tensor(tail, dtype=torch.int32).to(dev)
+    views = torch.cat([rt.contiguous().view(torch.int32), centres.view(torch.int32), tail], dim=1).contiguous()
+    return views, centres, sizes, maps
+
+
+def meshvis_vertex_bits(vertices, views, sizes, tol, free_tol):
+    """visible_bits, free_bits int64 [V] of vertices fp32 [V, 3] against the views of meshvis_views: ONE launch for all of them
+    (perf_meshvis_vertex_bits)."""
+    if not vertices.is_cuda:
+        raise _lib.PerfError('meshvis_vertex_bits: vertices must be a CUDA tensor (there is no CPU path)')
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
+        raise _lib.PerfError(f'meshvis_vertex_bits: vertices must be a contiguous fp32 [V, 3] tensor, got {tuple(vertices.shape)}')
+    n, k = int(vertices.shape[0]), len(sizes)
+    if tuple(views.shape) != (k, 16) or views.dtype != torch.int32 or (k and views.device != vertices.device) or not views.is_contiguous():
+        raise _lib.PerfError(f'meshvis_vertex_bits: views must be the contiguous int32 [{k}, 16] tensor of meshvis_views on the vertices\' device')
+    visible = torch.empty(n, dtype=torch.int64, device=vertices.device)
+    free = torch.empty(n, dtype=torch.int64, device=vertices.device)
+    flat = (ctypes.c_int32 * (2 * k))(*[v for hw in sizes for v in hw]) if k else None
+    _call('perf_meshvis_vertex_bits', _p(_f32(vertices, 'vertices')) if n else None, n, _p(views) if k else None, flat, k, float(tol), float(free_tol),
+          _p(visible) if n else None, _p(free) if n else None, _stream())
+    return visible, free
+
+
+def meshvis_face_keep(faces, vertices, visible_bits, free_bits, centres, facing=True, min_views=1, carve=False, flag=None):
+    """face_keep uint8 [F] by the face rule of include/perf_hip_meshvis.h (perf_meshvis_face_keep) -> (face_keep, flag): flag = int64 [1]
+    ON THE DEVICE, the smallest index of a face with an index outside [0, V) or -1 (an int64 [1] view to write it into may be passed)."""
+    n = int(vertices.shape[0])
+    _, f = _cc_faces('meshvis_face_keep', faces, n)
+    vertices = _cc_vertices('meshvis_face_keep', vertices, n, faces.device)
+    _vis_bits('meshvis_face_keep', 'visible_bits', visible_bits, n, faces.device)
+    _vis_bits('meshvis_face_keep', 'free_bits', free_bits, n, faces.device)
+    k = int(centres.shape[0])
+    if tuple(centres.shape) != (k, 3) or not centres.is_contiguous() or (k and not centres.is_cuda):
+        raise _lib.PerfError(f'meshvis_face_keep: centres must be a contiguous CUDA fp32 [K, 3] tensor, got {tuple(centres.shape)}')
+    keep = torch.empty(f, dtype=torch.uint8, device=faces.device)
+    if flag is None:
+        flag = torch.empty(1, dtype=torch.int64, device=faces.device)
+    _call('perf_meshvis_face_keep', _p(faces) if f else None, f, _p(vertices) if n else None, n, _p(visible_bits) if n else None, _p(free_bits) if n else None,
+          _p(_f32(centres, 'centres')) if k else None, k, int(bool(facing)), int(min_views), int(bool(carve)), _p(keep) if f else None, _p(flag), _stream())
+    return keep, flag
+
+
+def _vis_keep(who, face_keep, f, device):
+    if not face_keep.is_cuda or face_keep.device != device:
+        raise _lib.PerfError(f'{who}: face_keep must be a CUDA tensor on the faces\' device')
+    if face_keep.dtype not in (torch.bool, torch.uint8) or tuple(face_keep.shape) != (f,):
+        raise _lib.PerfError(f'{who}: face_keep must be bool or uint8 [{f}], got {face_keep.dtype} {tuple(face_keep.shape)}')
+    k = face_keep.contiguous()
+    return k.view(torch.uint8) if k.dtype == torch.bool else k
+
+
+def meshvis_filter_count(faces, n_vertices, face_keep, ws=None, counts=None):
+    """Rank the faces face_keep [F] selects and the vertices they name (perf_meshvis_filter_count) -> (counts, ws): counts = int64 [2] ON
+    THE DEVICE (kept vertices, kept faces; an int64 [2] view to write them into may be passed), ws = the workspace meshvis_filter_write
+    needs."""
+    n, f = _cc_faces('meshvis_filter_count', faces, n_vertices)
+    k = _vis_keep('meshvis_filter_count', face_keep, f, faces.device)
+    ws = _vis_ws(n, f, ws, faces.device)
+    if counts is None:
+        counts = torch.empty(2, dtype=torch.int64, device=faces.device)
+    _call('perf_meshvis_filter_count', _p(faces) if f else None, f, n, _p(k) if f else None, _p(ws), ws.numel() * 8, _p(counts), _stream())
+    return counts, ws
+
+
+def meshvis_filter_write(faces, n_vertices, face_keep, ws, n_vertices_kept, n_faces_kept, vertices=None):
+    """The kept faces int32 [F', 3] re-indexed, kept_vertex_index int32 [V'] and, with vertices, the kept vertices fp32 [V', 3] (else
+    None) of what meshvis_filter_count ranked into ws (perf_meshvis_filter_write).  Counts below the counted totals are refused."""
+    n, f = _cc_faces('meshvis_filter_write', faces, n_vertices)
+    k = _vis_keep('meshvis_filter_write', face_keep, f, faces.device)
+    vertices = _cc_vertices('meshvis_filter_write', vertices, n, faces.device)
+    nv, nf = int(n_vertices_kept), int(n_faces_kept)
+    vertices_out = torch.empty(nv, 3, dtype=torch.float32, device=faces.device) if vertices is not None else None
+    index = torch.empty(nv, dtype=torch.int32, device=faces.device)
+    faces_out = torch.empty(nf, 3, dtype=torch.int32, device=faces.device)
+    _call('perf_meshvis_filter_write', _p(faces) if f else None, f, n, _p(k) if f else None, _p(vertices) if vertices is not None and n else None, _p(ws),
+          ws.numel() * 8, _p(vertices_out) if vertices_out is not None and nv else None, _p(index) if nv else None, nv, _p(faces_out) if nf else None, nf, _stream())
+    return vertices_out, faces_out, index
+
+
 def normal_composite(weights, grad, packed):
     """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
     R = packed.shape[0]

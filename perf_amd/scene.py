@@ -1586,6 +1586,11 @@ class NeRFScene:
         from .mesh import clean_mesh
         return clean_mesh(mesh, **kw)
 
+    def cull_unseen_mesh(self, mesh, sup_pool, **kw):
+        """mesh without the faces none of sup_pool's registered panoramas saw (perf_amd/mesh.py: cull_unseen's keywords) -> mesh.Mesh."""
+        from .mesh import cull_unseen
+        return cull_unseen(mesh, sup_pool, **kw)
+
 
 def psnr(pred, gt):
     """-10 log10(mean((pred-gt)^2))  (the reference never computes it)."""

@@ -1,6 +1,7 @@
 """Write the trained density as a triangle mesh (binary PLY): trains the synthetic room, or loads a checkpoint of NeRFScene.state_dict().
 
   python tools/extract_mesh.py --out room.ply [--resolution 256] [--threshold T] [--no-occupancy] [--no-colors] [--no-normals] [--sparse]
+                               [--seen-by-panoramas [--visibility-tol T] [--carve] [--sup-pool pool.pt]]
                                [--min-component-faces N] [--keep-largest K] [--orientation inward|outward]
                                [--checkpoint scene.pt | --geo 3000 --app 1500] [--dtype fp16]
 
@@ -25,6 +26,12 @@ ap.add_argument('--min-component-faces', type=int, default=0, help='drop the con
 ap.add_argument('--keep-largest', type=int, default=None, help='keep only this many components, the ones with the most faces')
 ap.add_argument('--orientation', choices=['inward', 'outward'], default=None,
                 help='keep the closed components whose normals point into (inward: a room seen from inside) or out of the volume they enclose')
+ap.add_argument('--seen-by-panoramas', action='store_true',
+                help='drop the faces no registered panorama saw (depth test per vertex, facing test per face), before the component cleaning')
+ap.add_argument('--visibility-tol', type=float, default=1 / 256, help='the band of the depth test of --seen-by-panoramas, in scene units')
+ap.add_argument('--carve', action='store_true', help='with --seen-by-panoramas: also drop the faces with a vertex in observed free space, in front of a stored surface by more than '
+                                                       '--visibility-tol (a skin that sits further inside the room than that is carved with the floaters: widen the band)')
+ap.add_argument('--sup-pool', default=None, help='with --checkpoint and --seen-by-panoramas: a torch.save of SupInfoPool.state_dict()')
 ap.add_argument('--checkpoint', default=None, help='a torch.save of NeRFScene.state_dict()')
 ap.add_argument('--geo', type=int, default=3000)
 ap.add_argument('--app', type=int, default=1500)
@@ -35,12 +42,19 @@ args = ap.parse_args()
 torch.manual_seed(0); np.random.seed(0)
 scene = NeRFScene(dtype=args.dtype)
 t0 = time.perf_counter()
+views = None          # --seen-by-panoramas: the registered panoramas the mesh is tested against
+if args.seen_by_panoramas and args.checkpoint and not args.sup_pool:
+    ap.error('--seen-by-panoramas with --checkpoint needs the panoramas: --sup-pool FILE, a torch.save of SupInfoPool.state_dict()')
 if args.checkpoint:
     scene.load_state_dict(torch.load(args.checkpoint, map_location='cuda'))
+    if args.seen_by_panoramas:
+        views = SupInfoPool(); views.load_state_dict(torch.load(args.sup_pool, map_location='cuda'))
 else:
     rays = gen_pano_rays(torch.eye(4), 256, 512)
     dist, rgb = synthetic.room(rays.d)
     pool = SupInfoPool(); pool.register_rays(rays.o, rays.d, rgb, dist)
+    if args.seen_by_panoramas:          # (register_rays leaves no sup_infos: the view is the pose and the distance map the scene trains on)
+        views = [{'pose': torch.eye(4), 'distance_map': dist.reshape(256, 512).float().to('cuda')}]
     scene.train_conf.pixel_loss_batch_size = args.batch
     scene.train_one_episode(pool, args.geo, args.app)
 scene.set_eval()
@@ -54,9 +68,12 @@ else:
                               normals=not args.no_normals)
 torch.cuda.synchronize(); t2 = time.perf_counter()
 extracted = (len(mesh.vertices), len(mesh.faces))
+if args.seen_by_panoramas:          # first the faces no panorama saw, then the components of what is left
+    mesh = scene.cull_unseen_mesh(mesh, views, tol=args.visibility_tol, carve=args.carve)
+seen = {'seen_vertices': len(mesh.vertices), 'seen_faces': len(mesh.faces)} if args.seen_by_panoramas else {}
 if args.min_component_faces > 0 or args.keep_largest is not None or args.orientation is not None:          # after either extraction path
     mesh = scene.clean_mesh(mesh, min_faces=args.min_component_faces, keep_largest=args.keep_largest, orientation=args.orientation)
 torch.cuda.synchronize(); t3 = time.perf_counter()
 write_ply(args.out, mesh)
 print(json.dumps({'out': args.out, 'vertices': len(mesh.vertices), 'faces': len(mesh.faces), 'resolution': args.resolution, 'sparse': args.sparse,
-                  'threshold': args.threshold, 'extracted_vertices': extracted[0], 'extracted_faces': extracted[1], 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'clean_s': t3 - t2, 'bytes': os.path.getsize(args.out)}))
+                  'threshold': args.threshold, 'extracted_vertices': extracted[0], 'extracted_faces': extracted[1], **seen, 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'clean_s': t3 - t2, 'bytes': os.path.getsize(args.out)}))

@@ -38,7 +38,7 @@ struct TileParams {
     int32_t replicas_of[PERF_MAX_LEVELS];  // replicas per tile
     int64_t ws_off[PERF_MAX_LEVELS];       // float2 offset of the level's replica slabs in the workspace
     int32_t accumulate;
-    int32_t code_slot[PERF_MAX_LEVELS];    // >=0: the level's tile codes are codes[slot][n_pad] (see tile_codes_kernel)
+    int32_t code_slot[PERF_MAX_LEVELS];    // >=0: the level's tile codes are codes[slot][n_pad] (see tile_codes4_kernel)
     int64_t n_pad;
     // XCD-aware placement: workgroup b runs work[b] = level << 16 | tile << 8 | replica (0xffffffff: idle).  The
     // dispatcher deals workgroups round-robin over the 8 XCDs, so b % 8 is the XCD: the owners of one level are put on
@@ -222,7 +222,7 @@ __device__ __forceinline__ void apply_pairs(const BwdCtx& cx, float* lds_tile, c
 
 // Dense-level counterpart (interleaved 32-entry chunks): the two x-corners of a (y,z) combination are tested
 // separately -- they part at a chunk boundary -- and a combination that would wrap past the end of the level
-// (position far outside the unit cube; such a level takes the generic owners, see tile_codes_kernel) is skipped.
+// (position far outside the unit cube; such a level takes the generic owners, see tile_codes4_kernel) is skipped.
 template <bool FIXED>
 __device__ __forceinline__ void apply_pairs_dense(const BwdCtx& cx, float* lds_tile, const float2 g, const uint32_t gx, float fx,
                                                   float fy, float fz, const uint32_t ay0, const uint32_t az0, uint32_t cm) {
@@ -321,7 +321,7 @@ __device__ __forceinline__ void bwd_apply(const BwdCtx& cx, float* lds_tile, con
 
 // ---- hashed owners, coded variant ------------------------------------------------------------------------------
 // The owner test of a hashed level depends on (y,z) only, and it is the same for the 16 owners of the level, so a
-// pre-pass (tile_codes_kernel) evaluates it ONCE per (sample, level): one byte per (y,z) combination = the tile the
+// pre-pass (tile_codes4_kernel) evaluates it ONCE per (sample, level): one byte per (y,z) combination = the tile the
 // combination's two x-corners fall in.  An owner then streams 4-byte codes instead of positions + gradients, keeps
 // the samples that name its tile in a wave-private LDS queue (one ballot per sample) and applies them 64 at a time
 // at full lane occupancy; positions and gradients are gathered for queued samples only (about 22 % of them), and the
@@ -342,110 +342,176 @@ constexpr int kCodeSamplesPerBlock = 256;
 // when any of the sample's four (y,z) combinations names tile t.  The row lives in the first half of the level's code slot
 // (stride n_pad elements of two bytes); its owners are bwd_stream_masks.
 constexpr int kMaskTiles = 16;
-__device__ __forceinline__ bool mask_level(const TileParams& tp, int l) { return tp.tiles_of[l] <= kMaskTiles; }     // (of a hashed level)
+constexpr uint32_t kCodeMasks = 0u, kCodeBytes = 1u, kCodeDense = 2u, kCodeDenseWide = 3u;
+constexpr uint32_t kPackedMaxRes = 500;     // kCodeDense: res <= 500, so that no corner index of cells below 16383 wraps (16383 * (1 + 500 + 500^2) + 500 + 500^2 < 2^32)
 
-// The tile code of sample (x, y, z) at level l (see tile_codes_kernel); bad: the premise of the code does not hold.
-__device__ __forceinline__ uint32_t tile_code_of(const GridParams& gp, const TileParams& tp, int l, float x, float y, float z, bool& bad) {
-    const float py = grid_pos(y, gp.scale[l]), pz = grid_pos(z, gp.scale[l]);
-    const uint32_t gy = (uint32_t)(int32_t)floorf(py), gz = (uint32_t)(int32_t)floorf(pz);
-    const uint32_t gx = (uint32_t)(int32_t)floorf(grid_pos(x, gp.scale[l]));
+// What the pre-pass needs of one coded level, as ONE 48-byte piece of the kernel arguments: two wide scalar loads per level,
+// requested one level ahead.  (Read field by field out of GridParams / TileParams -- 3.4 KB by value -- a level cost three dependent
+// scalar loads per SAMPLE, each waited for: profiles/tile_codes_prepass.json.)  Only coded levels are listed.
+struct CodeLevel {
+    float scale;
+    uint32_t kind_level;        // kCode... | level << 8
+    uint32_t last;              // size - 1: a hashed level's index mask; a dense level's last entry (an x0 corner there or beyond has no x1 corner)
+    uint32_t res, res2;         // dense
+    uint32_t tmask;             // dense: tiles - 1 (1..63: single-tile levels are not coded)
+    int64_t row;                // slot * n_pad: the level's code row, in 4-byte words from `codes`
+    // dense, one byte per (y,z) combination c, whose x0 corner lies off_c = (c & 1) * res + (c >> 1) * res2 entries after the sample's first:
+    uint32_t off5;              // off_c % 32
+    uint32_t offc;              // (off_c / 32) % 64
+    uint32_t tmask4;            // tmask
+    uint32_t pad;
+};
+constexpr int kCodeWaves = 4;   // waves of a pre-pass workgroup: wave w takes the listed levels w, w + 4, ...
+struct CodePlan {
+    CodeLevel lv[PERF_MAX_LEVELS + kCodeWaves];     // (the tail stays zero: a wave requests the descriptor after its last unconditionally)
+    int32_t n_coded;
+};
+
+// Cell of a coordinate.  INSIDE: the caller knows that the grid position is >= 0 (or NaN), where the conversion's truncation IS the floor.
+template <bool INSIDE>
+__device__ __forceinline__ uint32_t code_cell(float v, float scale) {
+    const float p = grid_pos(v, scale);
+    return (uint32_t)(int32_t)(INSIDE ? p : floorf(p));
+}
+
+// The (y,z) part of a hashed level's four tile expressions.  A tile is bits 14 and up of an index below size <= 2^22 (coded levels
+// have at most 255 tiles), so only the low 24 bits of gy * P_y and gz * P_z count, and those are the low 24 bits of the full-rate
+// 24-bit product of the factors' low 24 bits: the same tiles as the 32-bit (quarter-rate) multiply gives, for any gy, gz.
+template <bool INSIDE>
+__device__ __forceinline__ void hashed_tiles(const CodeLevel& d, float y, float z, uint32_t t[4]) {
+    const uint32_t gy = code_cell<INSIDE>(y, d.scale), gz = code_cell<INSIDE>(z, d.scale);
+    const uint32_t ay0 = __umul24(gy, kPrimeY & 0xffffffu), ay1 = ay0 + kPrimeY, az0 = __umul24(gz, kPrimeZ & 0xffffffu), az1 = az0 + kPrimeZ;
+    const uint32_t m = d.last;
+    t[0] = ((ay0 ^ az0) & m) / (uint32_t)kTileEntries; t[1] = ((ay1 ^ az0) & m) / (uint32_t)kTileEntries;
+    t[2] = ((ay0 ^ az1) & m) / (uint32_t)kTileEntries; t[3] = ((ay1 ^ az1) & m) / (uint32_t)kTileEntries;
+}
+// dense level: byte = tile of the x0 corner, bit 7 set when the x1 corner sits in the next chunk (= next tile); 0x7f (no tile) when
+// the pair would wrap past the end of the level (the owners apply such a sample corner by corner, see bwd_stream_codes).
+// With i1 = i0 + 1: "i1 >= size or i1 == 0" is i0 >= size - 1, and the chunks of the two differ exactly when i0 is the last entry of
+// its chunk -- then the tiles differ too, as there are at least two.
+template <bool INSIDE>
+__device__ __forceinline__ uint32_t dense_code(const CodeLevel& d, float x, float y, float z) {
+    const uint32_t gy = code_cell<INSIDE>(y, d.scale), gz = code_cell<INSIDE>(z, d.scale), gx = code_cell<INSIDE>(x, d.scale);
+    const uint32_t base = gx + gy * d.res + gz * d.res2;
     uint32_t code = 0u;
-    if (gp.hashed[l]) {
-        const uint32_t ay0 = gy * kPrimeY, ay1 = ay0 + kPrimeY, az0 = gz * kPrimeZ, az1 = az0 + kPrimeZ;
-        const uint32_t m = gp.size[l] - 1u;
-        const uint32_t t0 = ((ay0 ^ az0) & m) / (uint32_t)kTileEntries, t1 = ((ay1 ^ az0) & m) / (uint32_t)kTileEntries,
-                       t2 = ((ay0 ^ az1) & m) / (uint32_t)kTileEntries, t3 = ((ay1 ^ az1) & m) / (uint32_t)kTileEntries;
-        // up to kMaskTiles tiles: a 16-bit MASK of the tiles the four combinations name (the caller stores two bytes per sample);
-        // beyond that one byte per combination
-        if (mask_level(tp, l)) code = (1u << t0) | (1u << t1) | (1u << t2) | (1u << t3);
-        else code = t0 | (t1 << 8) | (t2 << 16) | (t3 << 24);
-        // a position so far outside the unit cube that its x-corners leave the first 16384 columns breaks
-        // "(y,z) decides the tile"
-        bad = gx >= (uint32_t)(kTileEntries - 1);
-    } else {
-        // dense level: byte = tile of the x0 corner, bit 7 set when the x1 corner sits in the next chunk (= next
-        // tile); 0x7f (no tile) when the pair would wrap past the end of the level
-        const uint32_t res = gp.res[l], r2 = res * res, tmask = (uint32_t)tp.tiles_of[l] - 1u;
-        bad = false;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const uint32_t i0 = gx + (gy + (uint32_t)(c & 1)) * res + (gz + (uint32_t)(c >> 1)) * r2, i1 = i0 + 1u;
-            uint32_t b = 0x7fu;
-            if (i1 >= gp.size[l] || i1 == 0u) bad = true;
-            else b = ((i0 / kChunk) & tmask) | ((((i1 / kChunk) & tmask) != ((i0 / kChunk) & tmask)) ? 0x80u : 0u);
-            code |= b << (8 * c);
-        }
+    for (int c = 0; c < 4; ++c) {
+        const uint32_t i0 = base + ((c & 1) ? d.res : 0u) + ((c >> 1) ? d.res2 : 0u);
+        uint32_t b = ((i0 / kChunk) & d.tmask) | ((((i0 % kChunk) + 1u) * (0x80u / kChunk)) & 0x80u);
+        if (i0 >= d.last) b = 0x7fu;
+        code |= b << (8 * c);
     }
     return code;
 }
+// The same four bytes at once, for cells in [0, 16383) of a kCodeDense level (no index wraps): corner c is base + off_c, so
+//   its place in its chunk is  (base % 32 + off_c % 32) % 32          (the sum is at most 62: it stays in its byte),
+//   its chunk, modulo 64, is   (base / 32 % 64 + off_c / 32 % 64 + carry of the sum above) % 64     (at most 127),
+// and the tile is the chunk modulo the number of tiles, a power of two up to 64.  top: the largest x0 corner seen; when that has no x1
+// corner in the level (top >= last) some byte may have to be 0x7f, and the caller takes dense_code.
+__device__ __forceinline__ uint32_t byte4(uint32_t v) { return __builtin_amdgcn_perm(v, v, 0u); }      // the low byte of v in all four bytes (v * 0x01010101 is a quarter-rate multiply)
+__device__ __forceinline__ uint32_t dense_code_packed(const CodeLevel& d, float x, float y, float z, uint32_t& top) {
+    const uint32_t gy = code_cell<true>(y, d.scale), gz = code_cell<true>(z, d.scale), gx = code_cell<true>(x, d.scale);
+    const uint32_t base = gx + __umul24(gy, d.res) + __umul24(gz, d.res2);
+    top = max(top, base + d.res + d.res2);
+    const uint32_t place = byte4(base % kChunk) + d.off5;
+    const uint32_t next = (((place & 0x1f1f1f1fu) + 0x01010101u) << 2) & 0x80808080u;      // bit 7: the last entry of its chunk
+    const uint32_t chunk = byte4((base / kChunk) & 63u) + d.offc + ((place >> 5) & 0x01010101u);
+    return (chunk & d.tmask4) | next;
+}
 
-// one workgroup = the 256 samples of one escape word, a sample per thread
-__device__ __forceinline__ void tile_codes_block(const GridParams& gp, const TileParams& tp, const float* __restrict__ x01,
-                                                 const float2* __restrict__ dfeat, uint32_t* __restrict__ codes,
-                                                 uint32_t* __restrict__ escape, int64_t n, int64_t n_live) {
+// One coded level of a lane's four consecutive samples (cnt of them live): the codes, stored with one 8-byte (masks) or 16-byte store
+// (cnt < 4: element by element); returns the level's escape bit.  The kind is branched on once, around the four samples.
+// INSIDE: every grid position of the four samples is in [0, 16383) (or NaN) at this level.
+template <bool INSIDE>
+__device__ __forceinline__ uint32_t code_level(const CodeLevel& d, const float (&p)[12], int cnt, int64_t i0, uint32_t* __restrict__ codes,
+                                               const float2* __restrict__ dfeat, int64_t n) {
+    const uint32_t kind = d.kind_level & 0xffu;
+    uint32_t code[4];
+    if (kind == kCodeMasks) {           // 16-bit masks of the tiles the four combinations name
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            uint32_t t[4];
+            hashed_tiles<INSIDE>(d, p[3 * k + 1], p[3 * k + 2], t);
+            code[k] = (1u << t[0]) | (1u << t[1]) | (1u << t[2]) | (1u << t[3]);
+        }
+        uint16_t* row16 = reinterpret_cast<uint16_t*>(codes + d.row) + i0;
+        if (cnt == 4) {
+            *reinterpret_cast<uint2*>(row16) = make_uint2(code[0] | (code[1] << 16), code[2] | (code[3] << 16));
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < cnt) row16[k] = (uint16_t)code[k];
+        }
+    } else {                            // one byte per combination
+        if (kind == kCodeBytes) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                uint32_t t[4];
+                hashed_tiles<INSIDE>(d, p[3 * k + 1], p[3 * k + 2], t);
+                code[k] = t[0] | (t[1] << 8) | (t[2] << 16) | (t[3] << 24);
+            }
+        } else {
+            uint32_t top = 0xffffffffu;
+            if (INSIDE && kind == kCodeDense) {
+                top = 0u;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) code[k] = dense_code_packed(d, p[3 * k], p[3 * k + 1], p[3 * k + 2], top);
+            }
+            if (top >= d.last) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) code[k] = dense_code<INSIDE>(d, p[3 * k], p[3 * k + 1], p[3 * k + 2]);
+            }
+        }
+        uint32_t* row = codes + d.row + i0;
+        if (cnt == 4) {
+            *reinterpret_cast<uint4*>(row) = make_uint4(code[0], code[1], code[2], code[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < cnt) row[k] = code[k];
+        }
+    }
+    uint32_t esc = 0u;
+    if (!INSIDE && (kind == kCodeMasks || kind == kCodeBytes)) {
+        // a position so far outside the unit cube that its x-corners leave the first 16384 columns breaks "(y,z) decides the tile":
+        // harmless without gradient; with gradient the level's owners take the generic path
+        const uint32_t l = d.kind_level >> 8;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < cnt && code_cell<false>(p[3 * k], d.scale) >= (uint32_t)(kTileEntries - 1)) {
+                const float2 g = dfeat[(int64_t)l * n + i0 + k];
+                if (!(g.x == 0.f && g.y == 0.f)) esc = 1u << l;
+            }
+    }
+    return esc;
+}
+
+// The tile codes of every coded level.  One workgroup = the 256 samples of one escape word: each of its four waves holds all 256 (four
+// consecutive samples per lane: 48 bytes of positions in three 16-byte loads, one 16- or 8-byte store per level) and computes every
+// fourth level, so that 1 M samples give a SIMD sixteen short waves, and the 16-35 k live rows of the reference-faithful training
+// step (1 M-row capacity; the count is on the device) still some hundred waves; workgroups past the live count only write their
+// (zero) escape word.  What bounds the kernel is its vector arithmetic (profiles/tile_codes_prepass.json), so the work per
+// (sample, level) is kept short:
+//  * one test per level and lane, on the smallest and the largest coordinate of the lane's samples (the grid position is monotonic
+//    in the coordinate), says that every position of the level lies in [0, 16383) -- then nothing escapes, the cells need no floor
+//    and a dense level's four bytes are formed at once (dense_code_packed); lanes that fail it take the exact path, so the codes are
+//    the same for any input;
+//  * the hashed levels multiply with the full-rate 24-bit multiplier (hashed_tiles);
+//  * the exact dense byte takes two comparisons per corner (dense_code).
+// (The launch can carry the MLP backward's second stage in workgroups of its own behind the `own_blocks` that compute codes:
+//  mlp_reduce_device.hpp.)
+__global__ __launch_bounds__(64 * kCodeWaves) void tile_codes4_kernel(CodePlan cp, const float* __restrict__ x01,
+                                                                       const float2* __restrict__ dfeat, uint32_t* __restrict__ codes,
+                                                                       uint32_t* __restrict__ escape, int64_t n,
+                                                                       const int64_t* __restrict__ n_dev, MlpReduceJob job, unsigned own_blocks) {
+    if (blockIdx.x >= own_blocks) { mlp_reduce_block(job, (int)(blockIdx.x - own_blocks)); return; }
+    const int64_t n_live = live_count(n, n_dev);            // n: capacity = stride of dfeat
     __shared__ uint32_t esc_block;
     if (threadIdx.x == 0) esc_block = 0u;
     __syncthreads();
-    uint32_t esc = 0u;                  // bit l: level l must take the generic owners (see below)
-    const int64_t i0 = (int64_t)blockIdx.x * kCodeSamplesPerBlock;
-    for (int64_t i = i0 + threadIdx.x; i < n_live && i < i0 + kCodeSamplesPerBlock; i += 256) {
-        const float x = x01[3 * i], y = x01[3 * i + 1], z = x01[3 * i + 2];
-        for (int l = 0; l < gp.n_levels; ++l) {
-            const int slot = tp.code_slot[l];
-            if (slot < 0) continue;
-            bool bad;       // the premise of the code does not hold for this sample
-            const uint32_t code = tile_code_of(gp, tp, l, x, y, z, bad);
-            if (gp.hashed[l] && mask_level(tp, l)) reinterpret_cast<uint16_t*>(codes + (int64_t)slot * tp.n_pad)[i] = (uint16_t)code;
-            else codes[(int64_t)slot * tp.n_pad + i] = code;
-            if (bad && gp.hashed[l]) {      // harmless without gradient; with gradient the level's owners take the generic path
-                                            // (dense: the owners apply such a sample corner by corner, see bwd_stream_codes)
-                const float2 g = dfeat[(int64_t)l * n + i];
-                if (!(g.x == 0.f && g.y == 0.f)) esc |= 1u << l;
-            }
-        }
-    }
-    if (esc) atomicOr(&esc_block, esc);
-    __syncthreads();
-    if (threadIdx.x == 0) escape[blockIdx.x] = esc_block;       // every word is written: no zero-fill needed
-}
-
-// (both pre-pass kernels can carry the MLP backward's second stage in workgroups of their own behind the `own_blocks` that compute
-//  codes: mlp_reduce_device.hpp)
-__global__ __launch_bounds__(256) void tile_codes_kernel(GridParams gp, TileParams tp, const float* __restrict__ x01,
-                                                         const float2* __restrict__ dfeat, uint32_t* __restrict__ codes,
-                                                         uint32_t* __restrict__ escape, int64_t n,
-                                                         const int64_t* __restrict__ n_dev, MlpReduceJob job, unsigned own_blocks) {
-    if (blockIdx.x >= own_blocks) { mlp_reduce_block(job, (int)(blockIdx.x - own_blocks)); return; }
-    tile_codes_block(gp, tp, x01, dfeat, codes, escape, n, live_count(n, n_dev));       // n: capacity = stride of dfeat / codes
-}
-
-// The same codes, four consecutive samples per thread: 48 bytes of positions in three 16-byte loads and one 16-byte store per
-// level instead of four 4-byte ones (the byte-code kernel spent most of a wave's life queueing stores: 16 per sample).  A wave
-// covers the 256 samples of one escape word.  (The kernel above serves workspaces whose code rows are not 16-byte aligned.)
-// The launch has one workgroup per escape word; with many live samples only the first quarter of them works (four words each).
-// With FEW live samples (the reference-faithful training step: 16-35 k live rows of a 1 M-row capacity) four samples per thread
-// leave a handful of waves walking 4 x 16 levels each -- 13.5 us against 7 for the one-sample-per-thread shape, which those
-// launches therefore take (the count is on the device: the shape is chosen here, not by the host).
-constexpr int64_t kCodes4MinLive = 65536;
-__global__ __launch_bounds__(256) void tile_codes4_kernel(GridParams gp, TileParams tp, const float* __restrict__ x01,
-                                                          const float2* __restrict__ dfeat, uint32_t* __restrict__ codes,
-                                                          uint32_t* __restrict__ escape, int64_t n, int64_t n_words,
-                                                          const int64_t* __restrict__ n_dev, MlpReduceJob job, unsigned own_blocks) {
-    if (blockIdx.x >= own_blocks) { mlp_reduce_block(job, (int)(blockIdx.x - own_blocks)); return; }
-    const int64_t n_live = live_count(n, n_dev);
-    if (n_live < kCodes4MinLive) {                         // (uniform)
-        tile_codes_block(gp, tp, x01, dfeat, codes, escape, n, n_live);
-        return;
-    }
-    if ((int64_t)blockIdx.x * 4 >= n_words) return;
-    __shared__ uint32_t esc_w[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) esc_w[wave] = 0u;
-    __builtin_amdgcn_wave_barrier();
-    const int64_t word = (int64_t)blockIdx.x * 4 + wave;
-    if (word >= n_words) return;                            // (whole waves leave)
-    const int64_t i0 = word * kCodeSamplesPerBlock + 4 * lane;
-    uint32_t esc = 0u;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t i0 = (int64_t)blockIdx.x * kCodeSamplesPerBlock + 4 * lane;
+    uint32_t esc = 0u;                  // bit l: level l must take the generic owners
     if (i0 < n_live) {
         const int cnt = (n_live - i0) < 4 ? (int)(n_live - i0) : 4;
         float p[12];
@@ -461,43 +527,22 @@ __global__ __launch_bounds__(256) void tile_codes4_kernel(GridParams gp, TilePar
                 p[3 * k] = x01[3 * i]; p[3 * k + 1] = x01[3 * i + 1]; p[3 * k + 2] = x01[3 * i + 2];
             }
         }
-        for (int l = 0; l < gp.n_levels; ++l) {
-            const int slot = tp.code_slot[l];
-            if (slot < 0) continue;
-            uint32_t code[4];
-            bool bad[4];
+        float lo = p[0], hi = p[0];     // (fminf / fmaxf skip NaNs: a NaN coordinate's cell is 0 on either path; all NaN fails the test)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) code[k] = tile_code_of(gp, tp, l, p[3 * k], p[3 * k + 1], p[3 * k + 2], bad[k]);
-            uint32_t* row = codes + (int64_t)slot * tp.n_pad + i0;
-            if (gp.hashed[l] && mask_level(tp, l)) {          // four masks: one 8-byte store
-                uint16_t* row16 = reinterpret_cast<uint16_t*>(codes + (int64_t)slot * tp.n_pad) + i0;
-                if (cnt == 4) {
-                    *reinterpret_cast<uint2*>(row16) = make_uint2(code[0] | (code[1] << 16), code[2] | (code[3] << 16));
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (k < cnt) row16[k] = (uint16_t)code[k];
-                }
-            } else if (cnt == 4) {
-                *reinterpret_cast<uint4*>(row) = make_uint4(code[0], code[1], code[2], code[3]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (k < cnt) row[k] = code[k];
-            }
-            if (gp.hashed[l]) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (bad[k] && k < cnt) {   // harmless without gradient; with gradient the level's owners take the generic path
-                        const float2 g = dfeat[(int64_t)l * n + i0 + k];
-                        if (!(g.x == 0.f && g.y == 0.f)) esc |= 1u << l;
-                    }
-            }
+        for (int k = 1; k < 12; ++k) { lo = fminf(lo, p[k]); hi = fmaxf(hi, p[k]); }
+        CodeLevel next = cp.lv[wave];
+        for (int j = wave; j < cp.n_coded; j += kCodeWaves) {
+            const CodeLevel d = next;
+            next = cp.lv[j + kCodeWaves];
+            if (grid_pos(lo, d.scale) >= 0.f && grid_pos(hi, d.scale) < (float)(kTileEntries - 1))
+                esc |= code_level<true>(d, p, cnt, i0, codes, dfeat, n);
+            else
+                esc |= code_level<false>(d, p, cnt, i0, codes, dfeat, n);
         }
     }
-    if (esc) atomicOr(&esc_w[wave], esc);
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) escape[word] = esc_w[wave];              // every word is written: no zero-fill needed
+    if (esc) atomicOr(&esc_block, esc);
+    __syncthreads();
+    if (threadIdx.x == 0) escape[blockIdx.x] = esc_block;       // every word is written: no zero-fill needed
 }
 
 // ---- levels of 256..2048 tiles (log2_hashmap_size 22..25): per-tile bitmaps ---------------------------------------
@@ -538,7 +583,7 @@ __global__ __launch_bounds__(256) void tile_bitmap_kernel(GridParams gp, TilePar
             atomicOr(&stage[(((ay1 ^ az0) & m) / (uint32_t)kTileEntries) * useg + word], bit);
             atomicOr(&stage[(((ay0 ^ az1) & m) / (uint32_t)kTileEntries) * useg + word], bit);
             atomicOr(&stage[(((ay1 ^ az1) & m) / (uint32_t)kTileEntries) * useg + word], bit);
-            bad = gx >= (uint32_t)(kTileEntries - 1);       // "(y,z) decides the tile" does not hold (see tile_codes_kernel)
+            bad = gx >= (uint32_t)(kTileEntries - 1);       // "(y,z) decides the tile" does not hold (see tile_codes4_kernel)
         } else {            // dense: chunk-interleaved ownership; every corner on its own, indices past the end wrap (bwd_apply's rule),
                             // so these levels never escape
             const uint32_t res = gp.res[l], r2 = res * res, tmask = (uint32_t)nt - 1u;
@@ -674,7 +719,7 @@ __device__ __forceinline__ void bwd_stream_codes(const BwdCtx& cx, float* lds_ti
             if (DENSE)
                 apply_pairs_dense<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, py - fly, pz - flz,
                                          (uint32_t)(int32_t)fly * cx.res, (uint32_t)(int32_t)flz * cx.r2, bcm);
-            else if (gx < (uint32_t)(kTileEntries - 1))      // (else: zero gradient, see tile_codes_kernel)
+            else if (gx < (uint32_t)(kTileEntries - 1))      // (else: zero gradient, see tile_codes4_kernel)
                 apply_pairs<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, py - fly, pz - flz,
                                    (uint32_t)(int32_t)fly * kPrimeY, (uint32_t)(int32_t)flz * kPrimeZ, bcm);
         }
@@ -728,12 +773,12 @@ __device__ __forceinline__ void bwd_stream_codes(const BwdCtx& cx, float* lds_ti
 #undef PERF_WAIT_BATCH
 }
 
-// ---- hashed owners of a mask level (at most 16 tiles: see mask_level) ------------------------------------------------
+// ---- hashed owners of a mask level (at most 16 tiles: kMaskTiles) ------------------------------------------------
 // The same loop over a 16-bit mask per sample: the test of a sample is ONE AND against this owner's bit and the compare that is
 // the ballot (the byte codes take five instructions for the zero-byte marks and a dot product on the lanes that hit), and a lane's four
 // samples arrive in one 8-byte load.  What the mask does not say is WHICH of the sample's four (y,z) combinations name the tile: a
 // fresh queue entry carries cm = 0 and the apply works the combinations out from the (y,z) it gathered anyway, with the pre-pass's own
-// four tile expressions (tile_code_of); re-queued entries carry their remaining combinations as before.
+// four tile expressions (hashed_tiles); re-queued entries carry their remaining combinations as before.
 // In flight at the head of an iteration, oldest first: [masks: 1][gather batch: 3], so "vmcnt(3)" = the masks have landed; every pop
 // issues 3 loads and every iteration 1, whatever the queue holds.  The queue bound is bwd_stream_codes' (kQueueCap).
 // (A SECOND gather batch in flight per wave -- two register sets taking turns, the main loop unrolled by two, bursts drained in pairs,
@@ -804,7 +849,7 @@ __device__ __forceinline__ void bwd_stream_masks(const BwdCtx& cx, float* lds_ti
         const uint32_t derived = ((((ay0 ^ az0) & m_hi) == t_hi) ? 1u : 0u) | ((((ay1 ^ az0) & m_hi) == t_hi) ? 2u : 0u) |
                                  ((((ay0 ^ az1) & m_hi) == t_hi) ? 4u : 0u) | ((((ay1 ^ az1) & m_hi) == t_hi) ? 8u : 0u);
         uint32_t cm = A.cm ? A.cm : derived;
-        if (!A.live || gx >= (uint32_t)(kTileEntries - 1)) cm = 0u;     // (idle lane; or zero gradient, see tile_codes_kernel)
+        if (!A.live || gx >= (uint32_t)(kTileEntries - 1)) cm = 0u;     // (idle lane; or zero gradient, see tile_codes4_kernel)
         const uint32_t rest = cm & (cm - 1u);
         cm &= 0u - cm;
         if (cm) apply_pairs<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, py - fly, pz - flz, ay0, az0, cm);
@@ -1468,6 +1513,29 @@ static int plan_codes(const GridParams& gp, int64_t n, TileParams* tp) {
     return slots;
 }
 
+// the coded levels as the pre-pass reads them (CodeLevel), in level order
+static void plan_code_levels(const GridParams& gp, const TileParams& tp, CodePlan* cp) {
+    *cp = CodePlan{};
+    for (int l = 0; l < gp.n_levels; ++l) {
+        if (tp.code_slot[l] < 0) continue;
+        CodeLevel& d = cp->lv[cp->n_coded++];
+        const uint32_t kind = gp.hashed[l] ? (tp.tiles_of[l] <= kMaskTiles ? kCodeMasks : kCodeBytes)
+                                           : (gp.res[l] <= kPackedMaxRes ? kCodeDense : kCodeDenseWide);
+        d.scale = gp.scale[l];
+        d.kind_level = kind | ((uint32_t)l << 8);
+        d.last = gp.size[l] - 1u;
+        d.res = gp.res[l]; d.res2 = gp.res[l] * gp.res[l];
+        d.tmask = (uint32_t)tp.tiles_of[l] - 1u;         // (plan_codes: 2..64 tiles)
+        d.row = (int64_t)tp.code_slot[l] * tp.n_pad;
+        for (uint32_t c = 0; c < 4; ++c) {
+            const uint32_t off = (c & 1u) * d.res + (c >> 1) * d.res2;
+            d.off5 |= (off % kChunk) << (8 * c);
+            d.offc |= ((off / kChunk) & 63u) << (8 * c);
+            d.tmask4 |= d.tmask << (8 * c);
+        }
+    }
+}
+
 constexpr int64_t kShiftBytes = 256;        // per-level shifts the owners leave for the replica reduction
 
 // bitmap rows of the levels plan_tiles marked (bitmap_levels); returns the bytes of [bitmaps][escape words] or 0
@@ -1622,12 +1690,10 @@ int perf_internal_hashgrid_bwd(const perf_grid_desc* grid, const float* x01, con
         workspace_bytes >= codes_at + (int64_t)slots * tp.n_pad * 4 + esc_words * 4) {
         codes = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + codes_at);
         escape = codes + (int64_t)slots * tp.n_pad;
-        const unsigned own = (unsigned)esc_words, all = own + (unsigned)job.n_blocks;
-        if ((reinterpret_cast<uintptr_t>(codes) & 15) == 0)
-            tile_codes4_kernel<<<dim3(all), dim3(256), 0, as_stream(stream)>>>(gp, tp, x01, (const float2*)dfeat, codes, escape, n, esc_words, n_dev,
-                                                                                job, own);
-        else
-            tile_codes_kernel<<<dim3(all), dim3(256), 0, as_stream(stream)>>>(gp, tp, x01, (const float2*)dfeat, codes, escape, n, n_dev, job, own);
+        CodePlan cp;
+        plan_code_levels(gp, tp, &cp);
+        const unsigned own = (unsigned)esc_words, all = own + (unsigned)job.n_blocks;       // (codes: 16-byte aligned, as the workspace and codes_at are)
+        tile_codes4_kernel<<<dim3(all), dim3(64 * kCodeWaves), 0, as_stream(stream)>>>(cp, x01, (const float2*)dfeat, codes, escape, n, n_dev, job, own);
         PERF_LAUNCH_CHECK("perf_hashgrid_bwd(codes)");
         job.n_blocks = 0;                          // (done)
     } else {

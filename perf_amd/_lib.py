@@ -19,6 +19,7 @@ MESH_ABI_VERSION = 1     # PERF_MESH_ABI_VERSION of include/perf_hip_mesh.h (sur
 BRICKMESH_ABI_VERSION = 1    # PERF_BRICKMESH_ABI_VERSION of include/perf_hip_brickmesh.h (surface nets on the live bricks of a lattice)
 MESHCC_ABI_VERSION = 1       # PERF_MESHCC_ABI_VERSION of include/perf_hip_meshcc.h (connected components of a triangle mesh)
 MESHVIS_ABI_VERSION = 1      # PERF_MESHVIS_ABI_VERSION of include/perf_hip_meshvis.h (cull the mesh faces no registered panorama saw)
+MESHSIMP_ABI_VERSION = 1     # PERF_MESHSIMP_ABI_VERSION of include/perf_hip_meshsimp.h (simplify a mesh by vertex clustering)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -232,6 +233,23 @@ _SIGS_MESHVIS = {
     'perf_meshvis_filter_write': (c_int, [P, c_int64, c_int64, P, P, P, c_int64, P, P, c_int64, P, c_int64, P]),
 }
 
+# include/perf_hip_meshsimp.h: simplify a mesh by vertex clustering, versioned on its own (perf_meshsimp_version)
+MESHSIMP_MAX_VERTICES = 1 << 30      # PERF_MESHSIMP_MAX_VERTICES
+MESHSIMP_MAX_FACES = (1 << 31) - 1   # PERF_MESHSIMP_MAX_FACES
+MESHSIMP_MAX_CELLS = 1 << 21         # PERF_MESHSIMP_MAX_CELLS, per axis
+MESHSIMP_PLACEMENT = {'mean': 0, 'member': 1}                       # PERF_MESHSIMP_PLACE_*
+MESHSIMP_DEDUPE = {None: 0, 'oriented': 1, 'unoriented': 2}         # PERF_MESHSIMP_DEDUPE_*
+MESHSIMP_SCRATCH_BYTES = 48          # of perf_meshsimp_place's scratch, per cluster
+_SIGS_MESHSIMP = {
+    'perf_meshsimp_version': (c_int, []),
+    'perf_meshsimp_table_slots': (c_int64, [c_int64]),
+    'perf_meshsimp_workspace_bytes': (c_int64, [c_int64, c_int64]),
+    'perf_meshsimp_bounds': (c_int, [P, c_int64, P, P]),
+    'perf_meshsimp_cluster': (c_int, [P, c_int64, c_int64, POINTER(c_float), c_float, c_int32, c_int32, c_int32, P, P, P, c_int64, P]),
+    'perf_meshsimp_place': (c_int, [P, c_int64, POINTER(c_float), c_float, c_int32, c_int32, c_int32, P, c_int64, c_int32, P, P, P, c_int64, P]),
+    'perf_meshsimp_faces': (c_int, [P, c_int64, P, c_int64, c_int32, P, P, P, P, c_int64, P]),
+}
+
 _lib = None
 
 
@@ -247,7 +265,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()) + list(_SIGS_MESHVIS.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()) + list(_SIGS_MESHVIS.items()) + list(_SIGS_MESHSIMP.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
@@ -281,6 +299,9 @@ def load():
     if lib.perf_meshvis_version() != MESHVIS_ABI_VERSION or lib.perf_meshvis_sizeof_view() != MESHVIS_VIEW_BYTES:
         raise PerfError(f'{LIB_PATH} has visibility-cull ABI version {lib.perf_meshvis_version()} and a view of {lib.perf_meshvis_sizeof_view()} bytes, this binding '
                         f'expects {MESHVIS_ABI_VERSION} and {MESHVIS_VIEW_BYTES}: rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_meshsimp_version() != MESHSIMP_ABI_VERSION:
+        raise PerfError(f'{LIB_PATH} has mesh-simplification ABI version {lib.perf_meshsimp_version()}, this binding expects {MESHSIMP_ABI_VERSION}: '
+                        'rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):
         raise PerfError('descriptor layout mismatch between perf_amd/_lib.py and include/perf_hip.h')

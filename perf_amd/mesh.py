@@ -377,6 +377,110 @@ def cull_unseen(mesh, views, tol=1 / 256, free_tol=None, facing=True, min_views=
     return _filter_faces(mesh, keep, counts, 'cull_unseen')[0]
 
 
+# ---- a mesh of a size the caller chooses: vertex clustering (include/perf_hip_meshsimp.h) -------------------------------------------------
+class Clusters(NamedTuple):
+    vertex_cluster: torch.Tensor                 # [V] int32: the id of each vertex's cluster, ids ordered by smallest member index
+    n_clusters: int
+    vertices: torch.Tensor                       # [C, 3] fp32: the clusters' vertices under the placement
+    representative: torch.Tensor                 # [C] int32: the member nearest the cluster's mean; it carries per-vertex attributes
+
+
+def _cluster_grid(who, vertices, cell, box):
+    """(lo [3], h, n [3]) of include/perf_hip_meshsimp.h: lo and h as the fp32 values the library takes, n = max(1, ceil((hi - lo) / h))
+    per axis in double.  box None: the bounds of the finite coordinates, read back from the device."""
+    h = float(np.float32(cell))
+    if not math.isfinite(h) or h <= 0:
+        raise _lib.PerfError(f'{who}: the cell edge {cell!r} is not positive or not finite')
+    if box is None:
+        bounds = ops.meshsimp_bounds(vertices).tolist()          # the host read-back of the six bounds
+        if not all(math.isfinite(b) for b in bounds):            # (no finite coordinate along an axis: the clustering names the vertex)
+            bounds = [0.0] * 6
+        lo, hi = bounds[:3], bounds[3:]
+    else:
+        lo, hi = ([float(v) for v in side] for side in box)
+        if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(v) for v in lo + hi) or any(b < a for a, b in zip(lo, hi)):
+            raise _lib.PerfError(f'{who}: box is (lo, hi), three finite values each with lo <= hi, got {box!r}')
+    lo = [float(np.float32(v)) for v in lo]
+    n = [max(1, math.ceil((b - a) / h)) for a, b in zip(lo, hi)]
+    if max(n) > _lib.MESHSIMP_MAX_CELLS:
+        raise _lib.PerfError(f'{who}: a cell of {h} makes {n} cells per axis of the box, more than 2^21: choose a larger cell')
+    return lo, h, n
+
+
+def _check_placement(who, placement, dedupe='oriented'):
+    if placement not in _lib.MESHSIMP_PLACEMENT:
+        raise _lib.PerfError(f"{who}: placement is 'mean' or 'member', got {placement!r}")
+    if dedupe not in _lib.MESHSIMP_DEDUPE:
+        raise _lib.PerfError(f"{who}: dedupe is 'oriented', 'unoriented' or None, got {dedupe!r}")
+
+
+def _raise_bad_vertex(who, vertices, bad):
+    raise _lib.PerfError(f'{who}: vertex {bad} = {vertices[bad].tolist()} has a coordinate that is not finite')
+
+
+def cluster_vertices(vertices, cell, box=None, placement='mean') -> Clusters:
+    """The vertices fp32 [V, 3] that share a cell of edge `cell` of the grid over box = (lo, hi) (None: the vertices' own bounds, one more
+    host read) become one cluster: its vertex is the mean of its members (exact integer sums of 2^-32 fixed-point fractions) or, under
+    placement='member', the member nearest that mean, bit for bit.  One host read: the cluster count with the flag of a vertex that is
+    not finite, which is refused."""
+    if not torch.is_tensor(vertices) or not vertices.is_cuda:
+        raise _lib.PerfError('cluster_vertices: vertices must be a CUDA tensor (there is no CPU path)')
+    _check_placement('cluster_vertices', placement)
+    vertices = vertices.contiguous()
+    lo, h, n = _cluster_grid('cluster_vertices', vertices, cell, box)
+    vertex_cluster, counts, _ = ops.meshsimp_cluster(vertices, lo, h, n)
+    n_clusters, bad = (int(v) for v in counts.tolist())          # the one host synchronisation of a clustering
+    if bad >= 0:
+        _raise_bad_vertex('cluster_vertices', vertices, bad)
+    placed, representative = ops.meshsimp_place(vertices, lo, h, n, vertex_cluster, n_clusters, placement)
+    return Clusters(vertex_cluster, n_clusters, placed, representative)
+
+
+def cluster_faces(faces, clusters, dedupe='oriented'):
+    """faces int32 [F, 3] through the clusters -> (faces int32 [F, 3] of cluster ids, keep uint8 [F]): a face is dropped when two of its
+    cluster ids are equal, and, of the faces whose triples are equal up to rotation (dedupe='oriented') or as sets ('unoriented': a double
+    skin thinner than a cell becomes one), all but the one with the smallest index; None keeps every face that is not degenerate.  One
+    host read: the flag of a face index outside [0, V), which is refused."""
+    if not torch.is_tensor(faces) or not faces.is_cuda:
+        raise _lib.PerfError('cluster_faces: faces must be a CUDA tensor (there is no CPU path)')
+    _check_placement('cluster_faces', 'mean', dedupe)
+    faces = faces.contiguous()
+    remapped, keep, flag = ops.meshsimp_faces(faces, clusters.vertex_cluster, dedupe)
+    bad = int(flag.item())          # the one host synchronisation
+    if bad >= 0:
+        _raise_bad_face('cluster_faces', faces, bad, clusters.vertex_cluster.numel())
+    return remapped, keep
+
+
+def simplify_mesh(mesh, cell, box=None, placement='mean', dedupe='oriented'):
+    """mesh with one vertex per occupied cell of edge `cell` -> (Mesh, kept_vertex_index int32 [V']): cluster_vertices -> cluster_faces ->
+    the compaction of filter_faces, with ONE host read of (clusters, the two flags, kept vertices, kept faces) beside the compaction's own.
+    Clusters no kept face names are dropped; kept_vertex_index holds the surviving clusters' representatives, through which colors and
+    normals are gathered.  Clustering can pinch a surface: there is no manifold repair."""
+    _check_mesh('simplify_mesh', mesh)
+    _check_placement('simplify_mesh', placement, dedupe)
+    vertices, faces = mesh.vertices.contiguous(), mesh.faces.contiguous()
+    n_vertices, n_faces = int(vertices.shape[0]), int(faces.shape[0])
+    lo, h, n = _cluster_grid('simplify_mesh', vertices, cell, box)
+    counts = torch.empty(5, dtype=torch.int64, device=faces.device)
+    vertex_cluster, _, ws = ops.meshsimp_cluster(vertices, lo, h, n, n_faces=n_faces, counts=counts[:2])
+    remapped, keep, _ = ops.meshsimp_faces(faces, vertex_cluster, dedupe, ws=ws, flag=counts[2:3])
+    _, filter_ws = ops.meshvis_filter_count(remapped, n_vertices, keep, counts=counts[3:])
+    n_clusters, bad_vertex, bad_face, kept_vertices, kept_faces = (int(c) for c in counts.tolist())          # the one host synchronisation
+    if bad_vertex >= 0:
+        _raise_bad_vertex('simplify_mesh', vertices, bad_vertex)
+    if bad_face >= 0:
+        _raise_bad_face('simplify_mesh', faces, bad_face, n_vertices)
+    placed, representative = ops.meshsimp_place(vertices, lo, h, n, vertex_cluster, n_clusters, placement)
+    _, new_faces, kept_cluster = ops.meshvis_filter_write(remapped, n_vertices, keep, filter_ws, kept_vertices, kept_faces)
+    kept_cluster = kept_cluster.long()
+    index = representative[kept_cluster]
+    gather = index.long()
+    colors = mesh.colors[gather] if mesh.colors is not None else None
+    normals = mesh.normals[gather] if mesh.normals is not None else None
+    return Mesh(placed[kept_cluster], new_faces, colors, normals), index
+
+
 def write_ply(path, mesh):
     """Binary little-endian PLY: x y z [nx ny nz] [red green blue as uchar] per vertex, a uchar-counted int list per face."""
     v = mesh.vertices.detach().cpu().numpy().astype('<f4')

@@ -1116,6 +1116,97 @@ def meshvis_filter_write(faces, n_vertices, face_keep, ws, n_vertices_kept, n_fa
     return vertices_out, faces_out, index
 
 
+# ---- simplify a mesh by vertex clustering (include/perf_hip_meshsimp.h) -----------------------------------------------------------------
+def _simp_ws(n_vertices, n_faces, ws, device):
+    nbytes = _lib.load().perf_meshsimp_workspace_bytes(n_vertices, n_faces)
+    if nbytes < 0:
+        _lib.check(-1, 'perf_meshsimp_workspace_bytes')
+    if ws is None or ws.numel() * 8 < nbytes or ws.device != device:
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+    return ws
+
+
+def _simp_vertices(who, vertices):
+    if not torch.is_tensor(vertices) or not vertices.is_cuda:
+        raise _lib.PerfError(f'{who}: vertices must be a CUDA tensor (there is no CPU path)')
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
+        raise _lib.PerfError(f'{who}: vertices must be a contiguous fp32 [V, 3] tensor, got {tuple(vertices.shape)}')
+    return _f32(vertices, 'vertices'), int(vertices.shape[0])
+
+
+def _simp_grid(who, lo, h, n):
+    lo3, n3 = [float(v) for v in lo], [int(v) for v in n]
+    if len(lo3) != 3 or len(n3) != 3:
+        raise _lib.PerfError(f'{who}: lo and n hold three values each')
+    if any(v < 1 or v > _lib.MESHSIMP_MAX_CELLS for v in n3):
+        raise _lib.PerfError(f'{who}: {n3} cells per axis are outside 1 .. 2^21')
+    return (ctypes.c_float * 3)(*lo3), float(h), n3
+
+
+def meshsimp_bounds(vertices):
+    """fp32 [6] ON THE DEVICE: the smallest x, y, z and the largest x, y, z among the finite coordinates of vertices fp32 [V, 3]
+    (perf_meshsimp_bounds); (+inf x 3, -inf x 3) when there is none."""
+    vertices, n = _simp_vertices('meshsimp_bounds', vertices)
+    bounds = torch.empty(6, dtype=torch.float32, device=vertices.device)
+    _call('perf_meshsimp_bounds', _p(vertices) if n else None, n, _p(bounds), _stream())
+    return bounds
+
+
+def meshsimp_cluster(vertices, lo, h, n, n_faces=0, ws=None, counts=None):
+    """The clusters of vertices fp32 [V, 3] in the grid (lo [3], cell edge h, n [3] cells per axis) by the cell rule of
+    include/perf_hip_meshsimp.h (perf_meshsimp_cluster) -> (vertex_cluster int32 [V], counts, ws): counts = int64 [2] ON THE DEVICE (C, the
+    first vertex with a coordinate that is not finite or -1; an int64 [2] view to write them into may be passed).  n_faces: the faces the
+    workspace is to serve as well (meshsimp_faces)."""
+    vertices, nv = _simp_vertices('meshsimp_cluster', vertices)
+    lo3, h, n3 = _simp_grid('meshsimp_cluster', lo, h, n)
+    ws = _simp_ws(nv, int(n_faces), ws, vertices.device)
+    vertex_cluster = torch.empty(nv, dtype=torch.int32, device=vertices.device)
+    if counts is None:
+        counts = torch.empty(2, dtype=torch.int64, device=vertices.device)
+    _call('perf_meshsimp_cluster', _p(vertices) if nv else None, nv, int(n_faces), lo3, h, *n3, _p(vertex_cluster) if nv else None, _p(counts), _p(ws), ws.numel() * 8,
+          _stream())
+    return vertex_cluster, counts, ws
+
+
+def meshsimp_place(vertices, lo, h, n, vertex_cluster, n_clusters, placement='mean'):
+    """(cluster_vertices fp32 [C, 3], representative int32 [C]) of the labelling meshsimp_cluster made of the SAME vertices and grid
+    (perf_meshsimp_place).  placement: 'mean' or 'member'."""
+    vertices, nv = _simp_vertices('meshsimp_place', vertices)
+    lo3, h, n3 = _simp_grid('meshsimp_place', lo, h, n)
+    _cc_labels('meshsimp_place', vertex_cluster, nv, vertices.device)
+    if placement not in _lib.MESHSIMP_PLACEMENT:
+        raise _lib.PerfError(f"meshsimp_place: placement is 'mean' or 'member', got {placement!r}")
+    c = int(n_clusters)
+    out = torch.empty(c, 3, dtype=torch.float32, device=vertices.device)
+    representative = torch.empty(c, dtype=torch.int32, device=vertices.device)
+    scratch = torch.empty(c * (_lib.MESHSIMP_SCRATCH_BYTES // 8), dtype=torch.int64, device=vertices.device)
+    _call('perf_meshsimp_place', _p(vertices) if nv else None, nv, lo3, h, *n3, _p(vertex_cluster) if nv else None, c, _lib.MESHSIMP_PLACEMENT[placement],
+          _p(out) if c else None, _p(representative) if c else None, _p(scratch) if c else None, scratch.numel() * 8, _stream())
+    return out, representative
+
+
+def meshsimp_faces(faces, vertex_cluster, dedupe='oriented', ws=None, flag=None):
+    """faces int32 [F, 3] through vertex_cluster int32 [V] (perf_meshsimp_faces) -> (remapped int32 [F, 3], face_keep uint8 [F], flag):
+    a face is kept unless two of its cluster ids are equal or (dedupe 'oriented' / 'unoriented') a face with a smaller index has its
+    triple up to rotation / as a set; flag = int64 [1] ON THE DEVICE, the smallest index of a face with an index outside [0, V) or -1 (an
+    int64 [1] view to write it into may be passed)."""
+    nv = int(vertex_cluster.numel()) if torch.is_tensor(vertex_cluster) else 0
+    _, f = _cc_faces('meshsimp_faces', faces, nv)
+    _cc_labels('meshsimp_faces', vertex_cluster, nv, faces.device)
+    if dedupe not in _lib.MESHSIMP_DEDUPE:
+        raise _lib.PerfError(f"meshsimp_faces: dedupe is 'oriented', 'unoriented' or None, got {dedupe!r}")
+    if f > _lib.MESHSIMP_MAX_FACES:
+        raise _lib.PerfError(f'meshsimp_faces: {f} faces are more than 2^31 - 1')
+    ws = _simp_ws(nv, f, ws, faces.device)
+    remapped = torch.empty(f, 3, dtype=torch.int32, device=faces.device)
+    keep = torch.empty(f, dtype=torch.uint8, device=faces.device)
+    if flag is None:
+        flag = torch.empty(1, dtype=torch.int64, device=faces.device)
+    _call('perf_meshsimp_faces', _p(faces) if f else None, f, _p(vertex_cluster) if nv else None, nv, _lib.MESHSIMP_DEDUPE[dedupe], _p(remapped) if f else None,
+          _p(keep) if f else None, _p(flag), _p(ws), ws.numel() * 8, _stream())
+    return remapped, keep, flag
+
+
 def normal_composite(weights, grad, packed):
     """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
     R = packed.shape[0]

@@ -1591,6 +1591,14 @@ class NeRFScene:
         from .mesh import cull_unseen
         return cull_unseen(mesh, sup_pool, **kw)
 
+    def simplify_mesh(self, mesh, cell, **kw):
+        """mesh with one vertex per occupied cell of edge `cell` of the grid over the scene's aabb (perf_amd/mesh.py: simplify_mesh's
+        keywords) -> mesh.Mesh."""
+        from .mesh import simplify_mesh
+        aabb = [float(v) for v in self.nerf._aabb_host]
+        kw.setdefault('box', (aabb[:3], aabb[3:]))
+        return simplify_mesh(mesh, cell, **kw)[0]
+
 
 def psnr(pred, gt):
     """-10 log10(mean((pred-gt)^2))  (the reference never computes it)."""

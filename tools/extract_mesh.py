@@ -3,6 +3,7 @@
   python tools/extract_mesh.py --out room.ply [--resolution 256] [--threshold T] [--no-occupancy] [--no-colors] [--no-normals] [--sparse]
                                [--seen-by-panoramas [--visibility-tol T] [--carve] [--sup-pool pool.pt]]
                                [--min-component-faces N] [--keep-largest K] [--orientation inward|outward]
+                               [--simplify-cell H [--simplify-placement mean|member] [--simplify-dedupe oriented|unoriented|none]]
                                [--checkpoint scene.pt | --geo 3000 --app 1500] [--dtype fp16]
 
 Prints one JSON line: the counts, the threshold and the seconds of training and extraction."""
@@ -32,6 +33,12 @@ ap.add_argument('--visibility-tol', type=float, default=1 / 256, help='the band 
 ap.add_argument('--carve', action='store_true', help='with --seen-by-panoramas: also drop the faces with a vertex in observed free space, in front of a stored surface by more than '
                                                        '--visibility-tol (a skin that sits further inside the room than that is carved with the floaters: widen the band)')
 ap.add_argument('--sup-pool', default=None, help='with --checkpoint and --seen-by-panoramas: a torch.save of SupInfoPool.state_dict()')
+ap.add_argument('--simplify-cell', type=float, default=None,
+                help='after the cleaning: one vertex per occupied cell of this edge (scene units) of the grid over the scene box (vertex clustering)')
+ap.add_argument('--simplify-placement', choices=['mean', 'member'], default='mean',
+                help='the vertex of a cell: the mean of its vertices, or the one of them nearest the mean (no shrinkage)')
+ap.add_argument('--simplify-dedupe', choices=['oriented', 'unoriented', 'none'], default='oriented',
+                help='of the faces that become equal up to rotation (oriented) or as sets (unoriented: a double skin thinner than a cell) one stays')
 ap.add_argument('--checkpoint', default=None, help='a torch.save of NeRFScene.state_dict()')
 ap.add_argument('--geo', type=int, default=3000)
 ap.add_argument('--app', type=int, default=1500)
@@ -73,7 +80,10 @@ if args.seen_by_panoramas:          # first the faces no panorama saw, then the 
 seen = {'seen_vertices': len(mesh.vertices), 'seen_faces': len(mesh.faces)} if args.seen_by_panoramas else {}
 if args.min_component_faces > 0 or args.keep_largest is not None or args.orientation is not None:          # after either extraction path
     mesh = scene.clean_mesh(mesh, min_faces=args.min_component_faces, keep_largest=args.keep_largest, orientation=args.orientation)
+cleaned = {'cleaned_vertices': len(mesh.vertices), 'cleaned_faces': len(mesh.faces)} if args.simplify_cell is not None else {}
+if args.simplify_cell is not None:          # last: the cull and the cleaning have seen the mesh as it was extracted
+    mesh = scene.simplify_mesh(mesh, args.simplify_cell, placement=args.simplify_placement, dedupe=None if args.simplify_dedupe == 'none' else args.simplify_dedupe)
 torch.cuda.synchronize(); t3 = time.perf_counter()
 write_ply(args.out, mesh)
 print(json.dumps({'out': args.out, 'vertices': len(mesh.vertices), 'faces': len(mesh.faces), 'resolution': args.resolution, 'sparse': args.sparse,
-                  'threshold': args.threshold, 'extracted_vertices': extracted[0], 'extracted_faces': extracted[1], **seen, 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'clean_s': t3 - t2, 'bytes': os.path.getsize(args.out)}))
+                  'threshold': args.threshold, 'extracted_vertices': extracted[0], 'extracted_faces': extracted[1], **seen, **cleaned, 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'clean_s': t3 - t2, 'bytes': os.path.getsize(args.out)}))

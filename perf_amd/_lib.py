@@ -20,6 +20,7 @@ BRICKMESH_ABI_VERSION = 1    # PERF_BRICKMESH_ABI_VERSION of include/perf_hip_br
 MESHCC_ABI_VERSION = 1       # PERF_MESHCC_ABI_VERSION of include/perf_hip_meshcc.h (connected components of a triangle mesh)
 MESHVIS_ABI_VERSION = 1      # PERF_MESHVIS_ABI_VERSION of include/perf_hip_meshvis.h (cull the mesh faces no registered panorama saw)
 MESHSIMP_ABI_VERSION = 1     # PERF_MESHSIMP_ABI_VERSION of include/perf_hip_meshsimp.h (simplify a mesh by vertex clustering)
+MESHCOLOR_ABI_VERSION = 1    # PERF_MESHCOLOR_ABI_VERSION of include/perf_hip_meshcolor.h (colour a mesh from the registered panoramas; normals from faces)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -250,6 +251,19 @@ _SIGS_MESHSIMP = {
     'perf_meshsimp_faces': (c_int, [P, c_int64, P, c_int64, c_int32, P, P, P, P, c_int64, P]),
 }
 
+# include/perf_hip_meshcolor.h: colour a mesh's vertices from the registered panoramas, vertex normals from faces (perf_meshcolor_version)
+MESHCOLOR_MAX_VIEWS = 64             # PERF_MESHCOLOR_MAX_VIEWS
+MESHCOLOR_MAX_VERTICES = 1 << 30     # PERF_MESHCOLOR_MAX_VERTICES
+MESHCOLOR_MAX_FACES = (1 << 31) - 1  # PERF_MESHCOLOR_MAX_FACES
+MESHCOLOR_MAX_POWER = 8              # PERF_MESHCOLOR_MAX_POWER
+MESHCOLOR_SELECT = {'blend': 0, 'best': 1}                          # PERF_MESHCOLOR_SELECT_*
+_SIGS_MESHCOLOR = {
+    'perf_meshcolor_version': (c_int, []),
+    'perf_meshcolor_normal_sums': (c_int, [P, c_int64, P, c_int64, c_int32, P, P, P]),
+    'perf_meshcolor_normals': (c_int, [P, c_int64, P, P]),
+    'perf_meshcolor_blend': (c_int, [P, P, c_int64, P, P, POINTER(c_int32), c_int32, c_float, c_int32, c_int32, c_int32, P, POINTER(c_float), P, P, P, P, P]),
+}
+
 _lib = None
 
 
@@ -265,7 +279,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()) + list(_SIGS_MESHVIS.items()) + list(_SIGS_MESHSIMP.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()) + list(_SIGS_MESHVIS.items()) + list(_SIGS_MESHSIMP.items()) + list(_SIGS_MESHCOLOR.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
@@ -301,6 +315,9 @@ def load():
                         f'expects {MESHVIS_ABI_VERSION} and {MESHVIS_VIEW_BYTES}: rebuild with `python -m perf_amd.build --force`')
     if lib.perf_meshsimp_version() != MESHSIMP_ABI_VERSION:
         raise PerfError(f'{LIB_PATH} has mesh-simplification ABI version {lib.perf_meshsimp_version()}, this binding expects {MESHSIMP_ABI_VERSION}: '
+                        'rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_meshcolor_version() != MESHCOLOR_ABI_VERSION:
+        raise PerfError(f'{LIB_PATH} has mesh-colouring ABI version {lib.perf_meshcolor_version()}, this binding expects {MESHCOLOR_ABI_VERSION}: '
                         'rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):

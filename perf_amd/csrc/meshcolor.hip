@@ -1,0 +1,265 @@
+// Colour a mesh's vertices from the registered panoramas and build vertex normals from its faces (include/perf_hip_meshcolor.h):
+// normal sums (int64 atomics) -> unit normals; the blend (one launch for all views).  The look-up of the blend is vis_lookup of
+// meshvis.hip restated line for line, keeping the taps and the weights it throws away.
+#include "common.hpp"
+#include "../../include/perf_hip_meshcolor.h"
+
+namespace perf {
+
+constexpr int kColGroup = 256;               // items of one workgroup: one per thread
+constexpr int kColViewWords = sizeof(perf_meshvis_view) / 4;
+static_assert(sizeof(perf_meshvis_view) == 64 && alignof(perf_meshvis_view) == 8, "the view descriptor is 64 bytes");
+static_assert(PERF_MESHCOLOR_MAX_VIEWS == PERF_MESHVIS_MAX_VIEWS, "a vertex has one bit per view in a 64-bit word");
+
+// ---- stage A ----------------------------------------------------------------------------------------------------------------------------
+// scale = 2^s, exact; a face whose scaled normal is not finite or reaches 2^62 contributes nothing
+__global__ void __launch_bounds__(kColGroup) meshcolor_normal_sums_kernel(const float* __restrict__ vertices, int64_t n_vertices, const int32_t* __restrict__ faces,
+                                                                          int64_t n_faces, double scale, unsigned long long* __restrict__ acc,
+                                                                          unsigned long long* __restrict__ first_bad) {
+#pragma clang fp contract(off)
+    const int64_t f = (int64_t)blockIdx.x * kColGroup + threadIdx.x;
+    if (f >= n_faces) return;
+    const int32_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+    if (!(a >= 0 && a < n_vertices && b >= 0 && b < n_vertices && c >= 0 && c < n_vertices)) {
+        atomicMin(first_bad, (unsigned long long)f);
+        return;
+    }
+    const double ax = vertices[3 * (int64_t)a], ay = vertices[3 * (int64_t)a + 1], az = vertices[3 * (int64_t)a + 2];
+    const double e1x = (double)vertices[3 * (int64_t)b] - ax, e1y = (double)vertices[3 * (int64_t)b + 1] - ay, e1z = (double)vertices[3 * (int64_t)b + 2] - az;
+    const double e2x = (double)vertices[3 * (int64_t)c] - ax, e2y = (double)vertices[3 * (int64_t)c + 1] - ay, e2z = (double)vertices[3 * (int64_t)c + 2] - az;
+    const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    const double sx = nx * scale, sy = ny * scale, sz = nz * scale;
+    const double kTop = 4611686018427387904.0;          // 2^62
+    if (!(fabs(sx) < kTop && fabs(sy) < kTop && fabs(sz) < kTop)) return;          // (a NaN fails every comparison)
+    const long long q[3] = {llrint(sx), llrint(sy), llrint(sz)};
+    const int32_t abc[3] = {a, b, c};
+#pragma unroll
+    for (int v = 0; v < 3; ++v)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (q[k] != 0) atomicAdd(acc + 3 * (int64_t)abc[v] + k, (unsigned long long)q[k]);          // (two's complement: the signed sum)
+}
+
+__global__ void __launch_bounds__(kColGroup) meshcolor_normals_kernel(const long long* __restrict__ acc, int64_t n_vertices, float* __restrict__ normals) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * kColGroup + threadIdx.x;
+    if (i >= n_vertices) return;
+    const double ax = (double)acc[3 * i], ay = (double)acc[3 * i + 1], az = (double)acc[3 * i + 2];
+    const double len = sqrt((ax * ax + ay * ay) + az * az);
+    const bool none = len == 0.0;
+    normals[3 * i] = none ? 0.0f : (float)(ax / len);
+    normals[3 * i + 1] = none ? 0.0f : (float)(ay / len);
+    normals[3 * i + 2] = none ? 0.0f : (float)(az / len);
+}
+
+// ---- stage B ----------------------------------------------------------------------------------------------------------------------------
+// what the look-up of one point in one view leaves: the four taps (element offsets y * w + x, -1 where the index test fails) and their weights
+struct ColTaps {
+    int64_t at[4];          // nw, ne, sw, se
+    float w[4];
+};
+
+// dist and proj of one point in one view: vis_lookup's lines (meshvis.hip), in its order
+__device__ __forceinline__ void col_lookup(float x, float y, float z, const perf_meshvis_view& pf, float& dist_out, float& proj_out, ColTaps& taps) {
+    const float px = sub_rn(x, pf.t[0]), py = sub_rn(y, pf.t[1]), pz = sub_rn(z, pf.t[2]);
+    float l[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) l[a] = add_rn(add_rn(mul_rn(pf.rt[3 * a], px), mul_rn(pf.rt[3 * a + 1], py)), mul_rn(pf.rt[3 * a + 2], pz));
+    const float dist = sqrtf(add_rn(add_rn(mul_rn(l[0], l[0]), mul_rn(l[1], l[1])), mul_rn(l[2], l[2])));
+    float d[3] = {__fdiv_rn(l[0], dist), __fdiv_rn(l[1], dist), __fdiv_rn(l[2], dist)};
+    const float nn = sqrtf(add_rn(add_rn(mul_rn(d[0], d[0]), mul_rn(d[1], d[1])), mul_rn(d[2], d[2])));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) d[a] = __fdiv_rn(d[a], nn);
+    const float kPi = 3.14159265358979323846f;
+    const float beta = asinf(d[2]), alpha = atan2f(d[1], d[0]);
+    const float row = add_rn(__fdiv_rn(-beta, kPi), 0.5f);
+    const float col = add_rn(-__fdiv_rn(alpha, mul_rn(2.0f, kPi)), 0.5f);
+    const float gx = sub_rn(mul_rn(col, 2.0f), 1.0f), gy = sub_rn(mul_rn(row, 2.0f), 1.0f);
+    const int32_t h = pf.height, w = pf.width;
+    float ix = __fdiv_rn(sub_rn(mul_rn(add_rn(gx, 1.0f), (float)w), 1.0f), 2.0f);
+    float iy = __fdiv_rn(sub_rn(mul_rn(add_rn(gy, 1.0f), (float)h), 1.0f), 2.0f);
+    ix = fminf(fmaxf(ix, 0.0f), (float)(w - 1));            // (a NaN becomes 0: fmaxf returns the other operand)
+    iy = fminf(fmaxf(iy, 0.0f), (float)(h - 1));
+    const float fx0 = floorf(ix), fy0 = floorf(iy);
+    const int x0 = (int)fx0, y0 = (int)fy0;
+    const int x1 = x0 + 1, y1 = y0 + 1;
+    const float wx1 = sub_rn(ix, fx0), wy1 = sub_rn(iy, fy0), wx0 = sub_rn(1.0f, wx1), wy0 = sub_rn(1.0f, wy1);
+    const float* __restrict__ dmap = pf.distance_map;
+    auto where = [&](int yy, int xx) { return (yy >= 0 && yy < h && xx >= 0 && xx < w) ? (int64_t)yy * w + xx : (int64_t)-1; };
+    taps.at[0] = where(y0, x0); taps.at[1] = where(y0, x1); taps.at[2] = where(y1, x0); taps.at[3] = where(y1, x1);
+    taps.w[0] = mul_rn(wx0, wy0); taps.w[1] = mul_rn(wx1, wy0); taps.w[2] = mul_rn(wx0, wy1); taps.w[3] = mul_rn(wx1, wy1);
+    auto at = [&](int t) { return taps.at[t] >= 0 ? dmap[taps.at[t]] : 0.0f; };
+    float proj = mul_rn(at(0), taps.w[0]);
+    proj = add_rn(proj, mul_rn(at(1), taps.w[1]));
+    proj = add_rn(proj, mul_rn(at(2), taps.w[2]));
+    proj = add_rn(proj, mul_rn(at(3), taps.w[3]));
+    dist_out = dist;
+    proj_out = proj;
+}
+
+// the same four-tap accumulation over one channel of a colour map [H, W, 3]
+__device__ __forceinline__ float col_sample(const float* __restrict__ cmap, const ColTaps& taps, int channel) {
+    auto at = [&](int t) { return taps.at[t] >= 0 ? cmap[3 * taps.at[t] + channel] : 0.0f; };
+    float c = mul_rn(at(0), taps.w[0]);
+    c = add_rn(c, mul_rn(at(1), taps.w[1]));
+    c = add_rn(c, mul_rn(at(2), taps.w[2]));
+    c = add_rn(c, mul_rn(at(3), taps.w[3]));
+    return c;
+}
+
+// A workgroup stages its 256 vertices (and, with facing, their normals), the views' descriptors and the colour maps' pointers in LDS; a
+// thread then loops over the views.  All 256 threads arrive at the barrier.
+__global__ void __launch_bounds__(kColGroup) meshcolor_blend_kernel(const float* __restrict__ vertices, const float* __restrict__ normals, int64_t n_vertices,
+                                                                    const perf_meshvis_view* __restrict__ views, const float* const* __restrict__ color_maps,
+                                                                    int32_t n_views, float tol, int32_t facing, int32_t power, int32_t select,
+                                                                    const float* __restrict__ fallback, float fill_r, float fill_g, float fill_b,
+                                                                    float* __restrict__ colors, float* __restrict__ weight, unsigned long long* __restrict__ used_bits,
+                                                                    int8_t* __restrict__ best_view) {
+#pragma clang fp contract(off)
+    __shared__ perf_meshvis_view view[PERF_MESHCOLOR_MAX_VIEWS];
+    __shared__ const float* cmap[PERF_MESHCOLOR_MAX_VIEWS];
+    __shared__ float xyz[3 * kColGroup];
+    __shared__ float nrm[3 * kColGroup];
+    const int64_t first = (int64_t)blockIdx.x * kColGroup;
+    const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(views);
+    uint32_t* staged = reinterpret_cast<uint32_t*>(view);
+    for (int k = threadIdx.x; k < n_views * kColViewWords; k += kColGroup) staged[k] = words[k];
+    for (int k = threadIdx.x; k < n_views; k += kColGroup) cmap[k] = color_maps[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int64_t at = 3 * first + k * kColGroup + threadIdx.x;
+        xyz[k * kColGroup + threadIdx.x] = at < 3 * n_vertices ? vertices[at] : 0.0f;
+        nrm[k * kColGroup + threadIdx.x] = facing && at < 3 * n_vertices ? normals[at] : 0.0f;
+    }
+    __syncthreads();
+    const int64_t i = first + threadIdx.x;
+    if (i >= n_vertices) return;
+    const float x = xyz[3 * threadIdx.x], y = xyz[3 * threadIdx.x + 1], z = xyz[3 * threadIdx.x + 2];
+    const double Nx = nrm[3 * threadIdx.x], Ny = nrm[3 * threadIdx.x + 1], Nz = nrm[3 * threadIdx.x + 2];
+    const double nlen = sqrt((Nx * Nx + Ny * Ny) + Nz * Nz);
+    unsigned long long used = 0;
+    double num[3] = {0.0, 0.0, 0.0}, den = 0.0, best_w = 0.0;
+    float best_c[3] = {0.0f, 0.0f, 0.0f};
+    int best_k = -1;
+    for (int k = 0; k < n_views; ++k) {
+        float dist, proj;
+        ColTaps taps;
+        col_lookup(x, y, z, view[k], dist, proj, taps);
+        if (!(dist < add_rn(proj, tol))) continue;
+        if (!(dist > 0.0f && dist <= 3.4028234663852886e38f)) continue;
+        const double d2 = (double)dist * (double)dist;
+        double w = 1.0 / d2;
+        if (facing) {
+            const double gx = (double)view[k].t[0] - (double)x, gy = (double)view[k].t[1] - (double)y, gz = (double)view[k].t[2] - (double)z;
+            const double s = (Nx * gx + Ny * gy) + Nz * gz;
+            if (!(s > 0.0)) continue;
+            const double c = s / (nlen * sqrt((gx * gx + gy * gy) + gz * gz));
+            double cp = c;
+            for (int e = 1; e < power; ++e) cp = cp * c;
+            w = cp / d2;
+        }
+        if (!(w > 0.0)) continue;
+        used |= 1ull << k;
+        const float* __restrict__ m = cmap[k];
+        const float c0 = col_sample(m, taps, 0), c1 = col_sample(m, taps, 1), c2 = col_sample(m, taps, 2);
+        if (select == PERF_MESHCOLOR_SELECT_BEST) {
+            if (best_k < 0 || w > best_w) { best_k = k; best_w = w; best_c[0] = c0; best_c[1] = c1; best_c[2] = c2; }
+        } else {
+            num[0] = num[0] + w * (double)c0; num[1] = num[1] + w * (double)c1; num[2] = num[2] + w * (double)c2;
+            den = den + w;
+        }
+    }
+    float out[3], wt = 0.0f;
+    if (used == 0) {
+        out[0] = fallback ? fallback[3 * i] : fill_r; out[1] = fallback ? fallback[3 * i + 1] : fill_g; out[2] = fallback ? fallback[3 * i + 2] : fill_b;
+    } else if (select == PERF_MESHCOLOR_SELECT_BEST) {
+        out[0] = best_c[0]; out[1] = best_c[1]; out[2] = best_c[2];
+        wt = (float)best_w;
+    } else {
+        out[0] = (float)(num[0] / den); out[1] = (float)(num[1] / den); out[2] = (float)(num[2] / den);
+        wt = (float)den;
+    }
+    colors[3 * i] = out[0]; colors[3 * i + 1] = out[1]; colors[3 * i + 2] = out[2];
+    weight[i] = wt;
+    used_bits[i] = used;
+    best_view[i] = (int8_t)best_k;
+}
+
+// ---- the checks of the entry points -------------------------------------------------------------------------------------------------------
+static int col_counts_check(const char* who, int64_t n_vertices, int64_t n_faces) {
+    PERF_REQUIRE(n_vertices >= 0, "%s: a negative number of vertices (%lld)", who, (long long)n_vertices);
+    PERF_REQUIRE(n_faces >= 0, "%s: a negative number of faces (%lld)", who, (long long)n_faces);
+    PERF_REQUIRE(n_vertices <= PERF_MESHCOLOR_MAX_VERTICES, "%s: %lld vertices are more than 2^30 (vertex indices are int32)", who, (long long)n_vertices);
+    PERF_REQUIRE(n_faces <= PERF_MESHCOLOR_MAX_FACES, "%s: %lld faces are more than 2^31 - 1", who, (long long)n_faces);
+    return PERF_OK;
+}
+
+static inline unsigned col_groups(int64_t n) { return (unsigned)div_up(n, kColGroup); }
+
+}  // namespace perf
+
+using namespace perf;
+
+extern "C" int perf_meshcolor_version(void) { return PERF_MESHCOLOR_ABI_VERSION; }
+
+extern "C" int perf_meshcolor_normal_sums(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t scale_log2,
+                                          int64_t* acc, int64_t* bad_face_dev, void* stream) {
+    if (int rc = col_counts_check("perf_meshcolor_normal_sums", n_vertices, n_faces)) return rc;
+    PERF_REQUIRE(scale_log2 >= -200 && scale_log2 <= 200, "perf_meshcolor_normal_sums: scale_log2 %d is outside -200 .. 200", scale_log2);
+    PERF_REQUIRE(vertices || n_vertices == 0, "perf_meshcolor_normal_sums: NULL input (vertices) with vertices to sum at");
+    PERF_REQUIRE(faces || n_faces == 0, "perf_meshcolor_normal_sums: NULL input (faces) with faces to sum");
+    PERF_REQUIRE(acc || n_vertices == 0, "perf_meshcolor_normal_sums: NULL output (acc) with vertices to sum at");
+    PERF_REQUIRE(bad_face_dev, "perf_meshcolor_normal_sums: NULL output (bad_face_dev)");
+    hipStream_t st = as_stream(stream);
+    if (hipMemsetAsync(bad_face_dev, 0xff, sizeof(int64_t), st) != hipSuccess ||          // the flag: no bad face (-1, the largest unsigned)
+        (n_vertices > 0 && hipMemsetAsync(acc, 0, (size_t)n_vertices * 3 * sizeof(int64_t), st) != hipSuccess)) {
+        (void)hipGetLastError();
+        set_error("perf_meshcolor_normal_sums: clearing the sums and the flag failed");
+        return PERF_E_LAUNCH;
+    }
+    if (n_faces > 0)
+        hipLaunchKernelGGL(meshcolor_normal_sums_kernel, dim3(col_groups(n_faces)), dim3(kColGroup), 0, st, vertices, n_vertices, faces, n_faces, ldexp(1.0, scale_log2),
+                           (unsigned long long*)acc, (unsigned long long*)bad_face_dev);
+    PERF_LAUNCH_CHECK("perf_meshcolor_normal_sums");
+    return PERF_OK;
+}
+
+extern "C" int perf_meshcolor_normals(const int64_t* acc, int64_t n_vertices, float* normals, void* stream) {
+    if (int rc = col_counts_check("perf_meshcolor_normals", n_vertices, 0)) return rc;
+    PERF_REQUIRE(acc || n_vertices == 0, "perf_meshcolor_normals: NULL input (acc) with vertices");
+    PERF_REQUIRE(normals || n_vertices == 0, "perf_meshcolor_normals: NULL output (normals) with vertices");
+    if (n_vertices == 0) return PERF_OK;
+    hipLaunchKernelGGL(meshcolor_normals_kernel, dim3(col_groups(n_vertices)), dim3(kColGroup), 0, as_stream(stream), (const long long*)acc, n_vertices, normals);
+    PERF_LAUNCH_CHECK("perf_meshcolor_normals");
+    return PERF_OK;
+}
+
+extern "C" int perf_meshcolor_blend(const float* vertices, const float* normals, int64_t n_vertices, const perf_meshvis_view* views_dev,
+                                    const float* const* color_maps_dev, const int32_t* view_sizes, int32_t n_views, float tol, int32_t facing,
+                                    int32_t power, int32_t select, const float* fallback, const float* fill, float* colors, float* weight,
+                                    int64_t* used_bits, int8_t* best_view, void* stream) {
+    const char* who = "perf_meshcolor_blend";
+    if (int rc = col_counts_check(who, n_vertices, 0)) return rc;
+    PERF_REQUIRE(n_views >= 0, "%s: a negative number of views (%d)", who, n_views);
+    PERF_REQUIRE(n_views <= PERF_MESHCOLOR_MAX_VIEWS, "%s: %d views are more than 64 (a vertex has one bit per view in a 64-bit word)", who, n_views);
+    PERF_REQUIRE(tol >= 0.0f && tol <= 3.0e38f, "%s: tol %g is negative or not finite", who, (double)tol);
+    PERF_REQUIRE(facing == 0 || facing == 1, "%s: facing (%d) is 0 or 1", who, facing);
+    PERF_REQUIRE(!facing || (power >= 1 && power <= PERF_MESHCOLOR_MAX_POWER), "%s: power %d is outside 1 .. 8", who, power);
+    PERF_REQUIRE(select == PERF_MESHCOLOR_SELECT_BLEND || select == PERF_MESHCOLOR_SELECT_BEST, "%s: select %d is neither blend (0) nor best (1)", who, select);
+    PERF_REQUIRE(vertices || n_vertices == 0, "%s: NULL input (vertices) with vertices to colour", who);
+    PERF_REQUIRE(normals || !facing || n_vertices == 0, "%s: NULL input (normals) with facing", who);
+    PERF_REQUIRE((views_dev && color_maps_dev && view_sizes) || n_views == 0, "%s: NULL input (views_dev, color_maps_dev or view_sizes) with views to colour from", who);
+    PERF_REQUIRE((reinterpret_cast<uintptr_t>(views_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(color_maps_dev) & 7) == 0,
+                 "%s: views_dev and color_maps_dev must be 8-byte aligned", who);
+    PERF_REQUIRE(fill, "%s: NULL input (fill)", who);
+    PERF_REQUIRE((colors && weight && used_bits && best_view) || n_vertices == 0, "%s: NULL output (colors, weight, used_bits or best_view) with vertices to colour", who);
+    for (int k = 0; k < n_views; ++k)
+        PERF_REQUIRE(view_sizes[2 * k] >= 1 && view_sizes[2 * k + 1] >= 1, "%s: view %d has a map of %d x %d: a map dimension below 1", who, k, view_sizes[2 * k],
+                     view_sizes[2 * k + 1]);
+    if (n_vertices == 0) return PERF_OK;
+    hipLaunchKernelGGL(meshcolor_blend_kernel, dim3(col_groups(n_vertices)), dim3(kColGroup), 0, as_stream(stream), vertices, normals, n_vertices, views_dev,
+                       color_maps_dev, n_views, tol, facing, power, select, fallback, fill[0], fill[1], fill[2], colors, weight, (unsigned long long*)used_bits,
+                       best_view);
+    PERF_LAUNCH_CHECK(who);
+    return PERF_OK;
+}

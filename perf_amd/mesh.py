@@ -368,7 +368,7 @@ def cull_unseen(mesh, views, tol=1 / 256, free_tol=None, facing=True, min_views=
     """mesh without the faces no registered panorama saw: vertex_visibility -> visible_faces -> filter_faces with ONE host
     synchronisation.  It separates the skin the cameras saw from the back of the density shell where the two are ONE connected component
     (clean_mesh(orientation='inward') keeps nothing of it).  There is no occlusion test against the mesh itself, no colours are taken from
-    the panoramas, and more than 64 views are refused."""
+    the panoramas (color_from_panoramas does that, on what the cull leaves), and more than 64 views are refused."""
     _check_mesh('cull_unseen', mesh)
     v = _views('cull_unseen', views)
     visibility = vertex_visibility(mesh.vertices, v, tol, free_tol)
@@ -479,6 +479,106 @@ def simplify_mesh(mesh, cell, box=None, placement='mean', dedupe='oriented'):
     colors = mesh.colors[gather] if mesh.colors is not None else None
     normals = mesh.normals[gather] if mesh.normals is not None else None
     return Mesh(placed[kept_cluster], new_faces, colors, normals), index
+
+
+# ---- the panoramas' colours on the mesh; vertex normals from the faces (include/perf_hip_meshcolor.h) ------------------------------------
+class PanoramaColors(NamedTuple):
+    colors: torch.Tensor                         # [V, 3] fp32: the blended (or the best view's) colour; the fallback where no view passed
+    weight: torch.Tensor                         # [V] fp32: the sum of the passing views' weights (best: the best view's), 0 where none passed
+    used: torch.Tensor                           # [V] int64: bit k set iff view k's colour went into the vertex
+    best_view: torch.Tensor                      # [V] int8: select='best': the view the colour is from; -1 where none passed and under 'blend'
+
+
+class _ColorViews(NamedTuple):
+    views: _Views                                # the geometric side, as the cull takes it
+    pointers: torch.Tensor                       # [K] int64: the device array of the colour maps' pointers
+    maps: list                                   # the colour maps it points into
+
+
+def _color_views(who, views) -> _ColorViews:
+    """views: what _views takes, each with a 'color_map' [H, W, 3] of its distance map's height and width (what SupInfoPool.sup_infos
+    holds)."""
+    if isinstance(views, _ColorViews):
+        return views
+    if isinstance(views, _Views):
+        raise _lib.PerfError(f'{who}: the views carry no colour maps: pass the pool or the list of views itself')
+    infos = list(views.sup_infos if hasattr(views, 'sup_infos') else views)
+    v = _views(who, infos)
+    maps = []
+    for k, info in enumerate(infos):
+        if info.get('color_map') is None:
+            raise _lib.PerfError(f'{who}: view {k} has no color_map')
+        maps.append(info['color_map'])
+    return _ColorViews(v, *ops.meshcolor_maps(maps, v.sizes))          # (which checks them)
+
+
+def _normal_scale(box):
+    """scale_log2 of include/perf_hip_meshcolor.h for a box (lo, hi): 40 - ceil(log2(D^2)), D^2 the squared diagonal; 0 for no extent."""
+    d2 = sum((float(b) - float(a)) ** 2 for a, b in zip(*box))
+    if not math.isfinite(d2) or d2 <= 0.0:
+        return 0
+    return max(-200, min(200, 40 - math.ceil(math.log2(d2))))
+
+
+def face_normals(mesh, box=None) -> torch.Tensor:
+    """Geometric vertex normals fp32 [V, 3]: the faces' area-weighted normals summed at their vertices in fixed point (int64 atomics: no
+    floating-point atomics, so the result does not depend on the faces' order and is bit-identical from run to run), then normalised;
+    exactly 0 at a vertex no face names or whose faces cancel.  They point where the faces do: from the dense side to the empty side.
+    box = (lo, hi) bounds the vertices and sets the fixed point's scale (None: the vertices' own bounds, one more host read).  One host
+    read: the flag of a face index outside [0, V), which is refused."""
+    _check_mesh('face_normals', mesh)
+    vertices, faces = mesh.vertices.contiguous(), mesh.faces.contiguous()
+    if box is None:
+        bounds = ops.meshsimp_bounds(vertices).tolist()          # the host read-back of the six bounds
+        box = (bounds[:3], bounds[3:])
+    elif len(box) != 2 or len(box[0]) != 3 or len(box[1]) != 3:
+        raise _lib.PerfError(f'face_normals: box is (lo, hi), three values each, got {box!r}')
+    acc, flag = ops.meshcolor_normal_sums(vertices, faces, _normal_scale(box))
+    bad = int(flag.item())          # the one host synchronisation
+    if bad >= 0:
+        _raise_bad_face('face_normals', faces, bad, vertices.shape[0])
+    return ops.meshcolor_normals(acc)
+
+
+def panorama_colors(vertices, views, normals=None, tol=1 / 256, facing=True, power=2, select='blend', fallback=None, fill=(0.5, 0.5, 0.5)) -> PanoramaColors:
+    """The registered panoramas' colours at vertices fp32 [V, 3], all views in ONE launch.  View k's colour map is sampled where the
+    cull's look-up reads its distance map (the same bilinear taps), and counts iff the view saw the vertex (the depth test of
+    vertex_visibility: dist < stored + tol) and, with facing, the normal points at the view's centre.  It is weighted by
+    cos^power / dist^2 (facing) or 1 / dist^2: a panorama pixel's footprint on the surface grows as dist^2 / cos.  select='blend': the
+    weighted mean; 'best': the colour of the view with the largest weight.  Where no view passes: the fallback row [V, 3] if given, else
+    fill.  No occlusion test against the mesh itself, no texture atlas (colours are per vertex), no exposure matching between views, no
+    wrap at the seam; more than 64 views are refused.  No host read."""
+    if not torch.is_tensor(vertices) or not vertices.is_cuda:
+        raise _lib.PerfError('panorama_colors: vertices must be a CUDA tensor (there is no CPU path)')
+    if select not in _lib.MESHCOLOR_SELECT:
+        raise _lib.PerfError(f"panorama_colors: select is 'blend' or 'best', got {select!r}")
+    if facing and normals is None:
+        raise _lib.PerfError('panorama_colors: facing weights the views by the normals: pass normals, or facing=False')
+    if facing and not 1 <= int(power) <= _lib.MESHCOLOR_MAX_POWER:
+        raise _lib.PerfError(f'panorama_colors: power {power} is outside 1 .. {_lib.MESHCOLOR_MAX_POWER}')
+    cv = _color_views('panorama_colors', views)
+    return PanoramaColors(*ops.meshcolor_blend(vertices.contiguous(), normals.contiguous() if facing else None, cv.views.table, cv.views.sizes, cv.pointers, float(tol),
+                                               facing, power, select, fallback.contiguous() if fallback is not None else None, fill))
+
+
+def color_from_panoramas(mesh, views, normals='faces', **kw) -> Mesh:
+    """mesh with the panoramas' colours at its vertices (panorama_colors' keywords, and box for face_normals).  normals='faces': the
+    views are weighted by the geometric normals of face_normals; 'mesh': by mesh.normals, which must be there; with facing=False neither
+    is needed.  mesh.colors, when present, is the fallback of the vertices no view passed for.  The result keeps mesh.normals."""
+    _check_mesh('color_from_panoramas', mesh)
+    if normals not in ('faces', 'mesh'):
+        raise _lib.PerfError(f"color_from_panoramas: normals is 'faces' or 'mesh', got {normals!r}")
+    box = kw.pop('box', None)
+    weigh_by = None
+    if kw.get('facing', True):
+        if normals == 'mesh':
+            if mesh.normals is None:
+                raise _lib.PerfError("color_from_panoramas: normals='mesh' needs mesh.normals: extract them, or use normals='faces'")
+            weigh_by = mesh.normals
+        else:
+            weigh_by = face_normals(mesh, box)
+    kw.setdefault('fallback', mesh.colors)
+    return Mesh(mesh.vertices, mesh.faces, panorama_colors(mesh.vertices, views, weigh_by, **kw).colors, mesh.normals)
 
 
 def write_ply(path, mesh):

@@ -1207,6 +1207,84 @@ def meshsimp_faces(faces, vertex_cluster, dedupe='oriented', ws=None, flag=None)
     return remapped, keep, flag
 
 
+# ---- colour a mesh from the registered panoramas; vertex normals from faces (include/perf_hip_meshcolor.h) -----------------------------
+def meshcolor_normal_sums(vertices, faces, scale_log2, flag=None):
+    """The faces' area-weighted normals (double, times 2^scale_log2, rounded to int64) summed at their vertices by integer atomics
+    (perf_meshcolor_normal_sums) -> (acc int64 [V, 3], flag): flag = int64 [1] ON THE DEVICE, the smallest index of a face with an index
+    outside [0, V) or -1 (an int64 [1] view to write it into may be passed)."""
+    vertices, nv = _simp_vertices('meshcolor_normal_sums', vertices)
+    _, f = _cc_faces('meshcolor_normal_sums', faces, nv)
+    if faces.device != vertices.device:
+        raise _lib.PerfError('meshcolor_normal_sums: faces must be on the vertices\' device')
+    if f > _lib.MESHCOLOR_MAX_FACES:
+        raise _lib.PerfError(f'meshcolor_normal_sums: {f} faces are more than 2^31 - 1')
+    acc = torch.empty(nv, 3, dtype=torch.int64, device=vertices.device)
+    if flag is None:
+        flag = torch.empty(1, dtype=torch.int64, device=vertices.device)
+    _call('perf_meshcolor_normal_sums', _p(vertices) if nv else None, nv, _p(faces) if f else None, f, int(scale_log2), _p(acc) if nv else None, _p(flag), _stream())
+    return acc, flag
+
+
+def meshcolor_normals(acc):
+    """Unit normals fp32 [V, 3] of the sums of meshcolor_normal_sums, exactly 0 where a sum is (perf_meshcolor_normals)."""
+    if not torch.is_tensor(acc) or not acc.is_cuda:
+        raise _lib.PerfError('meshcolor_normals: acc must be a CUDA tensor (there is no CPU path)')
+    if acc.dtype != torch.int64 or acc.dim() != 2 or acc.shape[1] != 3 or not acc.is_contiguous():
+        raise _lib.PerfError(f'meshcolor_normals: acc must be a contiguous int64 [V, 3] tensor, got {acc.dtype} {tuple(acc.shape)}')
+    n = int(acc.shape[0])
+    normals = torch.empty(n, 3, dtype=torch.float32, device=acc.device)
+    _call('perf_meshcolor_normals', _p(acc) if n else None, n, _p(normals) if n else None, _stream())
+    return normals
+
+
+def meshcolor_maps(color_maps, sizes):
+    """The device array of the K colour maps' pointers -> (pointers int64 [K] on the device, maps: the tensors it points into, to be kept
+    alive with it).  color_maps: K CUDA [H, W, 3], converted to fp32 when they are not; sizes: the (height, width) pairs of the views' distance maps (meshvis_views), which
+    map k must have."""
+    if len(color_maps) != len(sizes):
+        raise _lib.PerfError(f'meshcolor_maps: {len(color_maps)} colour maps and {len(sizes)} views')
+    maps = []
+    for k, (m, hw) in enumerate(zip(color_maps, sizes)):
+        if not torch.is_tensor(m) or not m.is_cuda:
+            raise _lib.PerfError(f'meshcolor_maps: view {k}\'s color_map must be a CUDA tensor (there is no CPU path)')
+        if m.dim() != 3 or m.shape[2] != 3 or tuple(m.shape[:2]) != tuple(hw):
+            raise _lib.PerfError(f'meshcolor_maps: view {k}\'s color_map is {tuple(m.shape)}, its distance map {tuple(hw)}: a colour map is [H, W, 3] of its distance map\'s size')
+        maps.append(m.float().contiguous())          # (both return m itself when it already is fp32 and contiguous)
+    dev = maps[0].device if maps else torch.device('cuda')
+    return torch.tensor([m.data_ptr() for m in maps], dtype=torch.int64).to(dev), maps
+
+
+def meshcolor_blend(vertices, normals, views, sizes, map_pointers, tol, facing=True, power=2, select='blend', fallback=None, fill=(0.5, 0.5, 0.5)):
+    """(colors fp32 [V, 3], weight fp32 [V], used_bits int64 [V], best_view int8 [V]) of vertices fp32 [V, 3] against the views of
+    meshvis_views and the colour maps of meshcolor_maps by the rule of include/perf_hip_meshcolor.h: ONE launch for all views
+    (perf_meshcolor_blend).  normals fp32 [V, 3] are read only with facing; fallback fp32 [V, 3] or None."""
+    vertices, n = _simp_vertices('meshcolor_blend', vertices)
+    dev, k = vertices.device, len(sizes)
+    if tuple(views.shape) != (k, 16) or views.dtype != torch.int32 or (k and views.device != dev) or not views.is_contiguous():
+        raise _lib.PerfError(f'meshcolor_blend: views must be the contiguous int32 [{k}, 16] tensor of meshvis_views on the vertices\' device')
+    if tuple(map_pointers.shape) != (k,) or map_pointers.dtype != torch.int64 or (k and map_pointers.device != dev):
+        raise _lib.PerfError(f'meshcolor_blend: map_pointers must be the int64 [{k}] tensor of meshcolor_maps on the vertices\' device')
+    if select not in _lib.MESHCOLOR_SELECT:
+        raise _lib.PerfError(f"meshcolor_blend: select is 'blend' or 'best', got {select!r}")
+    if facing and normals is None:
+        raise _lib.PerfError('meshcolor_blend: facing needs normals')
+    normals = _cc_vertices('meshcolor_blend', normals, n, dev) if facing else None
+    fallback = _cc_vertices('meshcolor_blend', fallback, n, dev)
+    fill3 = [float(v) for v in fill]
+    if len(fill3) != 3:
+        raise _lib.PerfError('meshcolor_blend: fill holds three values')
+    colors = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    weight = torch.empty(n, dtype=torch.float32, device=dev)
+    used = torch.empty(n, dtype=torch.int64, device=dev)
+    best = torch.empty(n, dtype=torch.int8, device=dev)
+    flat = (ctypes.c_int32 * (2 * k))(*[v for hw in sizes for v in hw]) if k else None
+    _call('perf_meshcolor_blend', _p(vertices) if n else None, _p(normals) if normals is not None and n else None, n, _p(views) if k else None,
+          _p(map_pointers) if k else None, flat, k, float(tol), int(bool(facing)), int(power), _lib.MESHCOLOR_SELECT[select],
+          _p(fallback) if fallback is not None and n else None, (ctypes.c_float * 3)(*fill3), _p(colors) if n else None, _p(weight) if n else None,
+          _p(used) if n else None, _p(best) if n else None, _stream())
+    return colors, weight, used, best
+
+
 def normal_composite(weights, grad, packed):
     """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
     R = packed.shape[0]

@@ -1599,6 +1599,14 @@ class NeRFScene:
         kw.setdefault('box', (aabb[:3], aabb[3:]))
         return simplify_mesh(mesh, cell, **kw)[0]
 
+    def color_mesh_from_panoramas(self, mesh, sup_pool, **kw):
+        """mesh with the colours of sup_pool's registered panoramas at its vertices, the field's colours where no panorama saw a vertex
+        (perf_amd/mesh.py: color_from_panoramas' keywords) -> mesh.Mesh."""
+        from .mesh import color_from_panoramas
+        aabb = [float(v) for v in self.nerf._aabb_host]
+        kw.setdefault('box', (aabb[:3], aabb[3:]))
+        return color_from_panoramas(mesh, sup_pool, **kw)
+
 
 def psnr(pred, gt):
     """-10 log10(mean((pred-gt)^2))  (the reference never computes it)."""

@@ -4,6 +4,7 @@
                                [--seen-by-panoramas [--visibility-tol T] [--carve] [--sup-pool pool.pt]]
                                [--min-component-faces N] [--keep-largest K] [--orientation inward|outward]
                                [--simplify-cell H [--simplify-placement mean|member] [--simplify-dedupe oriented|unoriented|none]]
+                               [--colors-from-panoramas [--color-select blend|best] [--color-power N] [--sup-pool pool.pt]]
                                [--checkpoint scene.pt | --geo 3000 --app 1500] [--dtype fp16]
 
 Prints one JSON line: the counts, the threshold and the seconds of training and extraction."""
@@ -39,6 +40,11 @@ ap.add_argument('--simplify-placement', choices=['mean', 'member'], default='mea
                 help='the vertex of a cell: the mean of its vertices, or the one of them nearest the mean (no shrinkage)')
 ap.add_argument('--simplify-dedupe', choices=['oriented', 'unoriented', 'none'], default='oriented',
                 help='of the faces that become equal up to rotation (oriented) or as sets (unoriented: a double skin thinner than a cell) one stays')
+ap.add_argument('--colors-from-panoramas', action='store_true',
+                help='after the cull and the cleaning, before the simplification: the vertex colours are the registered panoramas\' own, weighted by '
+                     'cos^N / dist^2 over the views that saw a vertex (the field\'s colours stay where none did)')
+ap.add_argument('--color-select', choices=['blend', 'best'], default='blend', help='with --colors-from-panoramas: the weighted mean of the views, or the best view alone')
+ap.add_argument('--color-power', type=int, default=2, help='with --colors-from-panoramas: the power N of the incidence cosine, 1 .. 8')
 ap.add_argument('--checkpoint', default=None, help='a torch.save of NeRFScene.state_dict()')
 ap.add_argument('--geo', type=int, default=3000)
 ap.add_argument('--app', type=int, default=1500)
@@ -50,18 +56,19 @@ torch.manual_seed(0); np.random.seed(0)
 scene = NeRFScene(dtype=args.dtype)
 t0 = time.perf_counter()
 views = None          # --seen-by-panoramas: the registered panoramas the mesh is tested against
-if args.seen_by_panoramas and args.checkpoint and not args.sup_pool:
-    ap.error('--seen-by-panoramas with --checkpoint needs the panoramas: --sup-pool FILE, a torch.save of SupInfoPool.state_dict()')
+with_views = args.seen_by_panoramas or args.colors_from_panoramas
+if with_views and args.checkpoint and not args.sup_pool:
+    ap.error('--seen-by-panoramas and --colors-from-panoramas with --checkpoint need the panoramas: --sup-pool FILE, a torch.save of SupInfoPool.state_dict()')
 if args.checkpoint:
     scene.load_state_dict(torch.load(args.checkpoint, map_location='cuda'))
-    if args.seen_by_panoramas:
+    if with_views:
         views = SupInfoPool(); views.load_state_dict(torch.load(args.sup_pool, map_location='cuda'))
 else:
     rays = gen_pano_rays(torch.eye(4), 256, 512)
     dist, rgb = synthetic.room(rays.d)
     pool = SupInfoPool(); pool.register_rays(rays.o, rays.d, rgb, dist)
-    if args.seen_by_panoramas:          # (register_rays leaves no sup_infos: the view is the pose and the distance map the scene trains on)
-        views = [{'pose': torch.eye(4), 'distance_map': dist.reshape(256, 512).float().to('cuda')}]
+    if with_views:          # (register_rays leaves no sup_infos: the view is the pose, the distance map the scene trains on and its colours)
+        views = [{'pose': torch.eye(4), 'distance_map': dist.reshape(256, 512).float().to('cuda'), 'color_map': rgb.reshape(256, 512, 3).float().to('cuda')}]
     scene.train_conf.pixel_loss_batch_size = args.batch
     scene.train_one_episode(pool, args.geo, args.app)
 scene.set_eval()
@@ -80,6 +87,8 @@ if args.seen_by_panoramas:          # first the faces no panorama saw, then the 
 seen = {'seen_vertices': len(mesh.vertices), 'seen_faces': len(mesh.faces)} if args.seen_by_panoramas else {}
 if args.min_component_faces > 0 or args.keep_largest is not None or args.orientation is not None:          # after either extraction path
     mesh = scene.clean_mesh(mesh, min_faces=args.min_component_faces, keep_largest=args.keep_largest, orientation=args.orientation)
+if args.colors_from_panoramas:          # on the fine vertices, which lie on the surface the depth test was made for; the simplification carries the colours
+    mesh = scene.color_mesh_from_panoramas(mesh, views, tol=args.visibility_tol, select=args.color_select, power=args.color_power)
 cleaned = {'cleaned_vertices': len(mesh.vertices), 'cleaned_faces': len(mesh.faces)} if args.simplify_cell is not None else {}
 if args.simplify_cell is not None:          # last: the cull and the cleaning have seen the mesh as it was extracted
     mesh = scene.simplify_mesh(mesh, args.simplify_cell, placement=args.simplify_placement, dedupe=None if args.simplify_dedupe == 'none' else args.simplify_dedupe)

@@ -21,6 +21,7 @@ MESHCC_ABI_VERSION = 1       # PERF_MESHCC_ABI_VERSION of include/perf_hip_meshc
 MESHVIS_ABI_VERSION = 1      # PERF_MESHVIS_ABI_VERSION of include/perf_hip_meshvis.h (cull the mesh faces no registered panorama saw)
 MESHSIMP_ABI_VERSION = 1     # PERF_MESHSIMP_ABI_VERSION of include/perf_hip_meshsimp.h (simplify a mesh by vertex clustering)
 MESHCOLOR_ABI_VERSION = 1    # PERF_MESHCOLOR_ABI_VERSION of include/perf_hip_meshcolor.h (colour a mesh from the registered panoramas; normals from faces)
+MESHRAY_ABI_VERSION = 1      # PERF_MESHRAY_ABI_VERSION of include/perf_hip_meshray.h (rays against a mesh on a uniform grid: closest hit, any hit, occlusion)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -264,6 +265,21 @@ _SIGS_MESHCOLOR = {
     'perf_meshcolor_blend': (c_int, [P, P, c_int64, P, P, POINTER(c_int32), c_int32, c_float, c_int32, c_int32, c_int32, P, POINTER(c_float), P, P, P, P, P]),
 }
 
+# include/perf_hip_meshray.h: rays against a triangle mesh on a uniform grid: closest hit, any hit, segment occlusion (perf_meshray_version)
+MESHRAY_MAX_CELLS = 1 << 24          # PERF_MESHRAY_MAX_CELLS
+MESHRAY_MAX_VIEWS = 64               # PERF_MESHRAY_MAX_VIEWS
+MESHRAY_MAX_VERTICES = 1 << 30       # PERF_MESHRAY_MAX_VERTICES
+MESHRAY_MAX_FACES = (1 << 31) - 1    # PERF_MESHRAY_MAX_FACES
+_RAY_MESH = [P, c_int64, P, c_int64]                                  # vertices, n_vertices, faces, n_faces
+_RAY_BOX = [POINTER(c_float), c_float, POINTER(c_int32)]              # origin, cell, dims
+_SIGS_MESHRAY = {
+    'perf_meshray_version': (c_int, []),
+    'perf_meshray_grid_count': (c_int, _RAY_MESH + _RAY_BOX + [P, P, P]),
+    'perf_meshray_grid_write': (c_int, _RAY_MESH + _RAY_BOX + [P, P, c_int64, P, c_int64, P]),
+    'perf_meshray_cast': (c_int, _RAY_MESH + _RAY_BOX + [P, P, c_int64, P, P, c_int64, c_float, c_float, c_int32, P, P, P, P, P, P]),
+    'perf_meshray_occluded': (c_int, _RAY_MESH + _RAY_BOX + [P, P, c_int64, P, c_int32, P, P, P]),
+}
+
 _lib = None
 
 
@@ -279,7 +295,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()) + list(_SIGS_MESHVIS.items()) + list(_SIGS_MESHSIMP.items()) + list(_SIGS_MESHCOLOR.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()) + list(_SIGS_MESHVIS.items()) + list(_SIGS_MESHSIMP.items()) + list(_SIGS_MESHCOLOR.items()) + list(_SIGS_MESHRAY.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
@@ -318,6 +334,9 @@ def load():
                         'rebuild with `python -m perf_amd.build --force`')
     if lib.perf_meshcolor_version() != MESHCOLOR_ABI_VERSION:
         raise PerfError(f'{LIB_PATH} has mesh-colouring ABI version {lib.perf_meshcolor_version()}, this binding expects {MESHCOLOR_ABI_VERSION}: '
+                        'rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_meshray_version() != MESHRAY_ABI_VERSION:
+        raise PerfError(f'{LIB_PATH} has mesh ray-casting ABI version {lib.perf_meshray_version()}, this binding expects {MESHRAY_ABI_VERSION}: '
                         'rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):

@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libperf_hip.so')
 # (the MLP kernels are instantiated in six units of their own: one unit took 65 s, the longest of them now takes ~15 s)
 SOURCES = ['mlp_bwd_bf16_nh2.hip', 'mlp_bwd_fp16_nh2.hip', 'mlp_bwd_bf16_nh1.hip', 'mlp_bwd_fp16_nh1.hip', 'mlp_fwd_bf16.hip', 'mlp_fwd_fp16.hip', 'mlp_fwd_rows.hip',
-           'hashgrid_bwd.hip', 'hashgrid_bwd_lines.hip', 'hashgrid_fwd.hip', 'hashgrid_aux.hip', 'march.hip', 'misc.hip', 'composite.hip', 'mlp.hip', 'visibility.hip', 'field_normal.hip', 'field_normal_bwd.hip', 'sphere_field.hip', 'hashgrid_pair.hip', 'joint_align.hip', 'mesh.hip', 'brickmesh.hip', 'meshcc.hip', 'meshvis.hip', 'meshsimp.hip', 'meshcolor.hip']
+           'hashgrid_bwd.hip', 'hashgrid_bwd_lines.hip', 'hashgrid_fwd.hip', 'hashgrid_aux.hip', 'march.hip', 'misc.hip', 'composite.hip', 'mlp.hip', 'visibility.hip', 'field_normal.hip', 'field_normal_bwd.hip', 'sphere_field.hip', 'hashgrid_pair.hip', 'joint_align.hip', 'mesh.hip', 'brickmesh.hip', 'meshcc.hip', 'meshvis.hip', 'meshsimp.hip', 'meshcolor.hip', 'meshray.hip']
 HEADERS = ['common.hpp', 'grid_device.hpp', 'grid_fixed_point.hpp', 'mlp_reduce_device.hpp', 'step_book_device.hpp', 'mlp_device.hpp', 'field_normal_device.hpp', 'mesh_device.hpp']
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs (no v_accvgpr_read per accumulator register before the epilogues)
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
@@ -25,7 +25,7 @@ def _newer(target, deps):
 
 def build(force=False, verbose=False):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(HERE, '..', 'include', h) for h in ('perf_hip.h', 'perf_hip_ext.h', 'perf_hip_sphere.h', 'perf_hip_pair.h', 'perf_hip_joint.h', 'perf_hip_mesh.h', 'perf_hip_brickmesh.h', 'perf_hip_meshcc.h', 'perf_hip_meshvis.h', 'perf_hip_meshsimp.h', 'perf_hip_meshcolor.h')]
+    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(HERE, '..', 'include', h) for h in ('perf_hip.h', 'perf_hip_ext.h', 'perf_hip_sphere.h', 'perf_hip_pair.h', 'perf_hip_joint.h', 'perf_hip_mesh.h', 'perf_hip_brickmesh.h', 'perf_hip_meshcc.h', 'perf_hip_meshvis.h', 'perf_hip_meshsimp.h', 'perf_hip_meshcolor.h', 'perf_hip_meshray.h')]
     deps = [os.path.join(CSRC, s) for s in SOURCES] + hdrs
     if not force and _newer(LIB, deps):
         return LIB
@@ -42,6 +42,7 @@ def build(force=False, verbose=False):
         own = [h for h in own if src == 'meshsimp.hip' or not h.endswith('perf_hip_meshsimp.h')]       # (and the vertex-clustering unit)
         own = [h for h in own if src == 'meshcolor.hip' or not h.endswith('perf_hip_meshcolor.h')]       # (and the colouring unit,
         own = own + [h for h in hdrs if src == 'meshcolor.hip' and h.endswith('perf_hip_meshvis.h')]       # whose header includes the cull's for the view descriptor)
+        own = [h for h in own if src == 'meshray.hip' or not h.endswith('perf_hip_meshray.h')]       # (and the ray-casting unit)
         own = [h for h in own if src in ('mesh.hip', 'brickmesh.hip') or not h.endswith('mesh_device.hpp')]       # (the vertex arithmetic the two share)
         if not force and _newer(obj, [os.path.join(CSRC, src)] + own):
             return obj

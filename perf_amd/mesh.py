@@ -581,6 +581,127 @@ def color_from_panoramas(mesh, views, normals='faces', **kw) -> Mesh:
     return Mesh(mesh.vertices, mesh.faces, panorama_colors(mesh.vertices, views, weigh_by, **kw).colors, mesh.normals)
 
 
+# ---- rays against the mesh itself: closest hit, any hit, occlusion-aware cull (include/perf_hip_meshray.h) ------------------------------
+class RayGrid(NamedTuple):
+    origin: tuple                                # 3 floats: the fp32 corner of the box
+    cell: float                                  # the fp32 cell edge; the margin of the lists is cell / 8
+    dims: tuple                                  # (nx, ny, nz)
+    offsets: torch.Tensor                        # [nx * ny * nz] int32: where each cell's faces begin in refs, cell (i, j, k) at (i ny + j) nz + k
+    refs: torch.Tensor                           # [R] int32: face indices, cell by cell, in no particular order inside a cell
+    n_vertices: int                              # of the mesh the grid was built of
+    n_faces: int
+    bad_face: int                                # the smallest index of a face that can never be hit (an index outside [0, V), a vertex that is not finite), or -1
+
+
+class RayHits(NamedTuple):
+    t: torch.Tensor                              # [N] fp32: the ray parameter of the closest hit, +inf where nothing is hit
+    face: torch.Tensor                           # [N] int32: the face hit, -1 where none
+    u: torch.Tensor                              # [N] fp32: the hit point is (1 - u - v) a + u b + v c; 0 where nothing is hit
+    v: torch.Tensor                              # [N] fp32
+
+
+def _default_cells(n_faces):
+    """Cells along the longest axis of the box: round(cbrt(2 F)) in 1 .. 255 -- about two cells per face over a cubic box, a cell about
+    two lattice spacings wide for a surface-nets room (F ~ 12 n^2 at resolution n), and (255 + 1)^3 = 2^24 cells at the most."""
+    return min(255, max(1, round((2.0 * max(int(n_faces), 1)) ** (1.0 / 3.0))))
+
+
+def build_ray_grid(mesh, cell=None) -> RayGrid:
+    """The uniform grid the ray queries walk: the box is the bounds of the mesh's finite vertices widened by the margin cell / 8, so every
+    finite vertex lies inside and the walked results equal brute force over all faces unconditionally (the grid only skips faces that
+    cannot hit).  cell None: the longest edge of the bounds over round(cbrt(2 F)) (at most 255).  Memory: 4 bytes per cell of counts
+    (freed on return), 4 per cell of offsets and 4 per reference, under the cap of 2^24 cells (64 MiB each); a surface-nets room lists a face
+    3.7 times at 256^3 and 2.7 times at 1024^3 at the default cell.  Count -> scan -> write with two host reads: the six bounds, then the reference count with the
+    flag of a face that can never be hit (kept in RayGrid.bad_face, not refused: such a face is listed nowhere)."""
+    _check_mesh('build_ray_grid', mesh)
+    vertices, faces = mesh.vertices.contiguous(), mesh.faces.contiguous()
+    bounds = ops.meshsimp_bounds(vertices).tolist()          # the host read-back of the six bounds
+    if not all(math.isfinite(b) for b in bounds):            # (no finite coordinate along an axis: nothing can be hit)
+        bounds = [0.0] * 6
+    lo, hi = bounds[:3], bounds[3:]
+    if cell is None:
+        longest = max(b - a for a, b in zip(lo, hi))
+        cell = longest / _default_cells(faces.shape[0]) if longest > 0 else 1.0
+    h = float(np.float32(cell))
+    if not math.isfinite(h) or h <= 0:
+        raise _lib.PerfError(f'build_ray_grid: the cell edge {cell!r} is not positive or not finite')
+    m = h / 8.0
+    origin = []
+    for a in lo:
+        o = np.float32(a - m)
+        while float(o) > a - m:                             # (the fp32 corner never lies above lo - m)
+            o = np.nextafter(o, np.float32(-np.inf))
+        origin.append(float(o))
+    dims = [int(math.floor((b + m - o) / h)) + 1 for o, b in zip(origin, hi)]
+    if dims[0] * dims[1] * dims[2] > _lib.MESHRAY_MAX_CELLS:
+        raise _lib.PerfError(f'build_ray_grid: a cell of {h} makes {dims} cells over the mesh\'s bounds, more than 2^24: choose a larger cell')
+    counts, flag = ops.meshray_grid_count(vertices, faces, origin, h, dims)
+    offsets, total = ops.exclusive_scan_i32(counts)
+    n_refs, bad = (int(v) for v in torch.cat([total, flag]).tolist())          # the host read of the reference count, with the flag
+    if n_refs >= 1 << 31:
+        raise _lib.PerfError(f'build_ray_grid: {n_refs} references are 2^31 or more: choose a larger cell')
+    refs = ops.meshray_grid_write(vertices, faces, origin, h, dims, counts, offsets, n_refs)
+    return RayGrid(tuple(origin), h, tuple(dims), offsets, refs, int(vertices.shape[0]), int(faces.shape[0]), bad)
+
+
+def _check_grid(who, mesh, grid):
+    _check_mesh(who, mesh)
+    if not isinstance(grid, RayGrid):
+        raise _lib.PerfError(f'{who}: grid is the RayGrid of build_ray_grid, got {type(grid).__name__}')
+    if grid.n_vertices != int(mesh.vertices.shape[0]) or grid.n_faces != int(mesh.faces.shape[0]):
+        raise _lib.PerfError(f'{who}: the grid was built of a mesh of {grid.n_vertices} vertices and {grid.n_faces} faces, this one has {int(mesh.vertices.shape[0])} and '
+                             f'{int(mesh.faces.shape[0])}')
+    return mesh.vertices.contiguous(), mesh.faces.contiguous()
+
+
+def cast_rays(mesh, grid, origins, directions, t_min=0.0, t_max=float('inf'), any_hit=False):
+    """Rays origins + t directions (CUDA fp32 [N, 3] each; directions need not be unit) against the mesh: the closest hit by the rule of
+    include/perf_hip_meshray.h -- double Moeller-Trumbore per face, two-sided, t_min <= t <= t_max, the lexicographic minimum of (t, face
+    index) over ALL faces -> RayHits; any_hit: uint8 [N], 1 iff some face is hit.  The grid only skips faces that cannot hit: the result does
+    not depend on its cell, and is bit-identical from run to run.  Not watertight along shared edges.  No host read."""
+    vertices, faces = _check_grid('cast_rays', mesh, grid)
+    for name, t in (('origins', origins), ('directions', directions)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.PerfError(f'cast_rays: {name} must be a CUDA tensor (there is no CPU path)')
+    if math.isnan(float(t_min)) or math.isnan(float(t_max)):
+        raise _lib.PerfError(f'cast_rays: t_min ({t_min}) or t_max ({t_max}) is NaN')
+    out = ops.meshray_cast(vertices, faces, grid.origin, grid.cell, grid.dims, grid.offsets, grid.refs, origins.contiguous(), directions.contiguous(), t_min, t_max, any_hit)
+    return out if any_hit else RayHits(*out)
+
+
+def vertex_occlusion(mesh, grid, views, visibility) -> torch.Tensor:
+    """int64 [V]: bit k is set iff bit k of visibility.visible is set and the mesh itself cuts the segment from the vertex to view k's centre
+    (a strict 0 < t < 1; the faces that name the vertex are not tested).  views: what vertex_visibility takes; at most 64.  No host read."""
+    vertices, faces = _check_grid('vertex_occlusion', mesh, grid)
+    v = _views('vertex_occlusion', views)
+    if visibility.n_views != len(v.sizes):
+        raise _lib.PerfError(f'vertex_occlusion: the visibility holds bits of {visibility.n_views} views, {len(v.sizes)} views are given')
+    return ops.meshray_occluded(vertices, faces, grid.origin, grid.cell, grid.dims, grid.offsets, grid.refs, v.centres, visibility.visible)
+
+
+def cull_occluded(mesh, views, tol=1 / 256, free_tol=None, facing=True, min_views=1, carve=False, cell=None) -> Mesh:
+    """cull_unseen with an occlusion test against the mesh itself: vertex_visibility -> vertex_occlusion on those bits -> the faces rule of
+    visible_faces on visible & ~occluded -> filter_faces.  A camera inside a room does not see the back of the density shell through the
+    front skin, whatever the faces' winding (facing=False suffices).  cell: of build_ray_grid."""
+    _check_mesh('cull_occluded', mesh)
+    v = _views('cull_occluded', views)
+    visibility = vertex_visibility(mesh.vertices, v, tol, free_tol)
+    occluded = vertex_occlusion(mesh, build_ray_grid(mesh, cell), v, visibility)
+    visibility = Visibility(visibility.visible & ~occluded, visibility.free, visibility.n_views)
+    counts = torch.empty(3, dtype=torch.int64, device=mesh.faces.device)
+    keep, _ = _face_keep('cull_occluded', mesh, visibility, v, facing, min_views, carve, counts[2:])
+    return _filter_faces(mesh, keep, counts, 'cull_occluded')[0]
+
+
+def mesh_distance(mesh, grid, rays_o, rays_d) -> torch.Tensor:
+    """fp32 [N]: the closest t >= 0 along rays_o + t rays_d (the distance for unit directions), +inf where the mesh is not hit."""
+    vertices, faces = _check_grid('mesh_distance', mesh, grid)
+    for name, t in (('rays_o', rays_o), ('rays_d', rays_d)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.PerfError(f'mesh_distance: {name} must be a CUDA tensor (there is no CPU path)')
+    return ops.meshray_cast(vertices, faces, grid.origin, grid.cell, grid.dims, grid.offsets, grid.refs, rays_o.contiguous(), rays_d.contiguous(), uv=False)[0]
+
+
 def write_ply(path, mesh):
     """Binary little-endian PLY: x y z [nx ny nz] [red green blue as uchar] per vertex, a uchar-counted int list per face."""
     v = mesh.vertices.detach().cpu().numpy().astype('<f4')

@@ -1285,6 +1285,112 @@ def meshcolor_blend(vertices, normals, views, sizes, map_pointers, tol, facing=T
     return colors, weight, used, best
 
 
+# ---- rays against a mesh on a uniform grid: closest hit, any hit, segment occlusion (include/perf_hip_meshray.h) -------------------------
+def _ray_mesh(who, vertices, faces):
+    vertices, nv = _simp_vertices(who, vertices)
+    _, f = _cc_faces(who, faces, nv)
+    if faces.device != vertices.device:
+        raise _lib.PerfError(f'{who}: faces must be on the vertices\' device')
+    if f > _lib.MESHRAY_MAX_FACES:
+        raise _lib.PerfError(f'{who}: {f} faces are more than 2^31 - 1')
+    return vertices, nv, f, (_p(vertices) if nv else None, nv, _p(faces) if f else None, f)
+
+
+def _ray_box(who, origin, cell, dims):
+    """(origin fp32 [3], cell fp32, dims int32 [3]) as the library takes them, and the number of cells."""
+    o3, d3 = [float(v) for v in origin], [int(v) for v in dims]
+    if len(o3) != 3 or len(d3) != 3:
+        raise _lib.PerfError(f'{who}: origin and dims hold three values each')
+    if any(v < 1 for v in d3) or d3[0] * d3[1] * d3[2] > _lib.MESHRAY_MAX_CELLS:
+        raise _lib.PerfError(f'{who}: a grid of {d3} cells has a dimension below 1 or more than 2^24 cells')
+    return ((ctypes.c_float * 3)(*o3), float(cell), (ctypes.c_int32 * 3)(*d3)), d3[0] * d3[1] * d3[2]
+
+
+def _ray_lists(who, offsets, refs, n_cells, device):
+    for name, t, n in (('offsets', offsets, n_cells), ('refs', refs, None)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != device:
+            raise _lib.PerfError(f'{who}: {name} must be a CUDA tensor on the mesh\'s device')
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or (n is not None and t.numel() != n):
+            raise _lib.PerfError(f'{who}: {name} must be a contiguous int32 [{n if n is not None else "R"}] tensor, got {t.dtype} {tuple(t.shape)}')
+    r = int(refs.numel())
+    return _p(offsets), _p(refs) if r else None, r
+
+
+def meshray_grid_count(vertices, faces, origin, cell, dims, flag=None):
+    """How many faces each cell of the grid (origin [3], cell edge, dims [3]) lists, by the range rule of include/perf_hip_meshray.h
+    (perf_meshray_grid_count) -> (counts int32 [nx * ny * nz], flag): flag = int64 [1] ON THE DEVICE, the smallest index of a face with an
+    index outside [0, V) or a vertex that is not finite, or -1 (an int64 [1] view to write it into may be passed)."""
+    vertices, nv, f, mesh = _ray_mesh('meshray_grid_count', vertices, faces)
+    box, n_cells = _ray_box('meshray_grid_count', origin, cell, dims)
+    counts = torch.empty(n_cells, dtype=torch.int32, device=vertices.device)
+    if flag is None:
+        flag = torch.empty(1, dtype=torch.int64, device=vertices.device)
+    _call('perf_meshray_grid_count', *mesh, *box, _p(counts), _p(flag), _stream())
+    return counts, flag
+
+
+def meshray_grid_write(vertices, faces, origin, cell, dims, counts, offsets, n_refs):
+    """refs int32 [n_refs]: the faces of every cell, cell c's at offsets[c] .. offsets[c] + its count, in no particular order
+    (perf_meshray_grid_write).  counts: what meshray_grid_count returned, left 0; offsets: their exclusive scan; n_refs: its total."""
+    vertices, nv, f, mesh = _ray_mesh('meshray_grid_write', vertices, faces)
+    box, n_cells = _ray_box('meshray_grid_write', origin, cell, dims)
+    for name, t in (('counts', counts), ('offsets', offsets)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != vertices.device or t.dtype != torch.int32 or tuple(t.shape) != (n_cells,) or not t.is_contiguous():
+            raise _lib.PerfError(f'meshray_grid_write: {name} must be a contiguous CUDA int32 [{n_cells}] tensor on the mesh\'s device')
+    r = int(n_refs)
+    refs = torch.empty(max(r, 0), dtype=torch.int32, device=vertices.device)
+    _call('perf_meshray_grid_write', *mesh, *box, _p(counts), _p(offsets), r, _p(refs) if r > 0 else None, int(refs.numel()), _stream())
+    return refs
+
+
+def _rays(who, name, t, device, n=None):
+    if not torch.is_tensor(t) or not t.is_cuda or t.device != device:
+        raise _lib.PerfError(f'{who}: {name} must be a CUDA tensor on the mesh\'s device (there is no CPU path)')
+    if t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous() or (n is not None and t.shape[0] != n):
+        raise _lib.PerfError(f'{who}: {name} must be a contiguous fp32 [{"N" if n is None else n}, 3] tensor, got {tuple(t.shape)}')
+    return _f32(t, name)
+
+
+def meshray_cast(vertices, faces, origin, cell, dims, offsets, refs, rays_o, rays_d, t_min=0.0, t_max=float('inf'), any_hit=False, uv=True):
+    """The closest hit of every ray -> (t fp32 [N], face int32 [N], u, v fp32 [N] or None without uv), or with any_hit the uint8 [N] flag
+    alone, by the rule of include/perf_hip_meshray.h over the grid meshray_grid_write made of the SAME mesh (perf_meshray_cast)."""
+    vertices, nv, f, mesh = _ray_mesh('meshray_cast', vertices, faces)
+    box, n_cells = _ray_box('meshray_cast', origin, cell, dims)
+    lists = _ray_lists('meshray_cast', offsets, refs, n_cells, vertices.device)
+    rays_o = _rays('meshray_cast', 'rays_o', rays_o, vertices.device)
+    n = int(rays_o.shape[0])
+    rays_d = _rays('meshray_cast', 'rays_d', rays_d, vertices.device, n)
+    dev = vertices.device
+    hit = t = face = u = v = None
+    if any_hit:
+        hit = torch.empty(n, dtype=torch.uint8, device=dev)
+    else:
+        t, face = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        if uv:
+            u, v = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+    ptr = lambda x: _p(x) if x is not None and n else None
+    _call('perf_meshray_cast', *mesh, *box, *lists, ptr(rays_o), ptr(rays_d), n, float(t_min), float(t_max), int(bool(any_hit)), ptr(t), ptr(face), ptr(u), ptr(v),
+          ptr(hit), _stream())
+    return hit if any_hit else (t, face, u, v)
+
+
+def meshray_occluded(vertices, faces, origin, cell, dims, offsets, refs, centres, mask_bits):
+    """occluded_bits int64 [V]: bit k iff bit k of mask_bits is set and a face that does not name the vertex cuts the segment from the vertex
+    to centres[k] (fp32 [K, 3], K <= 64) at a strict 0 < t < 1 (perf_meshray_occluded)."""
+    vertices, nv, f, mesh = _ray_mesh('meshray_occluded', vertices, faces)
+    box, n_cells = _ray_box('meshray_occluded', origin, cell, dims)
+    lists = _ray_lists('meshray_occluded', offsets, refs, n_cells, vertices.device)
+    if not torch.is_tensor(centres) or centres.dim() != 2 or centres.shape[1] != 3 or not centres.is_contiguous() or (centres.shape[0] and not centres.is_cuda):
+        raise _lib.PerfError('meshray_occluded: centres must be a contiguous CUDA fp32 [K, 3] tensor')
+    k = int(centres.shape[0])
+    if k > _lib.MESHRAY_MAX_VIEWS:
+        raise _lib.PerfError(f'meshray_occluded: {k} views are more than {_lib.MESHRAY_MAX_VIEWS} (a vertex has one bit per view in a 64-bit word)')
+    _vis_bits('meshray_occluded', 'mask_bits', mask_bits, nv, vertices.device)
+    out = torch.empty(nv, dtype=torch.int64, device=vertices.device)
+    _call('perf_meshray_occluded', *mesh, *box, *lists, _p(_f32(centres, 'centres')) if k else None, k, _p(mask_bits) if nv else None, _p(out) if nv else None, _stream())
+    return out
+
+
 def normal_composite(weights, grad, packed):
     """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
     R = packed.shape[0]

@@ -1607,6 +1607,24 @@ class NeRFScene:
         kw.setdefault('box', (aabb[:3], aabb[3:]))
         return color_from_panoramas(mesh, sup_pool, **kw)
 
+    def cull_occluded_mesh(self, mesh, sup_pool, **kw):
+        """mesh without the faces none of sup_pool's registered panoramas saw, the mesh's own occlusion included (perf_amd/mesh.py:
+        cull_occluded's keywords) -> mesh.Mesh."""
+        from .mesh import cull_occluded
+        return cull_occluded(mesh, sup_pool, **kw)
+
+    def render_mesh_distance(self, mesh, rays: Rays, grid=None):
+        """The distance panorama of the mesh itself: the closest hit of every ray -> [..., 1], the shape of render's 'distance'.  The value
+        is the ray parameter t of rays.o + t rays.d: a distance for unit directions (gen_pano_rays and gen_pers_rays give them), as
+        render's is; directions of another length are not normalised.  A ray that
+        misses the mesh holds 5, what the eval tail leaves for a ray without samples (distance += 5 (1 - opacity)).  grid: a
+        mesh.RayGrid to reuse, else one is built."""
+        from .mesh import build_ray_grid, mesh_distance
+        rays_o, rays_d = rays.collapse()
+        pre_shape = list(rays_o.shape[:-1])
+        t = mesh_distance(mesh, grid if grid is not None else build_ray_grid(mesh), rays_o.reshape(-1, 3).float().contiguous(), rays_d.reshape(-1, 3).float().contiguous())
+        return torch.where(torch.isinf(t), torch.full_like(t, 5.0), t).reshape(pre_shape + [1])
+
 
 def psnr(pred, gt):
     """-10 log10(mean((pred-gt)^2))  (the reference never computes it)."""

@@ -1,7 +1,7 @@
 """Write the trained density as a triangle mesh (binary PLY): trains the synthetic room, or loads a checkpoint of NeRFScene.state_dict().
 
   python tools/extract_mesh.py --out room.ply [--resolution 256] [--threshold T] [--no-occupancy] [--no-colors] [--no-normals] [--sparse]
-                               [--seen-by-panoramas [--visibility-tol T] [--carve] [--sup-pool pool.pt]]
+                               [--seen-by-panoramas [--occlusion] [--visibility-tol T] [--carve] [--sup-pool pool.pt]]
                                [--min-component-faces N] [--keep-largest K] [--orientation inward|outward]
                                [--simplify-cell H [--simplify-placement mean|member] [--simplify-dedupe oriented|unoriented|none]]
                                [--colors-from-panoramas [--color-select blend|best] [--color-power N] [--sup-pool pool.pt]]
@@ -33,6 +33,7 @@ ap.add_argument('--seen-by-panoramas', action='store_true',
 ap.add_argument('--visibility-tol', type=float, default=1 / 256, help='the band of the depth test of --seen-by-panoramas, in scene units')
 ap.add_argument('--carve', action='store_true', help='with --seen-by-panoramas: also drop the faces with a vertex in observed free space, in front of a stored surface by more than '
                                                        '--visibility-tol (a skin that sits further inside the room than that is carved with the floaters: widen the band)')
+ap.add_argument('--occlusion', action='store_true', help='with --seen-by-panoramas: also test each vertex against the mesh itself (a view does not see through the front skin)')
 ap.add_argument('--sup-pool', default=None, help='with --checkpoint and --seen-by-panoramas: a torch.save of SupInfoPool.state_dict()')
 ap.add_argument('--simplify-cell', type=float, default=None,
                 help='after the cleaning: one vertex per occupied cell of this edge (scene units) of the grid over the scene box (vertex clustering)')
@@ -83,7 +84,10 @@ else:
 torch.cuda.synchronize(); t2 = time.perf_counter()
 extracted = (len(mesh.vertices), len(mesh.faces))
 if args.seen_by_panoramas:          # first the faces no panorama saw, then the components of what is left
-    mesh = scene.cull_unseen_mesh(mesh, views, tol=args.visibility_tol, carve=args.carve)
+    if args.occlusion:          # (the depth test against the panoramas and the segment test against the mesh itself)
+        mesh = scene.cull_occluded_mesh(mesh, views, tol=args.visibility_tol, carve=args.carve)
+    else:
+        mesh = scene.cull_unseen_mesh(mesh, views, tol=args.visibility_tol, carve=args.carve)
 seen = {'seen_vertices': len(mesh.vertices), 'seen_faces': len(mesh.faces)} if args.seen_by_panoramas else {}
 if args.min_component_faces > 0 or args.keep_largest is not None or args.orientation is not None:          # after either extraction path
     mesh = scene.clean_mesh(mesh, min_faces=args.min_component_faces, keep_largest=args.keep_largest, orientation=args.orientation)

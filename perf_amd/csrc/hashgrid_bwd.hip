@@ -57,7 +57,16 @@ struct TileParams {
     uint32_t work[kMaxWork];
 };
 
-constexpr int kQueueCap = 448;             // per-wave match queue (entries): <128 left over + 4 x 64 new + 64 re-queued
+// per-wave match queue (entries).  An iteration of the code / mask loops starts with fewer than 128 entries (its burst loop ran
+// until then; the first starts empty), its four enqueue rounds add at most 4 x 64 (one per lane and sample slot: < 384), the apply's
+// re-queue at most 64 (< 448); the pop that follows takes 64 of them when there are that many, and every further burst round pops as
+// many as its apply re-queues at most.
+constexpr int kQueueCap = 448;
+// Levels whose owners stream tile codes (plan_codes): at most this many tiles.  Their owners form indices with the full-rate 24-bit
+// multiplier, which is exact while an index of the level fits 24 bits.
+constexpr int kMaxCodedHashedTiles = 255, kMaxCodedDenseTiles = 64;
+static_assert((int64_t)(kMaxCodedHashedTiles + 1) * 16384 <= ((int64_t)1 << 24) && (int64_t)kMaxCodedDenseTiles * 16384 <= ((int64_t)1 << 24),
+              "coded levels: indices must fit 24 bits (bwd_stream_masks / bwd_stream_codes multiply with v_mul_u32_u24)");
 constexpr int64_t kMaxCodedSamples = (int64_t)1 << 28;
 
 constexpr int kBitmapMinDenseTiles = 32;
@@ -220,9 +229,40 @@ __device__ __forceinline__ void apply_pairs(const BwdCtx& cx, float* lds_tile, c
     }
 }
 
+// (hi << 32) + lo of two signed fields as one 64-bit word, in 32-bit instructions: the sign extension of lo takes one from hi
+__device__ __forceinline__ unsigned long long field_pair(int lo, int hi) {
+    return ((unsigned long long)((uint32_t)hi + (uint32_t)(lo >> 31)) << 32) | (unsigned long long)(uint32_t)lo;
+}
+
+// The same for ONE combination (`cm` has exactly one bit set): what the code and mask owners pass, every lane its lowest.  Straight
+// line -- no find-first-bit, no loop mask, no back edge --, the factors of apply_pairs in its order: its sums to the bit.
+template <bool FIXED>
+__device__ __forceinline__ void apply_pair_one(const BwdCtx& cx, float* lds_tile, const float2 g, const uint32_t gx, float fx,
+                                               float fy, float fz, const uint32_t ay0, const uint32_t az0, const uint32_t cm) {
+    unsigned long long* lds64 = reinterpret_cast<unsigned long long*>(lds_tile);
+    if (cx.smooth) { fx = fx * fx * (3.0f - 2.0f * fx); fy = fy * fy * (3.0f - 2.0f * fy); fz = fz * fz * (3.0f - 2.0f * fz); }
+    const uint32_t tlo = cx.t * (uint32_t)kTileEntries;
+    const float sx = g.x * cx.to_fixed, sy = g.y * cx.to_fixed;
+    const bool by = (cm & 0xau) != 0u, bz = (cm & 0xcu) != 0u;
+    const uint32_t h = (by ? ay0 + kPrimeY : ay0) ^ (bz ? az0 + kPrimeZ : az0);
+    const float wyz = (by ? fy : 1.0f - fy) * (bz ? fz : 1.0f - fz);
+    const uint32_t a0 = ((gx ^ h) & cx.mask) - tlo, a1 = (((gx + 1u) ^ h) & cx.mask) - tlo;
+    const float w0 = (1.0f - fx) * wyz, w1 = fx * wyz;
+    if (FIXED) {
+        atomicAdd(&lds64[a0], field_pair(__float2int_rn(w0 * sx), __float2int_rn(w0 * sy)));
+        atomicAdd(&lds64[a1], field_pair(__float2int_rn(w1 * sx), __float2int_rn(w1 * sy)));
+    } else {
+        unsafeAtomicAdd(&lds_tile[2 * a0], w0 * g.x); unsafeAtomicAdd(&lds_tile[2 * a0 + 1], w0 * g.y);
+        unsafeAtomicAdd(&lds_tile[2 * a1], w1 * g.x); unsafeAtomicAdd(&lds_tile[2 * a1 + 1], w1 * g.y);
+    }
+}
+
 // Dense-level counterpart (interleaved 32-entry chunks): the two x-corners of a (y,z) combination are tested
 // separately -- they part at a chunk boundary -- and a combination that would wrap past the end of the level
 // (position far outside the unit cube; such a level takes the generic owners, see tile_codes4_kernel) is skipped.
+// ay0 / az0 need only be right in their low 24 bits (bwd_stream_codes forms them with the 24-bit multiplier): the pre-pass names a tile
+// only for a sample all of whose x0 corners lie below size - 1 <= 2^20 in exact 32-bit arithmetic (any 0x7f byte sends the sample to
+// bwd_apply), so the low 24 bits of the sum ARE the index.
 template <bool FIXED>
 __device__ __forceinline__ void apply_pairs_dense(const BwdCtx& cx, float* lds_tile, const float2 g, const uint32_t gx, float fx,
                                                   float fy, float fz, const uint32_t ay0, const uint32_t az0, uint32_t cm) {
@@ -234,18 +274,18 @@ __device__ __forceinline__ void apply_pairs_dense(const BwdCtx& cx, float* lds_t
         const int c = __ffs(cm) - 1;
         cm &= cm - 1u;
         const int by = c & 1, bz = c >> 1;
-        const uint32_t i0 = gx + (by ? ay0 + cx.res : ay0) + (bz ? az0 + cx.r2 : az0), i1 = i0 + 1u;
+        const uint32_t i0 = (gx + (by ? ay0 + cx.res : ay0) + (bz ? az0 + cx.r2 : az0)) & 0xffffffu, i1 = i0 + 1u;
         if (i1 >= cx.size || i1 == 0u) continue;
         const float wy = by ? fy : 1.0f - fy, wz = bz ? fz : 1.0f - fz;
         const float w0 = ((1.0f - fx) * wy) * wz, w1 = (fx * wy) * wz;      // association of the generic owners
         const uint32_t c0 = i0 / kChunk, c1 = i1 / kChunk;
         const uint32_t a0 = (c0 >> cx.tile_shift) * kChunk + (i0 % kChunk), a1 = (c1 >> cx.tile_shift) * kChunk + (i1 % kChunk);
         if ((c0 & tmask) == cx.t) {
-            if (FIXED) atomicAdd(&lds64[a0], (unsigned long long)(((long long)__float2int_rn(w0 * sy) << 32) + (long long)__float2int_rn(w0 * sx)));
+            if (FIXED) atomicAdd(&lds64[a0], field_pair(__float2int_rn(w0 * sx), __float2int_rn(w0 * sy)));
             else { unsafeAtomicAdd(&lds_tile[2 * a0], w0 * g.x); unsafeAtomicAdd(&lds_tile[2 * a0 + 1], w0 * g.y); }
         }
         if ((c1 & tmask) == cx.t) {
-            if (FIXED) atomicAdd(&lds64[a1], (unsigned long long)(((long long)__float2int_rn(w1 * sy) << 32) + (long long)__float2int_rn(w1 * sx)));
+            if (FIXED) atomicAdd(&lds64[a1], field_pair(__float2int_rn(w1 * sx), __float2int_rn(w1 * sy)));
             else { unsafeAtomicAdd(&lds_tile[2 * a1], w1 * g.x); unsafeAtomicAdd(&lds_tile[2 * a1 + 1], w1 * g.y); }
         }
     }
@@ -608,13 +648,53 @@ __global__ __launch_bounds__(256) void tile_bitmap_kernel(GridParams gp, TilePar
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x3 __attribute__((ext_vector_type(3)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// position of a lane among the set bits of a ballot
+__device__ __forceinline__ uint32_t ballot_rank(unsigned long long b) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+}
+// One sample slot into the wave's queue: the lanes that hit append their entries in lane order.  (`queue` and `qn` are wave-uniform and
+// live on the scalar unit -- the kernel takes the wave's number through readfirstlane --, so the address of a write is ONE vector
+// instruction on the lane's rank: rank * 4 + scalar.)
+__device__ __forceinline__ void enqueue1(uint32_t* queue, uint32_t& qn, bool hit, uint32_t e) {
+    const unsigned long long b = __ballot(hit);
+    if (b) {
+        if (hit) (queue + qn)[ballot_rank(b)] = e;
+        qn += (uint32_t)__popcll(b);
+    }
+}
+// grid_pos and a difference as single instructions the compiler cannot pair with their neighbours.  Left to itself it works on two of
+// a gathered sample's three coordinates with two-wide f32 instructions (v_pk_fma_f32, v_pk_add_f32: y and z arrive as a register
+// pair; with z taken out it pairs y with x), each of which holds a wave's issue about three times as long as the two plain
+// instructions it stands for.  The same instructions on the same operands: the same bits.
+__device__ __forceinline__ float grid_pos_alone(float x, float scale) {
+    float r;
+    asm("v_fma_f32 %0, %1, %2, 0.5" : "=v"(r) : "v"(x), "v"(scale));
+    return r;
+}
+__device__ __forceinline__ float sub_alone(float a, float b) {
+    float r;
+    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// byte offsets of sample i's gradient (8 i) and position (12 i) by shifts and adds: i may exceed 2^24 (no 24-bit multiply), and
+// the 32-bit multiply is quarter rate.  (The empty asm keeps the two shifts from being folded back into i * 12.)
+__device__ __forceinline__ void sample_offsets(uint32_t i, uint32_t& ox, uint32_t& og) {
+    og = i << 3;
+    asm("" : "+v"(og));
+    ox = (i << 2) + og;
+}
 
 // The loads of this loop are issued through inline assembly with hand-placed s_waitcnt: the compiler's own
 // placement waits for a gather right where it is issued (it packs the loaded y,z into a register pair for a packed
 // multiply) and drains vmcnt to 0 around the conditional drain.  VMEM loads return in issue order, so
 // "vmcnt(k)" = "everything but the k youngest loads has landed"; the number of loads issued per step is static
-// (2 code loads, then 3 gather loads per drain, idle lanes gather sample 0).
+// (2 code loads, then 2 gather loads per drain, idle lanes gather sample 0).  A sample's position is ONE 12-byte load
+// (global_load_dwordx3; 4-byte alignment is all it asks): as a 4-byte and an 8-byte load of the same line the address unit walked the
+// 64 lanes twice, and that walk, not arithmetic, is what the owners of the fine levels wait for in a training step -- their queued
+// samples are scattered, a line per lane (302 -> 281 us per workgroup at the finest levels, the coarse ones unchanged).
 // (Round 4 also built 16-bit nibble codes -- two samples tested with four bit-parallel operations --: bit-identical, owners 378.9
 //  vs 361.7 us per 1 M samples, profiles/r04_bwd_code16_ab.json; the variant is tools/exp/r05_retired_variants.diff.)
 template <bool FIXED, bool DENSE>
@@ -629,8 +709,8 @@ __device__ __forceinline__ void bwd_stream_codes(const BwdCtx& cx, float* lds_ti
     uint32_t qn = 0;                                    // wave-uniform queue fill
     const int64_t n_full = n / kPer;
     const int64_t g_lo = n_full * rep / R, g_hi = n_full * (rep + 1) / R;       // this replica's groups of kPer samples
-    // registers written by loads in flight: only ever read through the wait_* copies below
-    float ld_x = 0.f; f32x2 ld_yz = {0.f, 0.f}, ld_g = {0.f, 0.f}; u32x2 ld_c0 = {0u, 0u}, ld_c1 = {0u, 0u};
+    // registers written by loads in flight: only ever read behind the waits below
+    f32x3 ld_p = {0.f, 0.f, 0.f}; f32x2 ld_g = {0.f, 0.f}; u32x2 ld_c0 = {0u, 0u}, ld_c1 = {0u, 0u};
     uint32_t bcm = 0, bi = 0;                           // (y,z) combinations and sample index of the batch in flight
     bool blive = false;                                 // this lane holds an entry of the batch in flight
     const uint32_t t_split = 0x80u | cx.t, t_next = 0x80u | ((cx.t - 1u) & (cx.n_tiles - 1u));     // dense codes
@@ -662,47 +742,40 @@ __device__ __forceinline__ void bwd_stream_codes(const BwdCtx& cx, float* lds_ti
         }
         return wraps ? 0x10u : cm;
     };
-    auto enqueue = [&](uint32_t cm, uint32_t i) {
-        const unsigned long long b = __ballot(cm != 0u);
-        if (b) {
-            const uint32_t pos = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-            if (cm) queue[pos] = (i << 4) | (cm & 15u);
-            qn += (uint32_t)__popcll(b);
-        }
+    // queue entry of sample i: index << 4 | combinations (the index's low four bits are clear: the dot product's addend ORs them in)
+    auto entry = [&](uint32_t cm, uint32_t i) { return (i << 4) | (cm & 15u); };
+    auto entry_marks = [&](uint32_t marks, uint32_t i) {          // (hashed levels: `marks` of test_marks)
+        return __builtin_amdgcn_udot4(marks >> 7, 0x08040201u, i << 4, false);
     };
-    auto enqueue_marks = [&](uint32_t marks, uint32_t i) {        // (hashed levels: `marks` of test_marks)
-        const unsigned long long b = __ballot(marks != 0u);
-        if (b) {
-            const uint32_t pos = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-            if (marks) queue[pos] = (i << 4) | __builtin_amdgcn_udot4(marks >> 7, 0x08040201u, 0u, false);
-            qn += (uint32_t)__popcll(b);
-        }
-    };
-    auto load_codes = [&](int64_t grp) {                // 2 loads
-        const uint32_t off = (uint32_t)(grp < g_hi ? grp : g_hi - 1) * 16u;
+    auto enqueue = [&](uint32_t cm, uint32_t i) { enqueue1(queue, qn, cm != 0u, entry(cm, i)); };
+    auto enqueue_marks = [&](uint32_t marks, uint32_t i) { enqueue1(queue, qn, marks != 0u, entry_marks(marks, i)); };
+    auto load_codes = [&](uint32_t grp) {               // 2 loads
+        const uint32_t off = (grp < (uint32_t)g_hi ? grp : (uint32_t)g_hi - 1u) * 16u;
         asm volatile("global_load_dwordx2 %0, %2, %3\n\tglobal_load_dwordx2 %1, %2, %3 offset:8"
                      : "=&v"(ld_c0), "=&v"(ld_c1) : "v"(off), "s"(codes_l) : "memory");
     };
-    auto pop_and_gather = [&]() {       // up to 64 queued samples: issue the 3 loads of their position and gradient
-        const uint32_t take = qn < 64u ? qn : 64u;
+    auto pop_and_gather = [&]() {       // up to 64 queued samples: issue the 2 loads of their position and gradient
+        // (readfirstlane: scalar min and subtract -- left to itself the compiler forms qn - take as a saturating VECTOR subtract)
+        const uint32_t take = (uint32_t)__builtin_amdgcn_readfirstlane((int)(qn < 64u ? qn : 64u));
         __builtin_amdgcn_wave_barrier();
         uint32_t e = 0;
-        if (lane < take) e = queue[qn - take + lane];
+        if (lane < take) e = (queue + (qn - take))[lane];
         __builtin_amdgcn_wave_barrier();
         qn -= take;
         blive = lane < take;
         bcm = e & 15u;
         bi = e >> 4;
-        const uint32_t ox = bi * 12u, og = bi * 8u;
-        asm volatile("global_load_dword %0, %3, %4\n\tglobal_load_dwordx2 %1, %3, %4 offset:4\n\tglobal_load_dwordx2 %2, %5, %6"
-                     : "=&v"(ld_x), "=&v"(ld_yz), "=&v"(ld_g) : "v"(ox), "s"(x01), "v"(og), "s"(g_l) : "memory");
+        uint32_t ox, og;
+        sample_offsets(bi, ox, og);
+        asm volatile("global_load_dwordx3 %0, %2, %3\n\tglobal_load_dwordx2 %1, %4, %5"
+                     : "=&v"(ld_p), "=&v"(ld_g) : "v"(ox), "s"(x01), "v"(og), "s"(g_l) : "memory");
     };
-    // wait until at most `younger` loads are in flight, then copy the landed registers (the copy is part of the
-    // asm statement: the compiler must not move a read of those registers above the wait)
+    // wait until at most `younger` loads are in flight; the batch is then read from the registers it landed in (they are in-out
+    // operands of the wait: the compiler must not move a read of them above it, and no copy is spent -- the batch is dead before the
+    // next pop issues loads into them)
 #define PERF_WAIT_BATCH(younger)                                                                                        \
-    float bx; f32x2 byz, bg;                                                                                            \
-    asm volatile("s_waitcnt vmcnt(" #younger ")\n\tv_mov_b32 %0, %3\n\tv_mov_b64 %1, %4\n\tv_mov_b64 %2, %5"           \
-                 : "=&v"(bx), "=&v"(byz), "=&v"(bg) : "v"(ld_x), "v"(ld_yz), "v"(ld_g) : "memory")
+    asm volatile("s_waitcnt vmcnt(" #younger ")" : "+v"(ld_p), "+v"(ld_g) : : "memory");                                \
+    const float bx = ld_p.x; const f32x2 byz = {ld_p.y, ld_p.z}, bg = ld_g
     // The batch gathered one drain ago.  Every lane applies ONE combination (loop-free at full occupancy); the 7 % of
     // samples that name this tile with two or more combinations go back into the queue with the remaining ones.
     auto apply_batch = [&](float bx, f32x2 byz, f32x2 bg) {
@@ -713,35 +786,39 @@ __device__ __forceinline__ void bwd_stream_codes(const BwdCtx& cx, float* lds_ti
         const uint32_t rest = DENSE ? 0u : bcm & (bcm - 1u);        // (dense tiles are named by several combinations as a rule)
         if (!DENSE) bcm &= 0u - bcm;
         if (bcm) {
-            const float px = grid_pos(bx, cx.scale), py = grid_pos(byz.x, cx.scale), pz = grid_pos(byz.y, cx.scale);
+            const float px = grid_pos(bx, cx.scale), py = grid_pos_alone(byz.x, cx.scale), pz = grid_pos_alone(byz.y, cx.scale);
             const float flx = floorf(px), fly = floorf(py), flz = floorf(pz);
-            const uint32_t gx = (uint32_t)(int32_t)flx;
+            const uint32_t gx = (uint32_t)(int32_t)flx, gy = (uint32_t)(int32_t)fly, gz = (uint32_t)(int32_t)flz;
+            // (only the low 24 bits of the (y,z) terms count on a coded level -- kMaxCodedHashedTiles -- and those are the low 24 bits
+            //  of the full-rate 24-bit product of the factors' low 24 bits, for any cell: hashed_tiles)
             if (DENSE)
-                apply_pairs_dense<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, py - fly, pz - flz,
-                                         (uint32_t)(int32_t)fly * cx.res, (uint32_t)(int32_t)flz * cx.r2, bcm);
+                apply_pairs_dense<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, sub_alone(py, fly), sub_alone(pz, flz),
+                                         __umul24(gy, cx.res), __umul24(gz, cx.r2), bcm);
             else if (gx < (uint32_t)(kTileEntries - 1))      // (else: zero gradient, see tile_codes4_kernel)
-                apply_pairs<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, py - fly, pz - flz,
-                                   (uint32_t)(int32_t)fly * kPrimeY, (uint32_t)(int32_t)flz * kPrimeZ, bcm);
+                apply_pair_one<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, sub_alone(py, fly), sub_alone(pz, flz),
+                                      __umul24(gy, kPrimeY & 0xffffffu), __umul24(gz, kPrimeZ & 0xffffffu), bcm);
         }
         if (!DENSE) enqueue(rest, bi);
     };
     if (g_hi > g_lo) {
-        int64_t grp = g_lo + threadIdx.x;
+        // (groups and sample indices fit 32 bits: kMaxCodedSamples; the trip count is wave-uniform and kept on the scalar unit)
+        const uint32_t g_end = (uint32_t)g_hi;
+        uint32_t grp = (uint32_t)g_lo + threadIdx.x;
         load_codes(grp);
         pop_and_gather();               // empty queue: dummy gather, keeps the in-flight count of the loop static
-        for (int64_t base = g_lo + (int64_t)(threadIdx.x & ~63u); base < g_hi; base += kBwdThreads) {   // wave-uniform trip count
-            u32x2 c0, c1;               // in flight, oldest first: 2 code loads, 3 gather loads
-            asm volatile("s_waitcnt vmcnt(3)\n\tv_mov_b64 %0, %2\n\tv_mov_b64 %1, %3" : "=&v"(c0), "=&v"(c1) : "v"(ld_c0), "v"(ld_c1) : "memory");
-            const int64_t g0 = grp;
-            const bool valid = g0 < g_hi;
+        for (uint32_t base = (uint32_t)g_lo + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u)); base < g_end; base += kBwdThreads) {
+            u32x2 c0, c1;               // in flight, oldest first: 2 code loads, 2 gather loads
+            asm volatile("s_waitcnt vmcnt(2)\n\tv_mov_b64 %0, %2\n\tv_mov_b64 %1, %3" : "=&v"(c0), "=&v"(c1) : "v"(ld_c0), "v"(ld_c1) : "memory");
+            const uint32_t g0 = grp;
+            const bool valid = g0 < g_end;
             grp += kBwdThreads;
             load_codes(grp);
             const uint32_t cs[4] = {c0.x, c0.y, c1.x, c1.y};
             const uint32_t t4v = valid ? t4 : 0xffffffffu;
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                if (DENSE) enqueue(valid ? test(cs[s]) : 0u, (uint32_t)(4 * g0 + s));
-                else enqueue_marks(test_marks(cs[s], t4v), (uint32_t)(4 * g0 + s));
+                if (DENSE) enqueue(valid ? test(cs[s]) : 0u, 4u * g0 + (uint32_t)s);
+                else enqueue_marks(test_marks(cs[s], t4v), 4u * g0 + (uint32_t)s);
             }
             {
                 PERF_WAIT_BATCH(2);         // all but the 2 code loads
@@ -779,13 +856,13 @@ __device__ __forceinline__ void bwd_stream_codes(const BwdCtx& cx, float* lds_ti
 // samples arrive in one 8-byte load.  What the mask does not say is WHICH of the sample's four (y,z) combinations name the tile: a
 // fresh queue entry carries cm = 0 and the apply works the combinations out from the (y,z) it gathered anyway, with the pre-pass's own
 // four tile expressions (hashed_tiles); re-queued entries carry their remaining combinations as before.
-// In flight at the head of an iteration, oldest first: [masks: 1][gather batch: 3], so "vmcnt(3)" = the masks have landed; every pop
-// issues 3 loads and every iteration 1, whatever the queue holds.  The queue bound is bwd_stream_codes' (kQueueCap).
+// In flight at the head of an iteration, oldest first: [masks: 1][gather batch: 2], so "vmcnt(2)" = the masks have landed; every pop
+// issues 2 loads and every iteration 1, whatever the queue holds.  The queue bound is bwd_stream_codes' (kQueueCap).
 // (A SECOND gather batch in flight per wave -- two register sets taking turns, the main loop unrolled by two, bursts drained in pairs,
 //  the batch popped in one iteration applied in the one after the next -- was built and measured beside this loop: per-workgroup times
 //  of the hashed owners equal within 1 us, the step 0.846 ms either way; DESIGN.md 5.1, profiles/bwd_tile_masks.json.  Not kept.)
 struct GatherBatch {
-    float ld_x; f32x2 ld_yz, ld_g;      // written by loads in flight: only ever read through PERF_WAIT_APPLY
+    f32x3 ld_p; f32x2 ld_g;             // written by loads in flight: only ever read through PERF_WAIT_APPLY
     uint32_t cm, i;                     // combinations (0: not known yet) and sample index of the lane's entry
     bool live;                          // this lane holds an entry
 };
@@ -801,49 +878,39 @@ __device__ __forceinline__ void bwd_stream_masks(const BwdCtx& cx, float* lds_ti
     const int64_t n_full = n / kPer;
     const int64_t g_lo = n_full * rep / R, g_hi = n_full * (rep + 1) / R;       // this replica's groups of kPer samples
     u32x2 ld_m = {0u, 0u};                              // written by the load in flight
-    GatherBatch A = {0.f, {0.f, 0.f}, {0.f, 0.f}, 0u, 0u, false};               // the batch in flight
+    GatherBatch A = {{0.f, 0.f, 0.f}, {0.f, 0.f}, 0u, 0u, false};               // the batch in flight
     const uint32_t bit2 = (1u << cx.t) * 0x00010001u;   // this owner's bit in both halves of a word of two masks
     const uint32_t t_hi = cx.t * (uint32_t)kTileEntries, m_hi = cx.mask & ~(uint32_t)(kTileEntries - 1);
-    auto enqueue_hit = [&](bool hit, uint32_t e) __attribute__((always_inline)) {     // fresh entry: combinations not known yet
-        const unsigned long long b = __ballot(hit);
-        if (b) {
-            const uint32_t pos = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-            if (hit) queue[pos] = e;
-            qn += (uint32_t)__popcll(b);
-        }
-    };
-    auto requeue = [&](uint32_t cm, uint32_t i) __attribute__((always_inline)) {
-        const unsigned long long b = __ballot(cm != 0u);
-        if (b) {
-            const uint32_t pos = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-            if (cm) queue[pos] = (i << 4) | cm;
-            qn += (uint32_t)__popcll(b);
-        }
-    };
-    auto load_masks = [&](int64_t grp) __attribute__((always_inline)) {                // 1 load
-        const uint32_t off = (uint32_t)(grp < g_hi ? grp : g_hi - 1) * 8u;
+    // (fresh entries: index << 4, the combinations not known yet; re-queued ones carry theirs)
+    auto requeue = [&](uint32_t cm, uint32_t i) __attribute__((always_inline)) { enqueue1(queue, qn, cm != 0u, (i << 4) | cm); };
+    auto load_masks = [&](uint32_t grp) __attribute__((always_inline)) {               // 1 load
+        const uint32_t off = (grp < (uint32_t)g_hi ? grp : (uint32_t)g_hi - 1u) * 8u;
         asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(ld_m) : "v"(off), "s"(masks_l) : "memory");
     };
-    auto pop_and_gather = [&]() __attribute__((always_inline)) {                       // up to 64 queued samples: 3 loads
-        const uint32_t take = qn < 64u ? qn : 64u;
+    auto pop_and_gather = [&]() __attribute__((always_inline)) {                       // up to 64 queued samples: 2 loads
+        // (readfirstlane: scalar min and subtract -- left to itself the compiler forms qn - take as a saturating VECTOR subtract)
+        const uint32_t take = (uint32_t)__builtin_amdgcn_readfirstlane((int)(qn < 64u ? qn : 64u));
         __builtin_amdgcn_wave_barrier();
         uint32_t e = 0;
-        if (lane < take) e = queue[qn - take + lane];
+        if (lane < take) e = (queue + (qn - take))[lane];
         __builtin_amdgcn_wave_barrier();
         qn -= take;
         A.live = lane < take;
         A.cm = e & 15u;
         A.i = e >> 4;
-        const uint32_t ox = A.i * 12u, og = A.i * 8u;
-        asm volatile("global_load_dword %0, %3, %4\n\tglobal_load_dwordx2 %1, %3, %4 offset:4\n\tglobal_load_dwordx2 %2, %5, %6"
-                     : "=&v"(A.ld_x), "=&v"(A.ld_yz), "=&v"(A.ld_g) : "v"(ox), "s"(x01), "v"(og), "s"(g_l) : "memory");
+        uint32_t ox, og;
+        sample_offsets(A.i, ox, og);
+        asm volatile("global_load_dwordx3 %0, %2, %3\n\tglobal_load_dwordx2 %1, %4, %5"
+                     : "=&v"(A.ld_p), "=&v"(A.ld_g) : "v"(ox), "s"(x01), "v"(og), "s"(g_l) : "memory");
     };
     // Every lane applies ONE combination; the samples that name this tile with two or more go back into the queue with the rest.
     auto apply_batch = [&](float bx, f32x2 byz, f32x2 bg) __attribute__((always_inline)) {
-        const float px = grid_pos(bx, cx.scale), py = grid_pos(byz.x, cx.scale), pz = grid_pos(byz.y, cx.scale);
+        const float px = grid_pos(bx, cx.scale), py = grid_pos_alone(byz.x, cx.scale), pz = grid_pos_alone(byz.y, cx.scale);
         const float flx = floorf(px), fly = floorf(py), flz = floorf(pz);
         const uint32_t gx = (uint32_t)(int32_t)flx;
-        const uint32_t ay0 = (uint32_t)(int32_t)fly * kPrimeY, az0 = (uint32_t)(int32_t)flz * kPrimeZ;
+        // (a mask level has at most 2^18 entries: only the low 24 bits of the (y,z) terms count, and those are the low 24 bits of the
+        //  full-rate 24-bit product of the factors' low 24 bits, for any cell -- the pre-pass's own expressions, hashed_tiles)
+        const uint32_t ay0 = __umul24((uint32_t)(int32_t)fly, kPrimeY & 0xffffffu), az0 = __umul24((uint32_t)(int32_t)flz, kPrimeZ & 0xffffffu);
         const uint32_t ay1 = ay0 + kPrimeY, az1 = az0 + kPrimeZ;
         // (tile == t, with the tile's bits of the index compared in place)
         const uint32_t derived = ((((ay0 ^ az0) & m_hi) == t_hi) ? 1u : 0u) | ((((ay1 ^ az0) & m_hi) == t_hi) ? 2u : 0u) |
@@ -852,37 +919,38 @@ __device__ __forceinline__ void bwd_stream_masks(const BwdCtx& cx, float* lds_ti
         if (!A.live || gx >= (uint32_t)(kTileEntries - 1)) cm = 0u;     // (idle lane; or zero gradient, see tile_codes4_kernel)
         const uint32_t rest = cm & (cm - 1u);
         cm &= 0u - cm;
-        if (cm) apply_pairs<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, py - fly, pz - flz, ay0, az0, cm);
+        if (cm) apply_pair_one<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, sub_alone(py, fly), sub_alone(pz, flz), ay0, az0, cm);
         requeue(rest, A.i);
     };
-    // wait until at most `younger` loads are in flight, then copy the landed registers of the batch (the copy is part of the asm
-    // statement: the compiler must not move a read of those registers above the wait) and apply it.
+    // wait until at most `younger` loads are in flight, then apply the batch from the registers it landed in (they are in-out operands
+    // of the wait: the compiler must not move a read of them above it, and no copy is spent -- the batch is dead before the next pop
+    // issues loads into them).
     // (The batch must keep its registers from pop to apply on every path: a compiler-made copy of a register that a load in flight
     //  is still to write reads it too early.  After a change to this loop, compare the registers of the loads with those of the copies
     //  in the assembly.)
 #define PERF_WAIT_APPLY(younger)                                                                                        \
     {                                                                                                                   \
-        float bx; f32x2 byz, bg;                                                                                        \
-        asm volatile("s_waitcnt vmcnt(" #younger ")\n\tv_mov_b32 %0, %3\n\tv_mov_b64 %1, %4\n\tv_mov_b64 %2, %5"       \
-                     : "=&v"(bx), "=&v"(byz), "=&v"(bg) : "v"(A.ld_x), "v"(A.ld_yz), "v"(A.ld_g) : "memory");           \
-        apply_batch(bx, byz, bg);                                                                                       \
+        asm volatile("s_waitcnt vmcnt(" #younger ")" : "+v"(A.ld_p), "+v"(A.ld_g) : : "memory");                        \
+        apply_batch(A.ld_p.x, f32x2{A.ld_p.y, A.ld_p.z}, A.ld_g);                                                       \
     }
     if (g_hi > g_lo) {
-        int64_t grp = g_lo + threadIdx.x;
+        // (groups and sample indices fit 32 bits: kMaxCodedSamples; the trip count is wave-uniform and kept on the scalar unit)
+        const uint32_t g_end = (uint32_t)g_hi;
+        uint32_t grp = (uint32_t)g_lo + threadIdx.x;
         load_masks(grp);
         pop_and_gather();               // empty queue: dummy gather, keeps the in-flight count of the loop static
-        for (int64_t base = g_lo + (int64_t)(threadIdx.x & ~63u); base < g_hi; base += kBwdThreads) {   // wave-uniform trip count
+        for (uint32_t base = (uint32_t)g_lo + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u)); base < g_end; base += kBwdThreads) {
             u32x2 m;
-            asm volatile("s_waitcnt vmcnt(3)\n\tv_mov_b64 %0, %1" : "=&v"(m) : "v"(ld_m) : "memory");
-            const int64_t g0 = grp;
-            const uint32_t vb = g0 < g_hi ? bit2 : 0u;      // a lane without a group of its own in the last iteration hits nothing
+            asm volatile("s_waitcnt vmcnt(2)\n\tv_mov_b64 %0, %1" : "=&v"(m) : "v"(ld_m) : "memory");
+            const uint32_t g0 = grp;
+            const uint32_t vb = g0 < g_end ? bit2 : 0u;     // a lane without a group of its own in the last iteration hits nothing
             grp += kBwdThreads;
             load_masks(grp);
-            const uint32_t b_lo = vb & 0xffffu, b_hi = vb & 0xffff0000u, e0 = (uint32_t)(4 * g0) << 4;
-            enqueue_hit((m.x & b_lo) != 0u, e0);
-            enqueue_hit((m.x & b_hi) != 0u, e0 + 16u);
-            enqueue_hit((m.y & b_lo) != 0u, e0 + 32u);
-            enqueue_hit((m.y & b_hi) != 0u, e0 + 48u);
+            const uint32_t b_lo = vb & 0xffffu, b_hi = vb & 0xffff0000u, e0 = g0 << 6;
+            enqueue1(queue, qn, (m.x & b_lo) != 0u, e0);
+            enqueue1(queue, qn, (m.x & b_hi) != 0u, e0 + 16u);
+            enqueue1(queue, qn, (m.y & b_lo) != 0u, e0 + 32u);
+            enqueue1(queue, qn, (m.y & b_hi) != 0u, e0 + 48u);
             PERF_WAIT_APPLY(1)              // all but the mask load
             pop_and_gather();
             while (qn >= 128u) {            // bursts (ray-coherent samples at coarse hashed levels)
@@ -895,7 +963,7 @@ __device__ __forceinline__ void bwd_stream_masks(const BwdCtx& cx, float* lds_ti
         const int64_t i = n_full * kPer + lane;
         bool hit = false;
         if (i < n) hit = ((reinterpret_cast<const uint16_t*>(masks_l)[i] >> cx.t) & 1u) != 0u;
-        enqueue_hit(hit, (uint32_t)i << 4);
+        enqueue1(queue, qn, hit, (uint32_t)i << 4);
     }
     for (;;) {
         PERF_WAIT_APPLY(0)
@@ -1220,7 +1288,8 @@ __global__ __launch_bounds__(kBwdThreads) void hashgrid_bwd_kernel(GridParams gp
         __syncthreads();
         by_bitmap = esc_bm_any == 0u;
     }
-    uint32_t* queue = reinterpret_cast<uint32_t*>(lds_tile + 2 * kTileEntries) + (threadIdx.x >> 6) * kQueueCap;
+    // (the wave's number through readfirstlane: the queue's address stays on the scalar unit, see enqueue1)
+    uint32_t* queue = reinterpret_cast<uint32_t*>(lds_tile + 2 * kTileEntries) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kQueueCap;
     if (by_bitmap && hashed) bwd_stream_bitmap<FIXED, false>(cx, lds_tile, queue, bitmaps + (int64_t)(tp.bm_row[l] + (int)t) * tp.bm_row_words, x01, g_l, n_live);
     else if (by_bitmap) bwd_stream_bitmap<FIXED, true>(cx, lds_tile, queue, bitmaps + (int64_t)(tp.bm_row[l] + (int)t) * tp.bm_row_words, x01, g_l, n_live);
     else if (coded && hashed && n_tiles <= (uint32_t)kMaskTiles) bwd_stream_masks<FIXED>(cx, lds_tile, queue, codes + (int64_t)tp.code_slot[l] * tp.n_pad, x01, g_l, n_live, rep, R);
@@ -1505,7 +1574,8 @@ static int plan_codes(const GridParams& gp, int64_t n, TileParams* tp) {
         tp->code_slot[l] = -1;
         if (l >= gp.n_levels || n >= kMaxCodedSamples || ((tp->bitmap_levels >> l) & 1u)) continue;
         const int64_t nt = tp->tiles_of[l];         // (plan_tiles ran before)
-        if (gp.hashed[l] ? (nt >= 2 && nt <= 255 && gp.res[l] + 2u < (uint32_t)kTileEntries) : (nt >= 2 && nt <= 64)) {
+        // (at most 2^24 entries either way: the owners' 24-bit index arithmetic, see kMaxCodedHashedTiles)
+        if (gp.hashed[l] ? (nt >= 2 && nt <= kMaxCodedHashedTiles && gp.res[l] + 2u < (uint32_t)kTileEntries) : (nt >= 2 && nt <= kMaxCodedDenseTiles)) {
             tp->code_slot[l] = slots++;
         }
     }

@@ -1,5 +1,6 @@
 """Build libperf_hip.so (gfx950) in-tree with hipcc.  `python -m perf_amd.build [--force]`."""
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -10,7 +11,7 @@ LIB = os.path.join(HERE, 'libperf_hip.so')
 # (the MLP kernels are instantiated in six units of their own: one unit took 65 s, the longest of them now takes ~15 s)
 SOURCES = ['mlp_bwd_bf16_nh2.hip', 'mlp_bwd_fp16_nh2.hip', 'mlp_bwd_bf16_nh1.hip', 'mlp_bwd_fp16_nh1.hip', 'mlp_fwd_bf16.hip', 'mlp_fwd_fp16.hip', 'mlp_fwd_rows.hip',
            'hashgrid_bwd.hip', 'hashgrid_bwd_lines.hip', 'hashgrid_fwd.hip', 'hashgrid_aux.hip', 'march.hip', 'misc.hip', 'composite.hip', 'mlp.hip', 'visibility.hip', 'field_normal.hip', 'field_normal_bwd.hip', 'sphere_field.hip', 'hashgrid_pair.hip', 'joint_align.hip', 'mesh.hip', 'brickmesh.hip', 'meshcc.hip', 'meshvis.hip', 'meshsimp.hip', 'meshcolor.hip', 'meshray.hip']
-HEADERS = ['common.hpp', 'grid_device.hpp', 'grid_fixed_point.hpp', 'mlp_reduce_device.hpp', 'step_book_device.hpp', 'mlp_device.hpp', 'field_normal_device.hpp', 'mesh_device.hpp']
+HEADERS = ['common.hpp', 'grid_device.hpp', 'grid_fixed_point.hpp', 'mlp_reduce_device.hpp', 'step_book_device.hpp', 'mlp_device.hpp', 'field_normal_device.hpp', 'mesh_device.hpp', 'mesh_scan_device.hpp', 'mesh_filter_device.hpp']
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs (no v_accvgpr_read per accumulator register before the epilogues)
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
          '-mllvm', '-amdgpu-mfma-vgpr-form=1']
@@ -21,6 +22,12 @@ def _newer(target, deps):
         return False
     t = os.path.getmtime(target)
     return all(os.path.getmtime(d) <= t for d in deps)
+
+
+def _includes(path):
+    """path and, transitively, the files its `#include "..."` lines name: what a unit is rebuilt for"""
+    names = re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', open(path).read(), re.M)
+    return {path}.union(*(_includes(os.path.normpath(os.path.join(os.path.dirname(path), n))) for n in names))
 
 
 def build(force=False, verbose=False):
@@ -34,17 +41,7 @@ def build(force=False, verbose=False):
 
     def cc(src):
         obj = os.path.join(objdir, src.replace('.hip', '.o'))
-        own = [h for h in hdrs if src.startswith(('mlp', 'field_normal')) or not h.endswith(('mlp_device.hpp', 'field_normal_device.hpp'))]       # (only the mlp and field_normal units include these two)
-        own = [h for h in own if src == 'mesh.hip' or not h.endswith('perf_hip_mesh.h')]       # (and only the mesh unit its header)
-        own = [h for h in own if src == 'brickmesh.hip' or not h.endswith('perf_hip_brickmesh.h')]       # (the brick unit likewise)
-        own = [h for h in own if src == 'meshcc.hip' or not h.endswith('perf_hip_meshcc.h')]       # (and the component unit)
-        own = [h for h in own if src == 'meshvis.hip' or not h.endswith('perf_hip_meshvis.h')]       # (and the visibility-cull unit)
-        own = [h for h in own if src == 'meshsimp.hip' or not h.endswith('perf_hip_meshsimp.h')]       # (and the vertex-clustering unit)
-        own = [h for h in own if src == 'meshcolor.hip' or not h.endswith('perf_hip_meshcolor.h')]       # (and the colouring unit,
-        own = own + [h for h in hdrs if src == 'meshcolor.hip' and h.endswith('perf_hip_meshvis.h')]       # whose header includes the cull's for the view descriptor)
-        own = [h for h in own if src == 'meshray.hip' or not h.endswith('perf_hip_meshray.h')]       # (and the ray-casting unit)
-        own = [h for h in own if src in ('mesh.hip', 'brickmesh.hip') or not h.endswith('mesh_device.hpp')]       # (the vertex arithmetic the two share)
-        if not force and _newer(obj, [os.path.join(CSRC, src)] + own):
+        if not force and _newer(obj, _includes(os.path.join(CSRC, src))):
             return obj
         cmd = [hipcc] + FLAGS + ['-c', os.path.join(CSRC, src), '-o', obj]
         if verbose:

@@ -8,11 +8,11 @@
 // skip the same quads, and touches corner values only where a cell is active.
 #include "common.hpp"
 #include "mesh_device.hpp"
+#include "mesh_scan_device.hpp"
 #include "../../include/perf_hip_brickmesh.h"
 
 namespace perf {
 
-constexpr int kBmScanItems = 256;            // items of one workgroup of the scan: one per thread
 constexpr uint64_t kRow0 = 0xffull;                      // cells / corners with j == 0
 constexpr uint64_t kCol0 = 0x0101010101010101ull;        // cells / corners with k == 0
 
@@ -21,60 +21,6 @@ struct BrickDims {
     int32_t bx, by, bz;              // bricks
     int32_t m;                       // live bricks
 };
-
-static inline int64_t bm_scan_words(int64_t n) {
-    int64_t words = 0;
-    do {
-        n = div_up(n, kBmScanItems);
-        words += n;
-    } while (n > 1);
-    return words;
-}
-
-// ---- the scan: exclusive prefix of uint64 words in place, levels of 256 -----------------------------------------------------------------
-__global__ void __launch_bounds__(kBmScanItems) brickmesh_scan_kernel(uint64_t* __restrict__ data, int64_t n, uint64_t* __restrict__ sums) {
-    __shared__ uint64_t wave_sum[kBmScanItems / 64];
-    const int64_t idx = (int64_t)blockIdx.x * kBmScanItems + threadIdx.x;
-    const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t own = idx < n ? data[idx] : 0;
-    uint64_t incl = own;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t up = (uint64_t)__shfl_up((unsigned long long)incl, off);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, total = 0;
-    for (int w = 0; w < kBmScanItems / 64; ++w) {
-        if (w < wave) before += wave_sum[w];
-        total += wave_sum[w];
-    }
-    if (idx < n) data[idx] = before + incl - own;
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(kBmScanItems) brickmesh_scan_add_kernel(uint64_t* __restrict__ data, int64_t n, const uint64_t* __restrict__ prefix) {
-    const int64_t idx = (int64_t)blockIdx.x * kBmScanItems + threadIdx.x;
-    if (idx < n) data[idx] += prefix[blockIdx.x];
-}
-
-// Scans data [n] in place (n >= 1) with its levels in `level` (bm_scan_words(n) words) -> the word that holds the grand total.
-static const uint64_t* bm_scan(uint64_t* data, int64_t n, uint64_t* level, hipStream_t st) {
-    uint64_t* at[8]; int64_t count[8];
-    int levels = 0;
-    at[0] = data; count[0] = n;
-    while (true) {
-        const int64_t blocks = div_up(count[levels], kBmScanItems);
-        hipLaunchKernelGGL(brickmesh_scan_kernel, dim3((unsigned)blocks), dim3(kBmScanItems), 0, st, at[levels], count[levels], level);
-        at[levels + 1] = level; count[levels + 1] = blocks;
-        level += blocks;
-        ++levels;
-        if (blocks == 1) break;
-    }
-    for (int l = levels - 2; l >= 0; --l)
-        hipLaunchKernelGGL(brickmesh_scan_add_kernel, dim3((unsigned)count[l + 1]), dim3(kBmScanItems), 0, st, at[l], count[l], at[l + 1]);
-    return at[levels];
-}
 
 // ---- which bricks are live --------------------------------------------------------------------------------------------------------------
 // x01 of lattice corner i of n: fl32(fl32(i) * fl32(1 / n)) -- what density_lattice's `ijk.float() / float(res)` evaluates to on the
@@ -390,11 +336,7 @@ static int bm_occ_check(const char* who, const uint8_t* binaries, int32_t occ_re
 }
 
 static int bm_workspace_check(const char* who, int32_t nx, int32_t ny, int32_t nz, int32_t n_bricks, const void* workspace, int64_t workspace_bytes) {
-    PERF_REQUIRE(workspace, "%s: NULL workspace", who);
-    PERF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
-    const int64_t need = perf_brickmesh_workspace_bytes(nx, ny, nz, n_bricks);
-    PERF_REQUIRE(workspace_bytes >= need, "%s: the workspace holds %lld bytes, %lld are needed", who, (long long)workspace_bytes, (long long)need);
-    return PERF_OK;
+    return workspace_check(who, perf_brickmesh_workspace_bytes(nx, ny, nz, n_bricks), workspace, workspace_bytes);
 }
 
 static int bm_levels_check(const char* who, float thr, float fill) {
@@ -416,9 +358,9 @@ extern "C" int64_t perf_brickmesh_workspace_bytes(int32_t nx, int32_t ny, int32_
     if (bm_dims_check("perf_brickmesh_workspace_bytes", nx, ny, nz) != PERF_OK) return -1;
     if (bm_bricks_check("perf_brickmesh_workspace_bytes", nx, ny, nz, n_bricks) != PERF_OK) return -1;
     const int64_t groups = div_up((int64_t)(nx / 8) * (ny / 8) * (nz / 8), 256);
-    const int64_t select = groups + bm_scan_words(groups);
+    const int64_t select = groups + scan_words(groups);
     const int64_t slabs = 8 * (int64_t)n_bricks;
-    const int64_t count = n_bricks > 0 ? 3 * slabs + 2 * bm_scan_words(slabs) + 4 : 4;
+    const int64_t count = n_bricks > 0 ? 3 * slabs + 2 * scan_words(slabs) + 4 : 4;
     const int64_t words = select > count ? select : count;
     return ((words + 1) & ~(int64_t)1) * (int64_t)sizeof(uint64_t);      // (a multiple of 16)
 }
@@ -433,7 +375,7 @@ extern "C" int perf_brickmesh_select(const uint8_t* binaries, int32_t occ_res, i
     const int64_t all = (int64_t)d.bx * d.by * d.bz, groups = div_up(all, 256);
     uint64_t* sums = (uint64_t*)workspace;
     hipLaunchKernelGGL(brickmesh_select_kernel, dim3((unsigned)groups), dim3(256), 0, as_stream(stream), binaries, occ_res, d, all, table, sums);
-    const uint64_t* total = bm_scan(sums, groups, sums + groups, as_stream(stream));
+    const uint64_t* total = scan_u64(sums, groups, sums + groups, as_stream(stream));
     hipLaunchKernelGGL(brickmesh_select_add_kernel, dim3((unsigned)groups), dim3(256), 0, as_stream(stream), table, all, (const uint64_t*)sums, total, n_live_dev);
     PERF_LAUNCH_CHECK("perf_brickmesh_select");
     return PERF_OK;
@@ -484,14 +426,14 @@ extern "C" int perf_brickmesh_count(const float* values, const int32_t* ids, con
     uint64_t* ranks = masks + slabs;
     uint64_t* violations = ranks + slabs;
     uint64_t* level = violations + slabs;
-    const int64_t level_words = n_bricks > 0 ? bm_scan_words(slabs) : 0;
+    const int64_t level_words = n_bricks > 0 ? scan_words(slabs) : 0;
     int64_t* totals = (int64_t*)(level + 2 * level_words);
     const uint64_t *packed_total = nullptr, *violation_total = nullptr;
     if (n_bricks > 0) {
         hipLaunchKernelGGL(brickmesh_count_kernel, dim3((unsigned)div_up(slabs, 4)), dim3(256), 0, as_stream(stream), set, d, thr, fill, slabs, masks, ranks,
                            violations);
-        packed_total = bm_scan(ranks, slabs, level, as_stream(stream));
-        violation_total = bm_scan(violations, slabs, level + level_words, as_stream(stream));
+        packed_total = scan_u64(ranks, slabs, level, as_stream(stream));
+        violation_total = scan_u64(violations, slabs, level + level_words, as_stream(stream));
     }
     hipLaunchKernelGGL(brickmesh_totals_kernel, dim3(1), dim3(64), 0, as_stream(stream), packed_total, violation_total, totals, counts_dev);
     PERF_LAUNCH_CHECK("perf_brickmesh_count");
@@ -517,7 +459,7 @@ extern "C" int perf_brickmesh_write(const float* values, const int32_t* ids, con
     const int64_t slabs = 8 * (int64_t)n_bricks;
     const uint64_t* masks = (const uint64_t*)workspace;
     const uint64_t* ranks = masks + slabs;
-    const int64_t level_words = n_bricks > 0 ? bm_scan_words(slabs) : 0;
+    const int64_t level_words = n_bricks > 0 ? scan_words(slabs) : 0;
     const int64_t* totals_dev = (const int64_t*)(ranks + 2 * slabs + 2 * level_words);
     int64_t totals[4] = {0, 0, 0, 0};
     if (hipMemcpyAsync(totals, totals_dev, sizeof(totals), hipMemcpyDeviceToHost, as_stream(stream)) != hipSuccess ||

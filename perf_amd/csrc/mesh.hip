@@ -8,28 +8,18 @@
 // only where a cell is active.
 #include "common.hpp"
 #include "mesh_device.hpp"
+#include "mesh_scan_device.hpp"
 #include "../../include/perf_hip_mesh.h"
 
 namespace perf {
 
 constexpr int kStrip = 8;            // cell rows (consecutive j) per wave of the count pass
-constexpr int kScanItems = 256;      // items of one workgroup of the scan: one per thread
 
 struct MeshDims {
     int32_t nx, ny, nz, cz;          // cells per axis; chunks per row
 };
 
 static inline int64_t chunks_of(int32_t nx, int32_t ny, int32_t nz) { return (int64_t)nx * ny * div_up(nz, 64); }
-
-// words of the scan levels above the chunks: n1 = ceil(C / 256), n2 = ceil(n1 / 256), ... down to a level of one word (the total)
-static inline int64_t scan_words(int64_t chunks) {
-    int64_t words = 0, n = chunks;
-    do {
-        n = div_up(n, kScanItems);
-        words += n;
-    } while (n > 1);
-    return words;
-}
 
 __global__ void __launch_bounds__(256) mesh_count_kernel(const float* __restrict__ field, MeshDims d, float thr, int64_t n_strips, uint64_t* __restrict__ masks,
                                                          uint64_t* __restrict__ ranks) {
@@ -86,41 +76,17 @@ __global__ void __launch_bounds__(256) mesh_count_kernel(const float* __restrict
     }
 }
 
-// One level of the scan: the exclusive prefix of each run of 256 words in place, the run's sum to sums[block].  The packed halves never
-// carry into each other (at most 2^30 vertices, 3 * 2^30 quads).  totals != NULL (the level of one workgroup): the grand total, unpacked.
-__global__ void __launch_bounds__(kScanItems) mesh_scan_kernel(uint64_t* __restrict__ data, int64_t n, uint64_t* __restrict__ sums, int64_t* __restrict__ totals_ws,
-                                                               int64_t* __restrict__ counts_dev) {
-    __shared__ uint64_t wave_sum[kScanItems / 64];
-    const int64_t idx = (int64_t)blockIdx.x * kScanItems + threadIdx.x;
-    const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t own = idx < n ? data[idx] : 0;
-    uint64_t incl = own;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t up = (uint64_t)__shfl_up((unsigned long long)incl, off);
-        if (lane >= off) incl += up;
+// What the scan's top level does with the grand total of the packed words: (vertices, triangles) unpacked, to the workspace and to the
+// caller.  The packed halves never carry into each other (at most 2^30 vertices, 3 * 2^30 quads).
+struct MeshTotalsTail {
+    int64_t* totals_ws;
+    int64_t* counts_dev;
+    __device__ void operator()(uint64_t total) const {
+        const int64_t v = (int64_t)(total & 0xffffffffull), t = 2 * (int64_t)(total >> 32);
+        totals_ws[0] = v; totals_ws[1] = t;
+        counts_dev[0] = v; counts_dev[1] = t;
     }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, total = 0;
-    for (int w = 0; w < kScanItems / 64; ++w) {
-        if (w < wave) before += wave_sum[w];
-        total += wave_sum[w];
-    }
-    if (idx < n) data[idx] = before + incl - own;
-    if (threadIdx.x == 0) {
-        sums[blockIdx.x] = total;
-        if (totals_ws) {
-            const int64_t v = (int64_t)(total & 0xffffffffull), t = 2 * (int64_t)(total >> 32);
-            totals_ws[0] = v; totals_ws[1] = t;
-            counts_dev[0] = v; counts_dev[1] = t;
-        }
-    }
-}
-
-__global__ void __launch_bounds__(kScanItems) mesh_scan_add_kernel(uint64_t* __restrict__ data, int64_t n, const uint64_t* __restrict__ prefix) {
-    const int64_t idx = (int64_t)blockIdx.x * kScanItems + threadIdx.x;
-    if (idx < n) data[idx] += prefix[blockIdx.x];
-}
+};
 
 __device__ __forceinline__ int32_t rank_of(const uint64_t* __restrict__ masks, const uint64_t* __restrict__ ranks, const MeshDims& d, int32_t i, int32_t j, int32_t k) {
     const int64_t ch = ((int64_t)i * d.ny + j) * d.cz + (k >> 6);
@@ -215,11 +181,7 @@ static int mesh_dims_check(const char* who, int32_t nx, int32_t ny, int32_t nz) 
 }
 
 static int mesh_workspace_check(const char* who, int32_t nx, int32_t ny, int32_t nz, const void* workspace, int64_t workspace_bytes) {
-    PERF_REQUIRE(workspace, "%s: NULL workspace", who);
-    PERF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
-    const int64_t need = perf_mesh_workspace_bytes(nx, ny, nz);
-    PERF_REQUIRE(workspace_bytes >= need, "%s: the workspace holds %lld bytes, %lld are needed", who, (long long)workspace_bytes, (long long)need);
-    return PERF_OK;
+    return workspace_check(who, perf_mesh_workspace_bytes(nx, ny, nz), workspace, workspace_bytes);
 }
 
 }  // namespace perf
@@ -249,23 +211,7 @@ extern "C" int perf_mesh_count(const float* field, int32_t nx, int32_t ny, int32
     int64_t* totals = (int64_t*)(level + scan_words(chunks));
     const int64_t n_strips = (int64_t)nx * div_up(ny, kStrip) * d.cz;
     hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)div_up(n_strips, 4)), dim3(256), 0, as_stream(stream), field, d, thr, n_strips, masks, ranks);
-    // up the levels: each level's runs of 256 are scanned in place and their sums become the next level; the level of one word is the total
-    uint64_t* data[8]; int64_t count[8];
-    int levels = 0;
-    data[0] = ranks; count[0] = chunks;
-    while (true) {
-        const int64_t blocks = div_up(count[levels], kScanItems);
-        const bool top = blocks == 1;
-        hipLaunchKernelGGL(mesh_scan_kernel, dim3((unsigned)blocks), dim3(kScanItems), 0, as_stream(stream), data[levels], count[levels], level,
-                           top ? totals : (int64_t*)nullptr, counts_dev);
-        data[levels + 1] = level; count[levels + 1] = blocks;
-        level += blocks;
-        ++levels;
-        if (top) break;
-    }
-    // and down again: a level's run takes the prefix of its sum (the level under the top has one run, whose prefix is zero)
-    for (int l = levels - 2; l >= 0; --l)
-        hipLaunchKernelGGL(mesh_scan_add_kernel, dim3((unsigned)count[l + 1]), dim3(kScanItems), 0, as_stream(stream), data[l], count[l], data[l + 1]);
+    scan_u64(ranks, chunks, level, as_stream(stream), MeshTotalsTail{totals, counts_dev});
     PERF_LAUNCH_CHECK("perf_mesh_count");
     return PERF_OK;
 }

@@ -3,28 +3,13 @@
 // the value it returned, every read of a parent is an agent-scope relaxed atomic load (the header has the termination argument).
 // The roots' launch jumps pointers the same way; everything after it reads what an ended launch wrote, with plain loads.
 #include "common.hpp"
+#include "mesh_filter_device.hpp"
 #include "../../include/perf_hip_meshcc.h"
 
 namespace perf {
 
-constexpr int kCcGroup = 256;                // items of one workgroup: one per thread; the scan's fan-in
+constexpr int kCcGroup = kScanGroup;         // items of one workgroup: one per thread (group_rank's workgroup)
 constexpr int kCcPerThread = 16;             // stats, smallest: items one thread takes before the workgroup's flush
-
-static inline int64_t cc_scan_words(int64_t n) {
-    int64_t words = 0;
-    do {
-        n = div_up(n, kCcGroup);
-        words += n;
-    } while (n > 1);
-    return words;
-}
-
-// S(n) of the header: the groups' counts and the levels of their scan
-static inline int64_t cc_group_words(int64_t n) {
-    if (n == 0) return 0;
-    const int64_t groups = div_up(n, kCcGroup);
-    return groups + cc_scan_words(groups);
-}
 
 struct CcLayout {
     int32_t* a;              // [V] the parents' keys; then each root's smallest vertex; then the ranks within their groups of the components'
@@ -40,71 +25,9 @@ static inline CcLayout cc_layout(void* workspace, int64_t n_vertices, int64_t n_
     l.a = (int32_t*)workspace;
     l.b = l.a + n_vertices;
     l.vsums = (uint64_t*)workspace + n_vertices;
-    l.fsums = l.vsums + cc_group_words(n_vertices);
-    l.totals = (int64_t*)(l.fsums + cc_group_words(n_faces));
+    l.fsums = l.vsums + group_words(n_vertices);
+    l.totals = (int64_t*)(l.fsums + group_words(n_faces));
     return l;
-}
-
-// ---- the scan: exclusive prefix of uint64 words in place, levels of 256 (the brick mesher's, restated for this unit) --------------------
-__global__ void __launch_bounds__(kCcGroup) meshcc_scan_kernel(uint64_t* __restrict__ data, int64_t n, uint64_t* __restrict__ sums) {
-    __shared__ uint64_t wave_sum[kCcGroup / 64];
-    const int64_t idx = (int64_t)blockIdx.x * kCcGroup + threadIdx.x;
-    const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t own = idx < n ? data[idx] : 0;
-    uint64_t incl = own;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t up = (uint64_t)__shfl_up((unsigned long long)incl, off);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, total = 0;
-    for (int w = 0; w < kCcGroup / 64; ++w) {
-        if (w < wave) before += wave_sum[w];
-        total += wave_sum[w];
-    }
-    if (idx < n) data[idx] = before + incl - own;
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(kCcGroup) meshcc_scan_add_kernel(uint64_t* __restrict__ data, int64_t n, const uint64_t* __restrict__ prefix) {
-    const int64_t idx = (int64_t)blockIdx.x * kCcGroup + threadIdx.x;
-    if (idx < n) data[idx] += prefix[blockIdx.x];
-}
-
-// Scans data [n] in place (n >= 1) with its levels in `level` (cc_scan_words(n) words) -> the word that holds the grand total.
-static const uint64_t* cc_scan(uint64_t* data, int64_t n, uint64_t* level, hipStream_t st) {
-    uint64_t* at[8]; int64_t count[8];
-    int levels = 0;
-    at[0] = data; count[0] = n;
-    while (true) {
-        const int64_t blocks = div_up(count[levels], kCcGroup);
-        hipLaunchKernelGGL(meshcc_scan_kernel, dim3((unsigned)blocks), dim3(kCcGroup), 0, st, at[levels], count[levels], level);
-        at[levels + 1] = level; count[levels + 1] = blocks;
-        level += blocks;
-        ++levels;
-        if (blocks == 1) break;
-    }
-    for (int l = levels - 2; l >= 0; --l)
-        hipLaunchKernelGGL(meshcc_scan_add_kernel, dim3((unsigned)count[l + 1]), dim3(kCcGroup), 0, st, at[l], count[l], at[l + 1]);
-    return at[levels];
-}
-
-// The rank of a flagged thread among the flagged threads of its workgroup of 256, and the workgroup's count to sums[blockIdx.x].
-// All 256 threads arrive.
-__device__ __forceinline__ int32_t cc_group_rank(bool flag, uint64_t* __restrict__ sums) {
-    __shared__ int32_t wave_sum[kCcGroup / 64];
-    const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t mask = __ballot(flag);
-    if (lane == 0) wave_sum[wave] = __popcll(mask);
-    __syncthreads();
-    int32_t before = 0, total = 0;
-    for (int w = 0; w < kCcGroup / 64; ++w) {
-        if (w < wave) before += wave_sum[w];
-        total += wave_sum[w];
-    }
-    if (sums && threadIdx.x == 0) sums[blockIdx.x] = (uint64_t)total;
-    return before + __popcll(mask & ((1ull << lane) - 1));
 }
 
 // ---- label ------------------------------------------------------------------------------------------------------------------------------
@@ -288,7 +211,7 @@ __global__ void __launch_bounds__(kCcGroup) meshcc_root_rank_kernel(const int32_
                                                                     uint64_t* __restrict__ sums) {
     const int64_t v = (int64_t)blockIdx.x * kCcGroup + threadIdx.x;
     const bool is_root = v < n_vertices && roots[v] == (int32_t)v;
-    const int32_t r = cc_group_rank(is_root, sums);
+    const int32_t r = group_rank(is_root, sums);
     if (v < n_vertices) rank[v] = r;
 }
 
@@ -361,7 +284,7 @@ __global__ void __launch_bounds__(kCcGroup) meshcc_vertex_stats_kernel(const int
     cc_block_flush<false>(run >= 0, run, count, 0.0, nullptr, vertices_per, nullptr);
 }
 
-// ---- filter -----------------------------------------------------------------------------------------------------------------------------
+// ---- filter (the compaction is mesh_filter_device.hpp's, by the two predicates below) -----------------------------------------------------
 __device__ __forceinline__ bool cc_vertex_kept(const int32_t* __restrict__ vertex_component, const uint8_t* __restrict__ keep, int64_t n_vertices,
                                                int64_t n_components, int64_t v) {
     if (v < 0 || v >= n_vertices) return false;
@@ -378,10 +301,27 @@ __device__ __forceinline__ bool cc_face_kept(const int32_t* __restrict__ faces, 
     return cc_vertex_kept(vertex_component, keep, n_vertices, n_components, abc[0]);
 }
 
+struct CcVertexKept {
+    const int32_t* vertex_component;
+    const uint8_t* keep;
+    int64_t n_vertices, n_components;
+    __device__ __forceinline__ bool operator()(int64_t v) const { return cc_vertex_kept(vertex_component, keep, n_vertices, n_components, v); }
+};
+
+struct CcFaceKept {
+    const int32_t* faces;
+    const int32_t* vertex_component;
+    const uint8_t* keep;
+    int64_t n_faces, n_vertices, n_components;
+    __device__ __forceinline__ bool operator()(int64_t f, int32_t abc[3]) const {
+        return cc_face_kept(faces, vertex_component, keep, n_faces, n_vertices, n_components, f, abc);
+    }
+};
+
 __global__ void __launch_bounds__(kCcGroup) meshcc_keep_vertices_kernel(const int32_t* __restrict__ vertex_component, const uint8_t* __restrict__ keep,
                                                                         int64_t n_vertices, int64_t n_components, uint64_t* __restrict__ sums) {
     const int64_t v = (int64_t)blockIdx.x * kCcGroup + threadIdx.x;
-    cc_group_rank(cc_vertex_kept(vertex_component, keep, n_vertices, n_components, v), sums);
+    group_rank(cc_vertex_kept(vertex_component, keep, n_vertices, n_components, v), sums);
 }
 
 __global__ void __launch_bounds__(kCcGroup) meshcc_keep_faces_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ vertex_component,
@@ -389,45 +329,7 @@ __global__ void __launch_bounds__(kCcGroup) meshcc_keep_faces_kernel(const int32
                                                                      uint64_t* __restrict__ sums) {
     const int64_t f = (int64_t)blockIdx.x * kCcGroup + threadIdx.x;
     int32_t abc[3];
-    cc_group_rank(cc_face_kept(faces, vertex_component, keep, n_faces, n_vertices, n_components, f, abc), sums);
-}
-
-// sums hold the groups' exclusive prefixes now: the new index of every vertex, or -1
-__global__ void __launch_bounds__(kCcGroup) meshcc_new_index_kernel(const int32_t* __restrict__ vertex_component, const uint8_t* __restrict__ keep, int64_t n_vertices,
-                                                                    int64_t n_components, const uint64_t* __restrict__ prefix, int32_t* __restrict__ new_index) {
-    const int64_t v = (int64_t)blockIdx.x * kCcGroup + threadIdx.x;
-    const bool kept = cc_vertex_kept(vertex_component, keep, n_vertices, n_components, v);
-    const int32_t r = cc_group_rank(kept, nullptr);
-    if (v < n_vertices) new_index[v] = kept ? (int32_t)prefix[blockIdx.x] + r : -1;
-}
-
-__global__ void __launch_bounds__(kCcGroup) meshcc_write_vertices_kernel(const int32_t* __restrict__ new_index, int64_t n_vertices, const float* __restrict__ vertices,
-                                                                         float* __restrict__ vertices_out, int32_t* __restrict__ kept_vertex_index,
-                                                                         int64_t vertex_capacity) {
-    const int64_t v = (int64_t)blockIdx.x * kCcGroup + threadIdx.x;
-    if (v >= n_vertices) return;
-    const int64_t n = new_index[v];
-    if (n < 0 || n >= vertex_capacity) return;
-    kept_vertex_index[n] = (int32_t)v;
-    if (vertices) {
-        vertices_out[3 * n] = vertices[3 * v];
-        vertices_out[3 * n + 1] = vertices[3 * v + 1];
-        vertices_out[3 * n + 2] = vertices[3 * v + 2];
-    }
-}
-
-__global__ void __launch_bounds__(kCcGroup) meshcc_write_faces_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ vertex_component,
-                                                                      const uint8_t* __restrict__ keep, int64_t n_faces, int64_t n_vertices, int64_t n_components,
-                                                                      const uint64_t* __restrict__ prefix, const int32_t* __restrict__ new_index,
-                                                                      int32_t* __restrict__ faces_out, int64_t face_capacity) {
-    const int64_t f = (int64_t)blockIdx.x * kCcGroup + threadIdx.x;
-    int32_t abc[3];
-    const bool kept = cc_face_kept(faces, vertex_component, keep, n_faces, n_vertices, n_components, f, abc);
-    const int64_t n = (int64_t)prefix[blockIdx.x] + cc_group_rank(kept, nullptr);
-    if (!kept || n >= face_capacity) return;
-    faces_out[3 * n] = new_index[abc[0]];
-    faces_out[3 * n + 1] = new_index[abc[1]];
-    faces_out[3 * n + 2] = new_index[abc[2]];
+    group_rank(cc_face_kept(faces, vertex_component, keep, n_faces, n_vertices, n_components, f, abc), sums);
 }
 
 // ---- the checks of the entry points -------------------------------------------------------------------------------------------------------
@@ -446,14 +348,8 @@ static int cc_components_check(const char* who, int64_t n_components, int64_t n_
 }
 
 static int cc_workspace_check(const char* who, int64_t n_vertices, int64_t n_faces, const void* workspace, int64_t workspace_bytes) {
-    PERF_REQUIRE(workspace, "%s: NULL workspace", who);
-    PERF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
-    const int64_t need = perf_meshcc_workspace_bytes(n_vertices, n_faces);
-    PERF_REQUIRE(workspace_bytes >= need, "%s: the workspace holds %lld bytes, %lld are needed", who, (long long)workspace_bytes, (long long)need);
-    return PERF_OK;
+    return workspace_check(who, perf_meshcc_workspace_bytes(n_vertices, n_faces), workspace, workspace_bytes);
 }
-
-static inline unsigned cc_groups(int64_t n) { return (unsigned)div_up(n, kCcGroup); }
 
 }  // namespace perf
 
@@ -463,7 +359,7 @@ extern "C" int perf_meshcc_version(void) { return PERF_MESHCC_ABI_VERSION; }
 
 extern "C" int64_t perf_meshcc_workspace_bytes(int64_t n_vertices, int64_t n_faces) {
     if (cc_counts_check("perf_meshcc_workspace_bytes", n_vertices, n_faces) != PERF_OK) return -1;
-    const int64_t words = n_vertices + cc_group_words(n_vertices) + cc_group_words(n_faces) + 4;
+    const int64_t words = n_vertices + group_words(n_vertices) + group_words(n_faces) + 4;
     return ((words + 1) & ~(int64_t)1) * (int64_t)sizeof(uint64_t);      // (a multiple of 16)
 }
 
@@ -483,10 +379,10 @@ extern "C" int perf_meshcc_label(const int32_t* faces, int64_t n_faces, int64_t 
     }
     const uint64_t* total = nullptr;
     if (n_vertices > 0) {
-        const unsigned groups = cc_groups(n_vertices);
+        const unsigned groups = scan_groups(n_vertices);
         hipLaunchKernelGGL(meshcc_init_kernel, dim3(groups), dim3(kCcGroup), 0, st, (uint32_t*)l.a, n_vertices);
         if (n_faces > 0)
-            hipLaunchKernelGGL(meshcc_hook_kernel, dim3(cc_groups(n_faces)), dim3(kCcGroup), 0, st, faces, n_faces, n_vertices, (uint32_t*)l.a,
+            hipLaunchKernelGGL(meshcc_hook_kernel, dim3(scan_groups(n_faces)), dim3(kCcGroup), 0, st, faces, n_faces, n_vertices, (uint32_t*)l.a,
                                (unsigned long long*)(l.totals + 1));
         hipLaunchKernelGGL(meshcc_roots_kernel, dim3(groups), dim3(kCcGroup), 0, st, (uint32_t*)l.a, n_vertices, l.b);
         if (hipMemsetAsync(l.a, 0x7f, n_vertices * sizeof(int32_t), st) != hipSuccess) {          // 0x7f7f7f7f: above every index
@@ -497,7 +393,7 @@ extern "C" int perf_meshcc_label(const int32_t* faces, int64_t n_faces, int64_t 
         hipLaunchKernelGGL(meshcc_smallest_kernel, dim3((unsigned)div_up(n_vertices, kCcGroup * kCcPerThread)), dim3(kCcGroup), 0, st, (const int32_t*)l.b, n_vertices, l.a);
         hipLaunchKernelGGL(meshcc_canon_kernel, dim3(groups), dim3(kCcGroup), 0, st, l.b, (const int32_t*)l.a, n_vertices);
         hipLaunchKernelGGL(meshcc_root_rank_kernel, dim3(groups), dim3(kCcGroup), 0, st, (const int32_t*)l.b, n_vertices, l.a, l.vsums);
-        total = cc_scan(l.vsums, groups, l.vsums + groups, st);
+        total = scan_u64(l.vsums, groups, l.vsums + groups, st);
         hipLaunchKernelGGL(meshcc_ids_kernel, dim3(groups), dim3(kCcGroup), 0, st, (const int32_t*)l.b, (const int32_t*)l.a, (const uint64_t*)l.vsums, n_vertices,
                            vertex_component);
     } else if (n_faces > 0) {                               // every face is out of range: the first one is the first bad one
@@ -555,15 +451,16 @@ extern "C" int perf_meshcc_filter_count(const int32_t* faces, int64_t n_faces, c
     hipStream_t st = as_stream(stream);
     const uint64_t *v_total = nullptr, *f_total = nullptr;
     if (n_vertices > 0) {
-        const unsigned groups = cc_groups(n_vertices);
+        const unsigned groups = scan_groups(n_vertices);
         hipLaunchKernelGGL(meshcc_keep_vertices_kernel, dim3(groups), dim3(kCcGroup), 0, st, vertex_component, keep, n_vertices, n_components, l.vsums);
-        v_total = cc_scan(l.vsums, groups, l.vsums + groups, st);
-        hipLaunchKernelGGL(meshcc_new_index_kernel, dim3(groups), dim3(kCcGroup), 0, st, vertex_component, keep, n_vertices, n_components, (const uint64_t*)l.vsums, l.a);
+        v_total = scan_u64(l.vsums, groups, l.vsums + groups, st);
+        hipLaunchKernelGGL(filter_new_index_kernel<CcVertexKept>, dim3(groups), dim3(kCcGroup), 0, st, CcVertexKept{vertex_component, keep, n_vertices, n_components},
+                           (const uint64_t*)l.vsums, l.a);
     }
     if (n_faces > 0) {
-        const unsigned groups = cc_groups(n_faces);
+        const unsigned groups = scan_groups(n_faces);
         hipLaunchKernelGGL(meshcc_keep_faces_kernel, dim3(groups), dim3(kCcGroup), 0, st, faces, vertex_component, keep, n_faces, n_vertices, n_components, l.fsums);
-        f_total = cc_scan(l.fsums, groups, l.fsums + groups, st);
+        f_total = scan_u64(l.fsums, groups, l.fsums + groups, st);
     }
     hipLaunchKernelGGL(meshcc_totals_kernel, dim3(1), dim3(64), 0, st, v_total, f_total, false, l.totals, counts_dev);
     PERF_LAUNCH_CHECK("perf_meshcc_filter_count");
@@ -588,11 +485,11 @@ extern "C" int perf_meshcc_filter_write(const int32_t* faces, int64_t n_faces, c
     PERF_REQUIRE(vertex_capacity >= totals[0], "perf_meshcc_filter_write: room for %lld vertices, %lld were counted", (long long)vertex_capacity, (long long)totals[0]);
     PERF_REQUIRE(face_capacity >= totals[1], "perf_meshcc_filter_write: room for %lld faces, %lld were counted", (long long)face_capacity, (long long)totals[1]);
     if (totals[0] == 0) return PERF_OK;                     // (no kept vertex: no kept face either)
-    hipLaunchKernelGGL(meshcc_write_vertices_kernel, dim3(cc_groups(n_vertices)), dim3(kCcGroup), 0, st, (const int32_t*)l.a, n_vertices, vertices, vertices_out,
+    hipLaunchKernelGGL(filter_write_vertices_kernel, dim3(scan_groups(n_vertices)), dim3(kCcGroup), 0, st, (const int32_t*)l.a, n_vertices, vertices, vertices_out,
                        kept_vertex_index, vertex_capacity);
     if (totals[1] > 0)
-        hipLaunchKernelGGL(meshcc_write_faces_kernel, dim3(cc_groups(n_faces)), dim3(kCcGroup), 0, st, faces, vertex_component, keep, n_faces, n_vertices, n_components,
-                           (const uint64_t*)l.fsums, (const int32_t*)l.a, faces_out, face_capacity);
+        hipLaunchKernelGGL(filter_write_faces_kernel<CcFaceKept>, dim3(scan_groups(n_faces)), dim3(kCcGroup), 0, st,
+                           CcFaceKept{faces, vertex_component, keep, n_faces, n_vertices, n_components}, (const uint64_t*)l.fsums, (const int32_t*)l.a, faces_out, face_capacity);
     PERF_LAUNCH_CHECK("perf_meshcc_filter_write");
     return PERF_OK;
 }

@@ -3,11 +3,12 @@
 // by one compare-and-swap and only falls afterwards, by atomicMin of members of the same key; a failed compare-and-swap goes on from the
 // value it returned; the occupant's key is read from an array an earlier launch wrote (the header has the argument).
 #include "common.hpp"
+#include "mesh_scan_device.hpp"
 #include "../../include/perf_hip_meshsimp.h"
 
 namespace perf {
 
-constexpr int kSgGroup = 256;                // items of one workgroup: one per thread; the scan's fan-in
+constexpr int kSgGroup = kScanGroup;         // items of one workgroup: one per thread (group_rank's workgroup)
 constexpr int kSgPlaceGroup = 1024;          // sums, nearest: a workgroup of 16 waves joins its waves' runs before the atomics
 constexpr int kSgBoundsPerThread = 8;        // bounds: vertices one thread takes before the wave's six atomics
 constexpr uint32_t kSgEmpty = 0xffffffffu;
@@ -18,22 +19,6 @@ struct SgGrid {
     double h;
     int32_t n[3];
 };
-
-static inline int64_t sg_scan_words(int64_t n) {
-    int64_t words = 0;
-    do {
-        n = div_up(n, kSgGroup);
-        words += n;
-    } while (n > 1);
-    return words;
-}
-
-// S(n) of the header: the groups' counts and the levels of their scan
-static inline int64_t sg_group_words(int64_t n) {
-    if (n == 0) return 0;
-    const int64_t groups = div_up(n, kSgGroup);
-    return groups + sg_scan_words(groups);
-}
 
 // T(n) of the header, as its log2
 static inline int sg_table_bits(int64_t n) {
@@ -59,7 +44,7 @@ static inline SgLayout sg_layout(void* workspace, int64_t n_vertices, int64_t n_
     const uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
     int64_t at = 0;
     l.keys = reinterpret_cast<int64_t*>(base + at);       at += 8 * n_vertices;
-    l.vsums = reinterpret_cast<uint64_t*>(base + at);     at += 8 * sg_group_words(n_vertices);
+    l.vsums = reinterpret_cast<uint64_t*>(base + at);     at += 8 * group_words(n_vertices);
     l.totals = reinterpret_cast<int64_t*>(base + at);     at += 8 * 4;
     l.slot = reinterpret_cast<uint32_t*>(base + at);      at += 4 * n_vertices;
     l.smallest = reinterpret_cast<int32_t*>(base + at);   at += 4 * n_vertices;
@@ -68,68 +53,6 @@ static inline SgLayout sg_layout(void* workspace, int64_t n_vertices, int64_t n_
     l.ftable = reinterpret_cast<uint32_t*>(base + at);    at += 4 * ((int64_t)1 << sg_table_bits(n_faces));
     l.bytes = (at + 15) & ~(int64_t)15;
     return l;
-}
-
-// ---- the scan: exclusive prefix of uint64 words in place, levels of 256 (the component unit's, restated for this unit) ---------------------
-__global__ void __launch_bounds__(kSgGroup) meshsimp_scan_kernel(uint64_t* __restrict__ data, int64_t n, uint64_t* __restrict__ sums) {
-    __shared__ uint64_t wave_sum[kSgGroup / 64];
-    const int64_t idx = (int64_t)blockIdx.x * kSgGroup + threadIdx.x;
-    const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t own = idx < n ? data[idx] : 0;
-    uint64_t incl = own;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t up = (uint64_t)__shfl_up((unsigned long long)incl, off);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, total = 0;
-    for (int w = 0; w < kSgGroup / 64; ++w) {
-        if (w < wave) before += wave_sum[w];
-        total += wave_sum[w];
-    }
-    if (idx < n) data[idx] = before + incl - own;
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(kSgGroup) meshsimp_scan_add_kernel(uint64_t* __restrict__ data, int64_t n, const uint64_t* __restrict__ prefix) {
-    const int64_t idx = (int64_t)blockIdx.x * kSgGroup + threadIdx.x;
-    if (idx < n) data[idx] += prefix[blockIdx.x];
-}
-
-// Scans data [n] in place (n >= 1) with its levels in `level` (sg_scan_words(n) words) -> the word that holds the grand total.
-static const uint64_t* sg_scan(uint64_t* data, int64_t n, uint64_t* level, hipStream_t st) {
-    uint64_t* at[8]; int64_t count[8];
-    int levels = 0;
-    at[0] = data; count[0] = n;
-    while (true) {
-        const int64_t blocks = div_up(count[levels], kSgGroup);
-        hipLaunchKernelGGL(meshsimp_scan_kernel, dim3((unsigned)blocks), dim3(kSgGroup), 0, st, at[levels], count[levels], level);
-        at[levels + 1] = level; count[levels + 1] = blocks;
-        level += blocks;
-        ++levels;
-        if (blocks == 1) break;
-    }
-    for (int l = levels - 2; l >= 0; --l)
-        hipLaunchKernelGGL(meshsimp_scan_add_kernel, dim3((unsigned)count[l + 1]), dim3(kSgGroup), 0, st, at[l], count[l], at[l + 1]);
-    return at[levels];
-}
-
-// The rank of a flagged thread among the flagged threads of its workgroup of 256, and the workgroup's count to sums[blockIdx.x].
-// All 256 threads arrive.
-__device__ __forceinline__ int32_t sg_group_rank(bool flag, uint64_t* __restrict__ sums) {
-    __shared__ int32_t wave_sum[kSgGroup / 64];
-    const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t mask = __ballot(flag);
-    if (lane == 0) wave_sum[wave] = __popcll(mask);
-    __syncthreads();
-    int32_t before = 0, total = 0;
-    for (int w = 0; w < kSgGroup / 64; ++w) {
-        if (w < wave) before += wave_sum[w];
-        total += wave_sum[w];
-    }
-    if (sums && threadIdx.x == 0) sums[blockIdx.x] = (uint64_t)total;
-    return before + __popcll(mask & ((1ull << lane) - 1));
 }
 
 // ---- runs of one id along a wave ------------------------------------------------------------------------------------------------------------
@@ -304,7 +227,7 @@ __global__ void __launch_bounds__(kSgGroup) meshsimp_smallest_kernel(const int64
         s = table[slot_then_rank[v]];
         if (s > v) s = v;                                   // (s is in [0, v]: v itself took part in the minimum)
     }
-    const int32_t r = sg_group_rank(s == v && v < n_vertices, sums);
+    const int32_t r = group_rank(s == v && v < n_vertices, sums);
     if (v < n_vertices) {
         smallest[v] = (int32_t)s;
         slot_then_rank[v] = (uint32_t)r;
@@ -516,14 +439,8 @@ static int sg_grid_check(const char* who, const float* lo, float h, int32_t nx, 
 }
 
 static int sg_workspace_check(const char* who, int64_t n_vertices, int64_t n_faces, const void* workspace, int64_t workspace_bytes) {
-    PERF_REQUIRE(workspace, "%s: NULL workspace", who);
-    PERF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
-    const int64_t need = perf_meshsimp_workspace_bytes(n_vertices, n_faces);
-    PERF_REQUIRE(workspace_bytes >= need, "%s: the workspace holds %lld bytes, %lld are needed", who, (long long)workspace_bytes, (long long)need);
-    return PERF_OK;
+    return workspace_check(who, perf_meshsimp_workspace_bytes(n_vertices, n_faces), workspace, workspace_bytes);
 }
-
-static inline unsigned sg_groups(int64_t n) { return (unsigned)div_up(n, kSgGroup); }
 
 }  // namespace perf
 
@@ -579,12 +496,12 @@ extern "C" int perf_meshsimp_cluster(const float* vertices, int64_t n_vertices, 
     }
     const uint64_t* total = nullptr;
     if (n_vertices > 0) {
-        const unsigned groups = sg_groups(n_vertices);
+        const unsigned groups = scan_groups(n_vertices);
         hipLaunchKernelGGL(meshsimp_keys_kernel, dim3(groups), dim3(kSgGroup), 0, st, vertices, n_vertices, grid, l.keys, (unsigned long long*)(l.totals + 1));
         hipLaunchKernelGGL(meshsimp_insert_cells_kernel, dim3(groups), dim3(kSgGroup), 0, st, (const int64_t*)l.keys, n_vertices, l.vtable, bits, l.slot);
         hipLaunchKernelGGL(meshsimp_smallest_kernel, dim3(groups), dim3(kSgGroup), 0, st, (const int64_t*)l.keys, (const uint32_t*)l.vtable, n_vertices, l.slot,
                            l.smallest, l.vsums);
-        total = sg_scan(l.vsums, groups, l.vsums + groups, st);
+        total = scan_u64(l.vsums, groups, l.vsums + groups, st);
         hipLaunchKernelGGL(meshsimp_ids_kernel, dim3(groups), dim3(kSgGroup), 0, st, (const int32_t*)l.smallest, (const uint32_t*)l.slot, (const uint64_t*)l.vsums,
                            n_vertices, vertex_cluster);
     }
@@ -617,7 +534,7 @@ extern "C" int perf_meshsimp_place(const float* vertices, int64_t n_vertices, co
         set_error("perf_meshsimp_place: clearing the scratch failed");
         return PERF_E_LAUNCH;
     }
-    const unsigned vgroups = sg_groups(n_vertices), cgroups = sg_groups(n_clusters), pgroups = (unsigned)div_up(n_vertices, kSgPlaceGroup);
+    const unsigned vgroups = scan_groups(n_vertices), cgroups = scan_groups(n_clusters), pgroups = (unsigned)div_up(n_vertices, kSgPlaceGroup);
     hipLaunchKernelGGL(meshsimp_sums_kernel, dim3(pgroups), dim3(kSgPlaceGroup), 0, st, vertices, n_vertices, grid, vertex_cluster, n_clusters, s);
     hipLaunchKernelGGL(meshsimp_mean_kernel, dim3(cgroups), dim3(kSgGroup), 0, st, grid, n_clusters, s, placement, cluster_vertices, representative);
     hipLaunchKernelGGL(meshsimp_nearest_kernel, dim3(pgroups), dim3(kSgPlaceGroup), 0, st, vertices, n_vertices, vertex_cluster, n_clusters, s);
@@ -648,7 +565,7 @@ extern "C" int perf_meshsimp_faces(const int32_t* faces, int64_t n_faces, const 
         return PERF_E_LAUNCH;
     }
     if (n_faces > 0) {
-        const unsigned groups = sg_groups(n_faces);
+        const unsigned groups = scan_groups(n_faces);
         hipLaunchKernelGGL(meshsimp_remap_kernel, dim3(groups), dim3(kSgGroup), 0, st, faces, n_faces, vertex_cluster, n_vertices, faces_out, face_keep,
                            (unsigned long long*)bad_face_dev);
         if (dedupe == PERF_MESHSIMP_DEDUPE_ORIENTED)

@@ -1,12 +1,13 @@
 // Cull the faces of a mesh no registered panorama saw (include/perf_hip_meshvis.h): vertex bits (one launch for all views) -> face rule ->
 // compaction by the face mask (mark -> rank -> scan -> write).  The look-up of stage 1 is the arithmetic of pano_reproject_kernel
-// (visibility.hip) restated line for line; the scan and the group rank are the component unit's, restated for this unit.
+// (visibility.hip) restated line for line; the scan and the group rank are mesh_scan_device.hpp's, the compaction mesh_filter_device.hpp's.
 #include "common.hpp"
+#include "mesh_filter_device.hpp"
 #include "../../include/perf_hip_meshvis.h"
 
 namespace perf {
 
-constexpr int kVisGroup = 256;               // items of one workgroup: one per thread; the scan's fan-in
+constexpr int kVisGroup = kScanGroup;        // items of one workgroup: one per thread (group_rank's workgroup)
 constexpr int kVisViewWords = sizeof(perf_meshvis_view) / 4;
 static_assert(sizeof(perf_meshvis_view) == 64 && alignof(perf_meshvis_view) == 8, "the view descriptor is 64 bytes");
 
@@ -117,23 +118,7 @@ __global__ void __launch_bounds__(kVisGroup) meshvis_face_keep_kernel(const int3
     face_keep[f] = keep ? 1 : 0;
 }
 
-// ---- stage 3: the scan and the group rank (the component unit's, restated) --------------------------------------------------------------
-static inline int64_t vis_scan_words(int64_t n) {
-    int64_t words = 0;
-    do {
-        n = div_up(n, kVisGroup);
-        words += n;
-    } while (n > 1);
-    return words;
-}
-
-// S(n) of the header: the groups' counts and the levels of their scan
-static inline int64_t vis_group_words(int64_t n) {
-    if (n == 0) return 0;
-    const int64_t groups = div_up(n, kVisGroup);
-    return groups + vis_scan_words(groups);
-}
-
+// ---- stage 3: the compaction (mesh_filter_device.hpp) by the face mask ---------------------------------------------------------------------
 struct VisLayout {
     int32_t* a;              // [V] 1 where a kept face names the vertex; then the kept vertices' new indices (-1: dropped)
     uint64_t* vsums;         // S(V)
@@ -145,70 +130,9 @@ static inline VisLayout vis_layout(void* workspace, int64_t n_vertices, int64_t 
     VisLayout l;
     l.a = (int32_t*)workspace;
     l.vsums = (uint64_t*)workspace + (n_vertices + 1) / 2;
-    l.fsums = l.vsums + vis_group_words(n_vertices);
-    l.totals = (int64_t*)(l.fsums + vis_group_words(n_faces));
+    l.fsums = l.vsums + group_words(n_vertices);
+    l.totals = (int64_t*)(l.fsums + group_words(n_faces));
     return l;
-}
-
-__global__ void __launch_bounds__(kVisGroup) meshvis_scan_kernel(uint64_t* __restrict__ data, int64_t n, uint64_t* __restrict__ sums) {
-    __shared__ uint64_t wave_sum[kVisGroup / 64];
-    const int64_t idx = (int64_t)blockIdx.x * kVisGroup + threadIdx.x;
-    const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t own = idx < n ? data[idx] : 0;
-    uint64_t incl = own;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t up = (uint64_t)__shfl_up((unsigned long long)incl, off);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, total = 0;
-    for (int w = 0; w < kVisGroup / 64; ++w) {
-        if (w < wave) before += wave_sum[w];
-        total += wave_sum[w];
-    }
-    if (idx < n) data[idx] = before + incl - own;
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(kVisGroup) meshvis_scan_add_kernel(uint64_t* __restrict__ data, int64_t n, const uint64_t* __restrict__ prefix) {
-    const int64_t idx = (int64_t)blockIdx.x * kVisGroup + threadIdx.x;
-    if (idx < n) data[idx] += prefix[blockIdx.x];
-}
-
-// Scans data [n] in place (n >= 1) with its levels in `level` (vis_scan_words(n) words) -> the word that holds the grand total.
-static const uint64_t* vis_scan(uint64_t* data, int64_t n, uint64_t* level, hipStream_t st) {
-    uint64_t* at[8]; int64_t count[8];
-    int levels = 0;
-    at[0] = data; count[0] = n;
-    while (true) {
-        const int64_t blocks = div_up(count[levels], kVisGroup);
-        hipLaunchKernelGGL(meshvis_scan_kernel, dim3((unsigned)blocks), dim3(kVisGroup), 0, st, at[levels], count[levels], level);
-        at[levels + 1] = level; count[levels + 1] = blocks;
-        level += blocks;
-        ++levels;
-        if (blocks == 1) break;
-    }
-    for (int l = levels - 2; l >= 0; --l)
-        hipLaunchKernelGGL(meshvis_scan_add_kernel, dim3((unsigned)count[l + 1]), dim3(kVisGroup), 0, st, at[l], count[l], at[l + 1]);
-    return at[levels];
-}
-
-// The rank of a flagged thread among the flagged threads of its workgroup of 256, and the workgroup's count to sums[blockIdx.x].
-// All 256 threads arrive.
-__device__ __forceinline__ int32_t vis_group_rank(bool flag, uint64_t* __restrict__ sums) {
-    __shared__ int32_t wave_sum[kVisGroup / 64];
-    const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t mask = __ballot(flag);
-    if (lane == 0) wave_sum[wave] = __popcll(mask);
-    __syncthreads();
-    int32_t before = 0, total = 0;
-    for (int w = 0; w < kVisGroup / 64; ++w) {
-        if (w < wave) before += wave_sum[w];
-        total += wave_sum[w];
-    }
-    if (sums && threadIdx.x == 0) sums[blockIdx.x] = (uint64_t)total;
-    return before + __popcll(mask & ((1ull << lane) - 1));
 }
 
 // a face is kept iff the mask says so and its three indices are vertices
@@ -219,6 +143,20 @@ __device__ __forceinline__ bool vis_face_kept(const int32_t* __restrict__ faces,
     return abc[0] >= 0 && abc[0] < n_vertices && abc[1] >= 0 && abc[1] < n_vertices && abc[2] >= 0 && abc[2] < n_vertices;
 }
 
+struct VisFaceKept {
+    const int32_t* faces;
+    const uint8_t* face_keep;
+    int64_t n_faces, n_vertices;
+    __device__ __forceinline__ bool operator()(int64_t f, int32_t abc[3]) const { return vis_face_kept(faces, face_keep, n_faces, n_vertices, f, abc); }
+};
+
+// a vertex is kept iff a kept face marked it
+struct VisVertexKept {
+    const int32_t* marks;
+    int64_t n_vertices;
+    __device__ __forceinline__ bool operator()(int64_t v) const { return v < n_vertices && marks[v] != 0; }
+};
+
 // marks [V] are 0 before the launch: a kept face stores 1 on its three vertices (every store to a word stores the same value); the
 // group's count of kept faces to sums
 __global__ void __launch_bounds__(kVisGroup) meshvis_mark_kernel(const int32_t* __restrict__ faces, const uint8_t* __restrict__ face_keep, int64_t n_faces,
@@ -227,20 +165,12 @@ __global__ void __launch_bounds__(kVisGroup) meshvis_mark_kernel(const int32_t* 
     int32_t abc[3];
     const bool kept = vis_face_kept(faces, face_keep, n_faces, n_vertices, f, abc);
     if (kept) { marks[abc[0]] = 1; marks[abc[1]] = 1; marks[abc[2]] = 1; }
-    vis_group_rank(kept, sums);
+    group_rank(kept, sums);
 }
 
 __global__ void __launch_bounds__(kVisGroup) meshvis_count_vertices_kernel(const int32_t* __restrict__ marks, int64_t n_vertices, uint64_t* __restrict__ sums) {
     const int64_t v = (int64_t)blockIdx.x * kVisGroup + threadIdx.x;
-    vis_group_rank(v < n_vertices && marks[v] != 0, sums);
-}
-
-// sums hold the groups' exclusive prefixes now: every vertex's mark becomes its new index, or -1 (a thread reads and writes its own word)
-__global__ void __launch_bounds__(kVisGroup) meshvis_new_index_kernel(int32_t* marks, int64_t n_vertices, const uint64_t* __restrict__ prefix) {
-    const int64_t v = (int64_t)blockIdx.x * kVisGroup + threadIdx.x;
-    const bool kept = v < n_vertices && marks[v] != 0;
-    const int32_t r = vis_group_rank(kept, nullptr);
-    if (v < n_vertices) marks[v] = kept ? (int32_t)prefix[blockIdx.x] + r : -1;
+    group_rank(v < n_vertices && marks[v] != 0, sums);
 }
 
 __global__ void meshvis_totals_kernel(const uint64_t* __restrict__ first, const uint64_t* __restrict__ second, int64_t* __restrict__ totals,
@@ -249,34 +179,6 @@ __global__ void meshvis_totals_kernel(const uint64_t* __restrict__ first, const 
     const int64_t a = first ? (int64_t)first[0] : 0, b = second ? (int64_t)second[0] : 0;
     totals[0] = a; totals[1] = b; totals[2] = 0; totals[3] = 0;
     counts_dev[0] = a; counts_dev[1] = b;
-}
-
-__global__ void __launch_bounds__(kVisGroup) meshvis_write_vertices_kernel(const int32_t* __restrict__ new_index, int64_t n_vertices, const float* __restrict__ vertices,
-                                                                           float* __restrict__ vertices_out, int32_t* __restrict__ kept_vertex_index,
-                                                                           int64_t vertex_capacity) {
-    const int64_t v = (int64_t)blockIdx.x * kVisGroup + threadIdx.x;
-    if (v >= n_vertices) return;
-    const int64_t n = new_index[v];
-    if (n < 0 || n >= vertex_capacity) return;
-    kept_vertex_index[n] = (int32_t)v;
-    if (vertices) {
-        vertices_out[3 * n] = vertices[3 * v];
-        vertices_out[3 * n + 1] = vertices[3 * v + 1];
-        vertices_out[3 * n + 2] = vertices[3 * v + 2];
-    }
-}
-
-__global__ void __launch_bounds__(kVisGroup) meshvis_write_faces_kernel(const int32_t* __restrict__ faces, const uint8_t* __restrict__ face_keep, int64_t n_faces,
-                                                                        int64_t n_vertices, const uint64_t* __restrict__ prefix, const int32_t* __restrict__ new_index,
-                                                                        int32_t* __restrict__ faces_out, int64_t face_capacity) {
-    const int64_t f = (int64_t)blockIdx.x * kVisGroup + threadIdx.x;
-    int32_t abc[3];
-    const bool kept = vis_face_kept(faces, face_keep, n_faces, n_vertices, f, abc);
-    const int64_t n = (int64_t)prefix[blockIdx.x] + vis_group_rank(kept, nullptr);
-    if (!kept || n >= face_capacity) return;
-    faces_out[3 * n] = new_index[abc[0]];
-    faces_out[3 * n + 1] = new_index[abc[1]];
-    faces_out[3 * n + 2] = new_index[abc[2]];
 }
 
 // ---- the checks of the entry points -------------------------------------------------------------------------------------------------------
@@ -295,11 +197,7 @@ static int vis_views_check(const char* who, int32_t n_views) {
 }
 
 static int vis_workspace_check(const char* who, int64_t n_vertices, int64_t n_faces, const void* workspace, int64_t workspace_bytes) {
-    PERF_REQUIRE(workspace, "%s: NULL workspace", who);
-    PERF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
-    const int64_t need = perf_meshvis_workspace_bytes(n_vertices, n_faces);
-    PERF_REQUIRE(workspace_bytes >= need, "%s: the workspace holds %lld bytes, %lld are needed", who, (long long)workspace_bytes, (long long)need);
-    return PERF_OK;
+    return workspace_check(who, perf_meshvis_workspace_bytes(n_vertices, n_faces), workspace, workspace_bytes);
 }
 
 static int vis_filter_check(const char* who, const int32_t* faces, int64_t n_faces, int64_t n_vertices, const uint8_t* face_keep, const void* workspace,
@@ -309,8 +207,6 @@ static int vis_filter_check(const char* who, const int32_t* faces, int64_t n_fac
     PERF_REQUIRE(face_keep || n_faces == 0, "%s: NULL input (face_keep) with faces to filter", who);
     return vis_workspace_check(who, n_vertices, n_faces, workspace, workspace_bytes);
 }
-
-static inline unsigned vis_groups(int64_t n) { return (unsigned)div_up(n, kVisGroup); }
 
 }  // namespace perf
 
@@ -322,7 +218,7 @@ extern "C" int64_t perf_meshvis_sizeof_view(void) { return (int64_t)sizeof(perf_
 
 extern "C" int64_t perf_meshvis_workspace_bytes(int64_t n_vertices, int64_t n_faces) {
     if (vis_counts_check("perf_meshvis_workspace_bytes", n_vertices, n_faces) != PERF_OK) return -1;
-    const int64_t words = (n_vertices + 1) / 2 + vis_group_words(n_vertices) + vis_group_words(n_faces) + 4;
+    const int64_t words = (n_vertices + 1) / 2 + group_words(n_vertices) + group_words(n_faces) + 4;
     return ((words + 1) & ~(int64_t)1) * (int64_t)sizeof(uint64_t);      // (a multiple of 16)
 }
 
@@ -340,7 +236,7 @@ extern "C" int perf_meshvis_vertex_bits(const float* vertices, int64_t n_vertice
         PERF_REQUIRE(view_sizes[2 * k] >= 1 && view_sizes[2 * k + 1] >= 1, "perf_meshvis_vertex_bits: view %d has a map of %d x %d: a map dimension below 1", k,
                      view_sizes[2 * k], view_sizes[2 * k + 1]);
     if (n_vertices == 0) return PERF_OK;
-    hipLaunchKernelGGL(meshvis_vertex_bits_kernel, dim3(vis_groups(n_vertices)), dim3(kVisGroup), 0, as_stream(stream), vertices, n_vertices, views_dev, n_views, tol,
+    hipLaunchKernelGGL(meshvis_vertex_bits_kernel, dim3(scan_groups(n_vertices)), dim3(kVisGroup), 0, as_stream(stream), vertices, n_vertices, views_dev, n_views, tol,
                        -free_tol, (unsigned long long*)visible_bits, (unsigned long long*)free_bits);
     PERF_LAUNCH_CHECK("perf_meshvis_vertex_bits");
     return PERF_OK;
@@ -367,7 +263,7 @@ extern "C" int perf_meshvis_face_keep(const int32_t* faces, int64_t n_faces, con
         return PERF_E_LAUNCH;
     }
     if (n_faces > 0)
-        hipLaunchKernelGGL(meshvis_face_keep_kernel, dim3(vis_groups(n_faces)), dim3(kVisGroup), 0, st, faces, n_faces, vertices, n_vertices,
+        hipLaunchKernelGGL(meshvis_face_keep_kernel, dim3(scan_groups(n_faces)), dim3(kVisGroup), 0, st, faces, n_faces, vertices, n_vertices,
                            (const unsigned long long*)visible_bits, (const unsigned long long*)free_bits, centres, n_views, facing, min_views, carve, face_keep,
                            (unsigned long long*)bad_face_dev);
     PERF_LAUNCH_CHECK("perf_meshvis_face_keep");
@@ -387,15 +283,15 @@ extern "C" int perf_meshvis_filter_count(const int32_t* faces, int64_t n_faces, 
         return PERF_E_LAUNCH;
     }
     if (n_faces > 0) {
-        const unsigned groups = vis_groups(n_faces);
+        const unsigned groups = scan_groups(n_faces);
         hipLaunchKernelGGL(meshvis_mark_kernel, dim3(groups), dim3(kVisGroup), 0, st, faces, face_keep, n_faces, n_vertices, l.a, l.fsums);
-        f_total = vis_scan(l.fsums, groups, l.fsums + groups, st);
+        f_total = scan_u64(l.fsums, groups, l.fsums + groups, st);
     }
     if (n_vertices > 0) {
-        const unsigned groups = vis_groups(n_vertices);
+        const unsigned groups = scan_groups(n_vertices);
         hipLaunchKernelGGL(meshvis_count_vertices_kernel, dim3(groups), dim3(kVisGroup), 0, st, (const int32_t*)l.a, n_vertices, l.vsums);
-        v_total = vis_scan(l.vsums, groups, l.vsums + groups, st);
-        hipLaunchKernelGGL(meshvis_new_index_kernel, dim3(groups), dim3(kVisGroup), 0, st, l.a, n_vertices, (const uint64_t*)l.vsums);
+        v_total = scan_u64(l.vsums, groups, l.vsums + groups, st);
+        hipLaunchKernelGGL(filter_new_index_kernel<VisVertexKept>, dim3(groups), dim3(kVisGroup), 0, st, VisVertexKept{l.a, n_vertices}, (const uint64_t*)l.vsums, l.a);
     }
     hipLaunchKernelGGL(meshvis_totals_kernel, dim3(1), dim3(64), 0, st, v_total, f_total, l.totals, counts_dev);
     PERF_LAUNCH_CHECK("perf_meshvis_filter_count");
@@ -420,10 +316,10 @@ extern "C" int perf_meshvis_filter_write(const int32_t* faces, int64_t n_faces, 
     PERF_REQUIRE(vertex_capacity >= totals[0], "perf_meshvis_filter_write: room for %lld vertices, %lld were counted", (long long)vertex_capacity, (long long)totals[0]);
     PERF_REQUIRE(face_capacity >= totals[1], "perf_meshvis_filter_write: room for %lld faces, %lld were counted", (long long)face_capacity, (long long)totals[1]);
     if (totals[0] == 0) return PERF_OK;                     // (no kept vertex: no kept face either)
-    hipLaunchKernelGGL(meshvis_write_vertices_kernel, dim3(vis_groups(n_vertices)), dim3(kVisGroup), 0, st, (const int32_t*)l.a, n_vertices, vertices, vertices_out,
+    hipLaunchKernelGGL(filter_write_vertices_kernel, dim3(scan_groups(n_vertices)), dim3(kVisGroup), 0, st, (const int32_t*)l.a, n_vertices, vertices, vertices_out,
                        kept_vertex_index, vertex_capacity);
     if (totals[1] > 0)
-        hipLaunchKernelGGL(meshvis_write_faces_kernel, dim3(vis_groups(n_faces)), dim3(kVisGroup), 0, st, faces, face_keep, n_faces, n_vertices,
+        hipLaunchKernelGGL(filter_write_faces_kernel<VisFaceKept>, dim3(scan_groups(n_faces)), dim3(kVisGroup), 0, st, VisFaceKept{faces, face_keep, n_faces, n_vertices},
                            (const uint64_t*)l.fsums, (const int32_t*)l.a, faces_out, face_capacity);
     PERF_LAUNCH_CHECK("perf_meshvis_filter_write");
     return PERF_OK;

@@ -162,6 +162,14 @@ def test_all_bricks_live():
     _compare(ids, table, values, virtual, 0.5, 0.0, label='all live (16, 24, 8)')
 
 
+def test_all_bricks_live_with_two_scan_levels():
+    """40 bricks are 320 slabs, more than one scan workgroup's 256: the scan over the slabs takes a second level."""
+    shape = (40, 32, 16)
+    ids, table, values, virtual = _brick_set(_random_field(shape, 6), np.ones((5, 4, 2), dtype=bool), 0.5, 0.0)
+    assert len(ids) == 40 and 8 * len(ids) > 256
+    _compare(ids, table, values, virtual, 0.5, 0.0, label='all live (40, 32, 16)')
+
+
 def _random_half(close):
     shape = (24, 24, 24)
     rng = np.random.default_rng(7)

@@ -129,7 +129,9 @@ def test_the_unit_is_built_with_its_own_header():
     from perf_amd import build
     assert 'meshray.hip' in build.SOURCES and len(set(build.SOURCES)) == len(build.SOURCES)
     text = open(os.path.join(ROOT, 'perf_amd', 'build.py')).read()
-    assert "src == 'meshray.hip' or not h.endswith('perf_hip_meshray.h')" in text and "'perf_hip_meshray.h'" in text.split('hdrs =')[1].split('\n')[0]
+    assert "'perf_hip_meshray.h'" in text.split('hdrs =')[1].split('\n')[0]
+    users = [s for s in build.SOURCES if any(p.endswith(os.sep + 'perf_hip_meshray.h') for p in build._includes(os.path.join(build.CSRC, s)))]
+    assert users == ['meshray.hip'], users          # the units that include the header, by their #include lines, are the ones rebuilt for it
     assert "'-ffp-contract=off'" in text
     unit = open(os.path.join(ROOT, 'perf_amd', 'csrc', 'meshray.hip')).read()
     assert '#include "../../include/perf_hip_meshray.h"' in unit

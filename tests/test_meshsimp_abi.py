@@ -120,7 +120,9 @@ def test_the_unit_is_built_with_its_own_header_only():
     from perf_amd import build
     assert 'meshsimp.hip' in build.SOURCES and len(set(build.SOURCES)) == len(build.SOURCES)
     text = open(os.path.join(ROOT, 'perf_amd', 'build.py')).read()
-    assert "src == 'meshsimp.hip' or not h.endswith('perf_hip_meshsimp.h')" in text and "'perf_hip_meshsimp.h'" in text.split('hdrs =')[1].split('\n')[0]
+    assert "'perf_hip_meshsimp.h'" in text.split('hdrs =')[1].split('\n')[0]
+    users = [s for s in build.SOURCES if any(p.endswith(os.sep + 'perf_hip_meshsimp.h') for p in build._includes(os.path.join(build.CSRC, s)))]
+    assert users == ['meshsimp.hip'], users          # the units that include the header, by their #include lines, are the ones rebuilt for it
 
 
 def test_refuses_null_pointers():

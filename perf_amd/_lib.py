@@ -22,6 +22,7 @@ MESHVIS_ABI_VERSION = 1      # PERF_MESHVIS_ABI_VERSION of include/perf_hip_mesh
 MESHSIMP_ABI_VERSION = 1     # PERF_MESHSIMP_ABI_VERSION of include/perf_hip_meshsimp.h (simplify a mesh by vertex clustering)
 MESHCOLOR_ABI_VERSION = 1    # PERF_MESHCOLOR_ABI_VERSION of include/perf_hip_meshcolor.h (colour a mesh from the registered panoramas; normals from faces)
 MESHRAY_ABI_VERSION = 1      # PERF_MESHRAY_ABI_VERSION of include/perf_hip_meshray.h (rays against a mesh on a uniform grid: closest hit, any hit, occlusion)
+RIDERS_ABI_VERSION = 1       # PERF_RIDERS_ABI_VERSION of include/perf_hip_riders.h (the next batch's front end riding in the backward's launches)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
 ACT_NONE, ACT_SIGMOID, ACT_EXP = 0, 1, 2
@@ -49,6 +50,28 @@ class StepBook(Structure):       # perf_step_book: the arguments of perf_step_bo
                 ('capacity', c_int64), ('overflow_flag', c_void_p), ('remote_flags', c_void_p), ('eff_gate_out', c_void_p),
                 ('schedule', c_void_p), ('iter_dev', c_void_p), ('lr_out', c_void_p), ('ratio_out', c_void_p), ('n_schedule', c_int32),
                 ('overflow_redone', c_int32)]
+
+
+# include/perf_hip_riders.h: the argument blocks of the three rider stages (field for field)
+class RiderDraw(Structure):      # perf_rider_draw
+    _fields_ = [('seed', c_uint64), ('counter_dev', c_void_p), ('ticket', c_void_p), ('pool_lo', c_int64), ('pool_hi', c_int64), ('n_local', c_int64),
+                ('first_global', c_int64), ('o_all', c_void_p), ('d_all', c_void_p), ('color_all', c_void_p), ('dist_all', c_void_p), ('normal_all', c_void_p),
+                ('o', c_void_p), ('d', c_void_p), ('color', c_void_p), ('dist', c_void_p), ('normal', c_void_p), ('indices_out', c_void_p),
+                ('jitter', c_void_p), ('noise', c_void_p), ('bg', c_void_p), ('t0_scale', c_float), ('t0_base', c_float), ('step', c_float),
+                ('max_steps', c_int32), ('runs', c_void_p), ('marched_live', c_void_p), ('marched_keep', c_void_p)]
+
+
+class RiderCount(Structure):     # perf_rider_count
+    _fields_ = [('rays_o', c_void_p), ('rays_d', c_void_p), ('t0', c_void_p), ('t0_scale', c_float), ('t0_base', c_float), ('n_rays', c_int64),
+                ('occ_bits', c_void_p), ('occ_coarse', c_void_p), ('res', c_int32), ('aabb', c_float * 6), ('far_plane', c_float), ('step', c_float),
+                ('max_steps', c_int32), ('runs', c_void_p), ('masks', c_void_p), ('counts', c_void_p)]
+
+
+class RiderWrite(Structure):     # perf_rider_write
+    _fields_ = [('t0', c_void_p), ('t0_scale', c_float), ('t0_base', c_float), ('n_rays', c_int64), ('step', c_float), ('max_steps', c_int32),
+                ('runs', c_void_p), ('masks', c_void_p), ('counts', c_void_p), ('offsets', c_void_p), ('total', c_void_p), ('capacity', c_int64),
+                ('ray_indices', c_void_p), ('t_starts', c_void_p), ('t_ends', c_void_p), ('packed_info', c_void_p), ('rays_o', c_void_p),
+                ('rays_d', c_void_p), ('points_aabb', c_float * 6), ('x01', c_void_p), ('sel', c_void_p)]
 
 
 class PerfError(RuntimeError):
@@ -280,6 +303,21 @@ _SIGS_MESHRAY = {
     'perf_meshray_occluded': (c_int, _RAY_MESH + _RAY_BOX + [P, P, c_int64, P, c_int32, P, P, P]),
 }
 
+# include/perf_hip_riders.h: the step riders, exported from the same library, versioned on their own (perf_riders_version)
+RIDER_THREADS = 256          # PERF_RIDER_THREADS
+RIDER_DRAW_RAYS = 256        # PERF_RIDER_DRAW_RAYS
+RIDER_MARCH_RAYS = 4         # PERF_RIDER_MARCH_RAYS
+RIDER_MAX_RAYS = 65536       # PERF_RIDER_MAX_RAYS
+_SIGS_RIDERS = {
+    'perf_riders_version': (c_int, []),
+    'perf_sizeof_rider_draw': (c_int64, []),
+    'perf_sizeof_rider_count': (c_int64, []),
+    'perf_sizeof_rider_write': (c_int64, []),
+    'perf_field_bwd_riders': (c_int, [POINTER(GridDesc), POINTER(MlpDesc), P, P, P, P, c_int64, P, P, P, c_int32, c_int32, P, P, P, c_int64, c_int64, P, c_int,
+                                      POINTER(StepBook), POINTER(RiderDraw), POINTER(RiderCount), P]),
+    'perf_adam_step_dev_riders': (c_int, [P, P, P, P, P, c_int64, c_int, P, P, P, c_float, c_float, c_float, c_int, P, P, c_int, c_int64, POINTER(RiderWrite), P]),
+}
+
 _lib = None
 
 
@@ -295,7 +333,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()) + list(_SIGS_MESHVIS.items()) + list(_SIGS_MESHSIMP.items()) + list(_SIGS_MESHCOLOR.items()) + list(_SIGS_MESHRAY.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()) + list(_SIGS_MESHVIS.items()) + list(_SIGS_MESHSIMP.items()) + list(_SIGS_MESHCOLOR.items()) + list(_SIGS_MESHRAY.items()) + list(_SIGS_RIDERS.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
@@ -337,6 +375,10 @@ def load():
                         'rebuild with `python -m perf_amd.build --force`')
     if lib.perf_meshray_version() != MESHRAY_ABI_VERSION:
         raise PerfError(f'{LIB_PATH} has mesh ray-casting ABI version {lib.perf_meshray_version()}, this binding expects {MESHRAY_ABI_VERSION}: '
+                        'rebuild with `python -m perf_amd.build --force`')
+    if lib.perf_riders_version() != RIDERS_ABI_VERSION or (lib.perf_sizeof_rider_draw(), lib.perf_sizeof_rider_count(), lib.perf_sizeof_rider_write()) != (
+            ctypes.sizeof(RiderDraw), ctypes.sizeof(RiderCount), ctypes.sizeof(RiderWrite)):
+        raise PerfError(f'{LIB_PATH} has step-rider ABI version {lib.perf_riders_version()} or other argument blocks than this binding ({RIDERS_ABI_VERSION}): '
                         'rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):

@@ -6,6 +6,7 @@
 #include "grid_fixed_point.hpp"
 #include "mlp_reduce_device.hpp"
 #include "step_book_device.hpp"
+#include "step_riders_device.hpp"
 
 namespace perf {
 
@@ -539,18 +540,22 @@ __device__ __forceinline__ uint32_t code_level(const CodeLevel& d, const float (
 //  * the hashed levels multiply with the full-rate 24-bit multiplier (hashed_tiles);
 //  * the exact dense byte takes two comparisons per corner (dense_code).
 // (The launch can carry the MLP backward's second stage in workgroups of its own behind the `own_blocks` that compute codes:
-//  mlp_reduce_device.hpp.)
+//  mlp_reduce_device.hpp; and, in its FIRST draw.n_blocks workgroups, stage A of the step riders -- the next batch's draw and lattice
+//  tables, step_riders_device.hpp: dispatched first, they run beside the code workgroups.)
 __global__ __launch_bounds__(64 * kCodeWaves) void tile_codes4_kernel(CodePlan cp, const float* __restrict__ x01,
                                                                        const float2* __restrict__ dfeat, uint32_t* __restrict__ codes,
                                                                        uint32_t* __restrict__ escape, int64_t n,
-                                                                       const int64_t* __restrict__ n_dev, MlpReduceJob job, unsigned own_blocks) {
-    if (blockIdx.x >= own_blocks) { mlp_reduce_block(job, (int)(blockIdx.x - own_blocks)); return; }
+                                                                       const int64_t* __restrict__ n_dev, MlpReduceJob job, unsigned own_blocks,
+                                                                       RiderDrawJob draw) {
+    if (blockIdx.x < (unsigned)draw.n_blocks) { rider_draw_block(draw, (int)blockIdx.x); return; }
+    const unsigned bx = blockIdx.x - (unsigned)draw.n_blocks;
+    if (bx >= own_blocks) { mlp_reduce_block(job, (int)(bx - own_blocks)); return; }
     const int64_t n_live = live_count(n, n_dev);            // n: capacity = stride of dfeat
     __shared__ uint32_t esc_block;
     if (threadIdx.x == 0) esc_block = 0u;
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t i0 = (int64_t)blockIdx.x * kCodeSamplesPerBlock + 4 * lane;
+    const int64_t i0 = (int64_t)bx * kCodeSamplesPerBlock + 4 * lane;
     uint32_t esc = 0u;                  // bit l: level l must take the generic owners
     if (i0 < n_live) {
         const int cnt = (n_live - i0) < 4 ? (int)(n_live - i0) : 4;
@@ -582,7 +587,7 @@ __global__ __launch_bounds__(64 * kCodeWaves) void tile_codes4_kernel(CodePlan c
     }
     if (esc) atomicOr(&esc_block, esc);
     __syncthreads();
-    if (threadIdx.x == 0) escape[blockIdx.x] = esc_block;       // every word is written: no zero-fill needed
+    if (threadIdx.x == 0) escape[bx] = esc_block;       // every word is written: no zero-fill needed
 }
 
 // ---- levels of 256..2048 tiles (log2_hashmap_size 22..25): per-tile bitmaps ---------------------------------------
@@ -1455,27 +1460,36 @@ __host__ __device__ inline int reduce_blocks_of(uint32_t size, int width) {
 __global__ __launch_bounds__(256) void hashgrid_bwd_reduce_kernel(GridParams gp, TileParams tp, const float2* __restrict__ ws,
                                                                   float2* __restrict__ grad, int32_t* __restrict__ hr_state,
                                                                   const int32_t* __restrict__ shifts, int fixed,
-                                                                  int32_t* __restrict__ overflow_flag, int n_ticket_blocks) {
+                                                                  int32_t* __restrict__ overflow_flag, int n_ticket_blocks,
+                                                                  RiderCountJob count, unsigned rider_cols) {
+    // stage B of the step riders (step_riders_device.hpp) in the first `rider_cols` columns of every row: the next batch's counting pass
+    if (blockIdx.x < rider_cols) {
+        const unsigned b = blockIdx.y * rider_cols + blockIdx.x;
+        if (b < (unsigned)count.n_blocks) rider_count_block(count, (int)b);
+        return;
+    }
+    const unsigned bx = blockIdx.x - rider_cols;
+    const int width = (int)(gridDim.x - rider_cols);
     const int l = blockIdx.y;
     const int R = tp.replicas_of[l];
     // (rows of levels without replicas have nothing to add up: they leave at once, without a ticket -- same-address atomics
     //  retire at ~11 ns each; with no replicated level at all, workgroup (0, 0) applies the feedback)
-    if (R <= 1 && !(n_ticket_blocks == 0 && blockIdx.x == 0 && blockIdx.y == 0)) return;
+    if (R <= 1 && !(n_ticket_blocks == 0 && bx == 0 && blockIdx.y == 0)) return;
     // a replicated level takes one workgroup per 1,024 entries (at most the grid's width): the smallest ones must not pay -- in
     // tickets -- for the width the largest one needs (reduce_blocks_of() is what the host counted)
-    if (R > 1 && (int)blockIdx.x >= reduce_blocks_of(gp.size[l], (int)gridDim.x)) return;
+    if (R > 1 && (int)bx >= reduce_blocks_of(gp.size[l], width)) return;
     int sink = 0;
     if (R > 1) {
         const uint32_t size = gp.size[l];
         const float from_fixed = fixed ? ldexpf(1.0f, -shifts[l]) : 1.0f;
         int32_t field_max = 0;
-        const uint32_t stride = (uint32_t)reduce_blocks_of(size, (int)gridDim.x) * 256;
+        const uint32_t stride = (uint32_t)reduce_blocks_of(size, width) * 256;
         if (fixed) {
             // Four entries x four slabs per round trip: a thread of the largest replicated level owns a dozen entries, and
             // written as "for entry: for slab: load, add" every one of its 4 R loads was a round trip of its own (14 us for a
             // few megabytes).  Indices are clamped so that all sixteen loads are unconditional; integer sums, any order.
             const int2* p = reinterpret_cast<const int2*>(ws + tp.ws_off[l]);
-            for (uint32_t e0 = blockIdx.x * 256 + threadIdx.x; e0 < size; e0 += 4 * stride) {
+            for (uint32_t e0 = bx * 256 + threadIdx.x; e0 < size; e0 += 4 * stride) {
                 int32_t sx[4] = {0, 0, 0, 0}, sy[4] = {0, 0, 0, 0};
                 uint32_t ej[4];
 #pragma unroll
@@ -1509,7 +1523,7 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_reduce_kernel(GridParams gp,
                 }
             }
         } else {
-            for (uint32_t e = blockIdx.x * 256 + threadIdx.x; e < size; e += stride) {
+            for (uint32_t e = bx * 256 + threadIdx.x; e < size; e += stride) {
                 float2* o = grad + gp.offset[l] + e;
                 const float2* p = ws + tp.ws_off[l] + e;
                 float sx = 0.f, sy = 0.f;
@@ -1679,6 +1693,27 @@ int perf_internal_hashgrid_bwd(const perf_grid_desc* grid, const float* x01, con
                                int32_t* overflow_flag, int32_t* headroom_state, const int32_t* shifts_dev, int raw_fields,
                                const int32_t* redo_flag, void* workspace, int64_t workspace_bytes, void* stream, const MlpReduceJob* job_in,
                                const perf_step_book* book) {
+    return perf_internal_hashgrid_bwd_riders(grid, x01, dfeat, grad_table, n, n_dev, accumulate, level_absmax, overflow_flag, headroom_state, shifts_dev,
+                                             raw_fields, redo_flag, workspace, workspace_bytes, stream, job_in, book, nullptr, nullptr);
+}
+
+namespace perf {
+// a rider whose host launch does not take place: a launch of its own at the same place of the stream
+__global__ __launch_bounds__(PERF_RIDER_THREADS) void rider_draw_kernel(RiderDrawJob j) { rider_draw_block(j, (int)blockIdx.x); }
+__global__ __launch_bounds__(PERF_RIDER_THREADS) void rider_count_kernel(RiderCountJob j) { rider_count_block(j, (int)blockIdx.x); }
+}  // namespace perf
+
+// draw / count (perf_field_bwd_riders): stages A and B of the step riders -- A in the tile-code launch, B in the replica reduction
+int perf_internal_hashgrid_bwd_riders(const perf_grid_desc* grid, const float* x01, const float* dfeat,
+                                      float* grad_table, int64_t n, const int64_t* n_dev, int accumulate, const float* level_absmax,
+                                      int32_t* overflow_flag, int32_t* headroom_state, const int32_t* shifts_dev, int raw_fields,
+                                      const int32_t* redo_flag, void* workspace, int64_t workspace_bytes, void* stream, const MlpReduceJob* job_in,
+                                      const perf_step_book* book, const RiderDrawJob* draw_in, const RiderCountJob* count_in) {
+    RiderDrawJob draw{};
+    RiderCountJob count{};
+    if (draw_in) draw = *draw_in;
+    if (count_in) count = *count_in;
+    PERF_REQUIRE(!(redo_flag && (draw.n_blocks || count.n_blocks)), "perf_hashgrid_bwd: a redo call carries no riders");
     PERF_REQUIRE(!book || redo_flag, "perf_hashgrid_bwd: the bookkeeping rides in a repair launch only");
     MlpReduceJob job{};
     if (job_in) job = *job_in;
@@ -1762,16 +1797,21 @@ int perf_internal_hashgrid_bwd(const perf_grid_desc* grid, const float* x01, con
         escape = codes + (int64_t)slots * tp.n_pad;
         CodePlan cp;
         plan_code_levels(gp, tp, &cp);
-        const unsigned own = (unsigned)esc_words, all = own + (unsigned)job.n_blocks;       // (codes: 16-byte aligned, as the workspace and codes_at are)
-        tile_codes4_kernel<<<dim3(all), dim3(64 * kCodeWaves), 0, as_stream(stream)>>>(cp, x01, (const float2*)dfeat, codes, escape, n, n_dev, job, own);
+        const unsigned own = (unsigned)esc_words, all = (unsigned)draw.n_blocks + own + (unsigned)job.n_blocks;       // (codes: 16-byte aligned, as the workspace and codes_at are)
+        tile_codes4_kernel<<<dim3(all), dim3(64 * kCodeWaves), 0, as_stream(stream)>>>(cp, x01, (const float2*)dfeat, codes, escape, n, n_dev, job, own, draw);
         PERF_LAUNCH_CHECK("perf_hashgrid_bwd(codes)");
         job.n_blocks = 0;                          // (done)
+        draw.n_blocks = 0;
     } else {
         for (int l = 0; l < PERF_MAX_LEVELS; ++l) tp.code_slot[l] = -1;
     }
     if (job.n_blocks) {                            // no tile-code launch to ride in
         perf_internal_launch_mlp_reduce(job, stream);
         PERF_LAUNCH_CHECK("perf_hashgrid_bwd(deferred MLP reduce)");
+    }
+    if (draw.n_blocks) {
+        rider_draw_kernel<<<dim3((unsigned)draw.n_blocks), dim3(PERF_RIDER_THREADS), 0, as_stream(stream)>>>(draw);
+        PERF_LAUNCH_CHECK("perf_hashgrid_bwd(stage A of its own)");
     }
     const int lds_bytes = 2 * kTileEntries * (int)sizeof(float) + (kBwdThreads / 64) * kQueueCap * (int)sizeof(uint32_t);
     static std::once_flag attr_once;                // one-time kernel attribute setup, safe under concurrent callers
@@ -1817,10 +1857,17 @@ int perf_internal_hashgrid_bwd(const perf_grid_desc* grid, const float* x01, con
         constexpr int kReduceBlocks = 64;
         int n_tickets = 0;
         for (int l = 0; l < gp.n_levels; ++l) n_tickets += tp.replicas_of[l] > 1 ? reduce_blocks_of(gp.size[l], kReduceBlocks) : 0;
-        hashgrid_bwd_reduce_kernel<<<dim3(kReduceBlocks, gp.n_levels), dim3(256), 0, as_stream(stream)>>>(
+        // (stage B's workgroups: the first columns of every row, see the kernel)
+        const unsigned rider_cols = (unsigned)div_up(count.n_blocks, gp.n_levels);
+        hashgrid_bwd_reduce_kernel<<<dim3(rider_cols + kReduceBlocks, gp.n_levels), dim3(256), 0, as_stream(stream)>>>(
             gp, tp, (const float2*)workspace, (float2*)grad_table, adapt ? headroom_state : nullptr,
-            shifts_dev ? shifts_dev : shifts_ws, fixed ? 1 : 0, overflow_flag, n_tickets);
+            shifts_dev ? shifts_dev : shifts_ws, fixed ? 1 : 0, overflow_flag, n_tickets, count, rider_cols);
         PERF_LAUNCH_CHECK("perf_hashgrid_bwd(reduce)");
+        count.n_blocks = 0;
+    }
+    if (count.n_blocks) {
+        rider_count_kernel<<<dim3((unsigned)count.n_blocks), dim3(PERF_RIDER_THREADS), 0, as_stream(stream)>>>(count);
+        PERF_LAUNCH_CHECK("perf_hashgrid_bwd(stage B of its own)");
     }
     return PERF_OK;
 }

@@ -6,6 +6,7 @@
 #include <type_traits>
 #include "common.hpp"
 #include "step_book_device.hpp"
+#include "step_riders_device.hpp"
 
 namespace perf {
 
@@ -83,16 +84,25 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
 // issued BEFORE the scalar prologue (gate, step count -> bias corrections, learning rate: a dependent chain of device reads and
 // two powf that every workgroup repeats): the 199 MB of a 3.3 M-entry table's step stream while it runs.  Element for element
 // the arithmetic of adam_kernel.
-template <typename T16, bool W16, bool PAIR = false>
+// RIDER (include/perf_hip_riders.h, stage C): the launch's first rj.n_blocks workgroups write the next batch's marched samples
+// (rider_write_block) and the step's own workgroups follow them; without it the kernel is what it was.
+struct NoRider {};
+template <typename T16, bool W16, bool PAIR = false, bool RIDER = false>
 __global__ __launch_bounds__(256) void adam4_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                     float* __restrict__ g, uint16_t* __restrict__ w16, int64_t n,
                                                     float one_minus_b1, float b2, float one_minus_b2, float step_size,
                                                     float inv_bc2_sqrt, float eps, int zero_grad,
                                                     const int32_t* __restrict__ step_dev, const float* __restrict__ lr_dev,
                                                     const int64_t* __restrict__ gate_dev, int32_t* __restrict__ clear_flag,
-                                                    std::conditional_t<PAIR, PairOut, NoPairOut> po) {
+                                                    std::conditional_t<PAIR, PairOut, NoPairOut> po,
+                                                    std::conditional_t<RIDER, RiderWriteJob, NoRider> rj = {}) {
+    unsigned bx = blockIdx.x;
+    if constexpr (RIDER) {
+        if (bx < (unsigned)rj.n_blocks) { rider_write_block(rj, (int)bx); return; }
+        bx -= (unsigned)rj.n_blocks;
+    }
     __shared__ float sc[2];
-    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const int64_t i = ((int64_t)bx * 256 + threadIdx.x) * 4;
     const int cnt = i + 3 < n ? 4 : (i < n ? (int)(n - i) : 0);
     float gi[4] = {0.f, 0.f, 0.f, 0.f}, mi[4] = {0.f, 0.f, 0.f, 0.f}, vi[4] = {0.f, 0.f, 0.f, 0.f}, pi[4] = {0.f, 0.f, 0.f, 0.f};
     if (cnt == 4) {
@@ -103,7 +113,7 @@ __global__ __launch_bounds__(256) void adam4_kernel(float* __restrict__ p, float
     } else {
         for (int k = 0; k < cnt; ++k) { gi[k] = g[i + k]; mi[k] = m[i + k]; vi[k] = v[i + k]; pi[k] = p[i + k]; }
     }
-    if (clear_flag && blockIdx.x == 0 && threadIdx.x == 0) clear_flag[0] = 0;      // (taken or not: perf_adam_step_dev)
+    if (clear_flag && bx == 0 && threadIdx.x == 0) clear_flag[0] = 0;      // (taken or not: perf_adam_step_dev)
     if (gate_dev && gate_dev[0] <= 0) return;       // batch without samples: the reference skips the step (nerf.py:204-206)
     if (step_dev) {
         if (threadIdx.x == 0) {
@@ -378,6 +388,42 @@ extern "C" int perf_adam_step_dev_pair(float* p, float* m, float* v, float* g, v
     return PERF_OK;
 }
 
+// perf_adam_step_dev / perf_adam_step_dev_pair whose launch carries stage C of the step riders (include/perf_hip_riders.h)
+extern "C" int perf_adam_step_dev_riders(float* p, float* m, float* v, float* g, void* w16, int64_t n, int dtype, const int32_t* step_dev,
+                                         const float* lr_dev, const int64_t* gate_dev, float beta1, float beta2, float eps, int zero_grad,
+                                         int32_t* clear_flag, void* pair, int field, int64_t n_net, const perf_rider_write* write, void* stream) {
+    RiderWriteJob rj;
+    const int rc = perf_internal_rider_write_job(write, &rj);
+    if (rc) return rc;
+    if (rj.n_blocks == 0)
+        return pair ? perf_adam_step_dev_pair(p, m, v, g, w16, n, dtype, step_dev, lr_dev, gate_dev, beta1, beta2, eps, zero_grad, clear_flag, pair, field, n_net, stream)
+                    : perf_adam_step_dev(p, m, v, g, w16, n, dtype, step_dev, lr_dev, gate_dev, beta1, beta2, eps, zero_grad, clear_flag, stream);
+    PERF_REQUIRE(step_dev && lr_dev, "perf_adam_step_dev_riders: NULL scalar pointers");
+    PERF_REQUIRE(p && m && v && g && w16 && n >= 1024, "perf_adam_step_dev_riders: NULL pointer, or fewer than 1024 elements");
+    PERF_REQUIRE(dtype == PERF_DTYPE_BF16 || dtype == PERF_DTYPE_FP16, "perf_adam_step_dev_riders: bad dtype %d", dtype);
+    const uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+                            reinterpret_cast<uintptr_t>(g) | (reinterpret_cast<uintptr_t>(w16) << 1);
+    PERF_REQUIRE((align & 15) == 0, "perf_adam_step_dev_riders: the arrays must be 16-byte aligned (w16: 8-byte)");
+    if (pair) {
+        PERF_REQUIRE(field == 0 || field == 1, "perf_adam_step_dev_riders: field %d is neither 0 nor 1", field);
+        PERF_REQUIRE(n_net >= 0 && n_net <= n && (n_net & 1) == 0 && ((n - n_net) & 1) == 0, "perf_adam_step_dev_riders: n_net and n - n_net must be even, 0 <= n_net <= n");
+        PERF_REQUIRE(((uintptr_t)pair & 7u) == 0, "perf_adam_step_dev_riders: the pair table must be 8-byte aligned");
+    }
+    const float omb1 = 1.0f - beta1, omb2 = 1.0f - beta2;
+    // (rider workgroups first: they are dispatched first and run beside the step's own)
+    dim3 g4((unsigned)(div_up(div_up(n, 4), 256) + rj.n_blocks)), b(256);
+    if (pair) {
+        const PairOut po{(uint32_t*)pair, n_net, field};
+        if (dtype == PERF_DTYPE_BF16) hipLaunchKernelGGL((adam4_kernel<BF16, true, true, true>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, 0.f, 1.f, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, po, rj);
+        else hipLaunchKernelGGL((adam4_kernel<FP16, true, true, true>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, 0.f, 1.f, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, po, rj);
+    } else {
+        if (dtype == PERF_DTYPE_BF16) hipLaunchKernelGGL((adam4_kernel<BF16, true, false, true>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, 0.f, 1.f, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, NoPairOut{}, rj);
+        else hipLaunchKernelGGL((adam4_kernel<FP16, true, false, true>), g4, b, 0, as_stream(stream), p, m, v, g, (uint16_t*)w16, n, omb1, beta2, omb2, 0.f, 1.f, eps, zero_grad, step_dev, lr_dev, gate_dev, clear_flag, NoPairOut{}, rj);
+    }
+    PERF_LAUNCH_CHECK("perf_adam_step_dev_riders");
+    return PERF_OK;
+}
+
 static Aabb make_aabb(const float* a) {
     Aabb bb;
     for (int i = 0; i < 3; ++i) { bb.lo[i] = a[i]; bb.hi[i] = a[3 + i]; }
@@ -512,26 +558,7 @@ extern "C" int perf_occ_splat(const float* rays_o, const float* rays_d, const fl
 // rand_ray_color_data (modules/dataset/sup_info.py:236-259) gathers origins, directions, colours, distances and normals of
 // the drawn pixels with five indexing kernels; here one launch gathers whatever is asked for (NULL = skip).
 namespace perf {
-// The rows of pixel j -> slot i of whatever outputs are asked for.  ALL the loads are issued before the first store: written as
-// "if (o) o[..] = o_all[..]" per element, every load is waited for on its own before the store that follows it -- thirteen
-// dependent round trips to random rows for what is one (11 us -> the latency of one gather, measured on the draw kernel).
-__device__ __forceinline__ void gather_rows(int64_t i, int64_t j, const float* __restrict__ o_all, const float* __restrict__ d_all,
-                                            const float* __restrict__ c_all, const float* __restrict__ t_all,
-                                            const float* __restrict__ n_all, float* __restrict__ o, float* __restrict__ d,
-                                            float* __restrict__ c, float* __restrict__ t, float* __restrict__ nrm) {
-    float vo[3] = {0.f, 0.f, 0.f}, vd[3] = {0.f, 0.f, 0.f}, vc[3] = {0.f, 0.f, 0.f}, vn[3] = {0.f, 0.f, 0.f}, vt = 0.f;
-    if (o) { vo[0] = o_all[3 * j]; vo[1] = o_all[3 * j + 1]; vo[2] = o_all[3 * j + 2]; }
-    if (d) { vd[0] = d_all[3 * j]; vd[1] = d_all[3 * j + 1]; vd[2] = d_all[3 * j + 2]; }
-    if (c) { vc[0] = c_all[3 * j]; vc[1] = c_all[3 * j + 1]; vc[2] = c_all[3 * j + 2]; }
-    if (nrm) { vn[0] = n_all[3 * j]; vn[1] = n_all[3 * j + 1]; vn[2] = n_all[3 * j + 2]; }
-    if (t) vt = t_all[j];
-    if (o) { o[3 * i] = vo[0]; o[3 * i + 1] = vo[1]; o[3 * i + 2] = vo[2]; }
-    if (d) { d[3 * i] = vd[0]; d[3 * i + 1] = vd[1]; d[3 * i + 2] = vd[2]; }
-    if (c) { c[3 * i] = vc[0]; c[3 * i + 1] = vc[1]; c[3 * i + 2] = vc[2]; }
-    if (nrm) { nrm[3 * i] = vn[0]; nrm[3 * i + 1] = vn[1]; nrm[3 * i + 2] = vn[2]; }
-    if (t) t[i] = vt;
-}
-
+// (gather_rows: step_riders_device.hpp)
 __global__ __launch_bounds__(256) void gather_supervision_kernel(const int64_t* __restrict__ idx, int64_t n,
                                                                  const float* __restrict__ o_all, const float* __restrict__ d_all,
                                                                  const float* __restrict__ c_all, const float* __restrict__ t_all,
@@ -559,20 +586,7 @@ extern "C" int perf_gather_supervision(const int64_t* indices, int64_t n, const 
 
 // ---- training batch draw: index stream + per-ray uniforms + supervision gather in one launch --------------------------------
 namespace perf {
-// Philox4x32-10 (Salmon et al., SC'11; the counter-based generator family torch.rand uses on the GPU): 128-bit counter,
-// 64-bit key -> four 32-bit words.
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-__device__ __forceinline__ float u01(uint32_t x) { return (float)(x & 0xffffffu) * (1.0f / 16777216.0f); }   // 24 bits, [0, 1)
-
+// (Philox4x32-10 and the body of the draw: step_riders_device.hpp -- the draw also rides in the grid backward, include/perf_hip_riders.h)
 __global__ __launch_bounds__(256) void draw_train_batch_kernel(uint32_t seed_lo, uint32_t seed_hi, int64_t* __restrict__ counter,
                                                                int32_t* __restrict__ ticket, int64_t pool_lo, int64_t pool_n,
                                                                int64_t n_local, int64_t first_global,
@@ -583,29 +597,8 @@ __global__ __launch_bounds__(256) void draw_train_batch_kernel(uint32_t seed_lo,
                                                                float* __restrict__ nrm, int64_t* __restrict__ idx_out,
                                                                float* __restrict__ jitter, float* __restrict__ noise,
                                                                float* __restrict__ bg) {
-    const uint64_t draw = (uint64_t)counter[0];              // read by every workgroup BEFORE any of them can advance it
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n_local) {
-        const uint64_t g = (uint64_t)(first_global + i);     // position in the GLOBAL batch: ranks draw disjoint slices of one stream
-        uint32_t r[4] = {(uint32_t)g, (uint32_t)(g >> 32), (uint32_t)draw, (uint32_t)(draw >> 32) & 0x7fffffffu};
-        philox4x32_10(r, seed_lo, seed_hi);
-        const int64_t j = pool_lo + (int64_t)(((uint64_t)r[0] * (uint64_t)pool_n) >> 32);
-        gather_rows(i, j, o_all, d_all, c_all, t_all, n_all, o, d, c, t, nrm);     // (first: its loads fly during the second Philox)
-        if (idx_out) idx_out[i] = j;
-        if (jitter) jitter[i] = u01(r[1]);
-        if (noise) noise[i] = u01(r[2]);
-        if (bg) {
-            uint32_t q[4] = {(uint32_t)g, (uint32_t)(g >> 32), (uint32_t)draw, ((uint32_t)(draw >> 32) & 0x7fffffffu) | 0x80000000u};
-            philox4x32_10(q, seed_lo, seed_hi);
-            bg[3 * i] = u01(q[0]); bg[3 * i + 1] = u01(q[1]); bg[3 * i + 2] = u01(q[2]);
-        }
-    }
-    // the last workgroup to finish advances the draw counter (every workgroup has read it by then) and rearms the ticket
-    __syncthreads();
-    if (threadIdx.x == 0 && atomicAdd(ticket, 1) == (int)gridDim.x - 1) {
-        counter[0] = (int64_t)(draw + 1);
-        *ticket = 0;
-    }
+    draw_train_batch_body((int)blockIdx.x, (int)gridDim.x, seed_lo, seed_hi, counter, ticket, pool_lo, pool_n, n_local, first_global, o_all, d_all, c_all, t_all,
+                          n_all, o, d, c, t, nrm, idx_out, jitter, noise, bg);
 }
 }  // namespace perf
 

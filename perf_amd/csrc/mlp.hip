@@ -2,6 +2,7 @@
 // instantiated in mlp_fwd_{bf16,fp16}.hip and mlp_bwd_{bf16,fp16}_nh{1,2}.hip.
 #include "mlp_device.hpp"
 #include "mlp_reduce_device.hpp"
+#include "step_riders_device.hpp"
 
 namespace perf {
 
@@ -160,7 +161,7 @@ static int field_bwd_chain(const perf_grid_desc* grid, const perf_mlp_desc* mlp,
                            const void* feat16, const int32_t* feat_index, int64_t feat_stride, const uint8_t* sel, const float* dout,
                            float* grad, int32_t fixed, int32_t redo, int32_t* overflow_flag, int32_t* headroom_state,
                            void* workspace, int64_t workspace_bytes, int64_t n, const int64_t* n_dev, int dtype, const perf_step_book* book,
-                           void* stream);
+                           void* stream, const perf_rider_draw* draw = nullptr, const perf_rider_count* count = nullptr);
 
 extern "C" int perf_field_bwd(const perf_grid_desc* grid, const perf_mlp_desc* mlp, const float* x01, const void* w16_net,
                               const void* feat16, const int32_t* feat_index, int64_t feat_stride, const uint8_t* sel, const float* dout,
@@ -172,23 +173,53 @@ extern "C" int perf_field_bwd(const perf_grid_desc* grid, const perf_mlp_desc* m
 
 // ... and the step's bookkeeping in one thread of the repair launch (one launch per training step fewer; the flag is left to
 // perf_adam_step_dev's clear_flag)
-extern "C" int perf_field_bwd_book(const perf_grid_desc* grid, const perf_mlp_desc* mlp, const float* x01, const void* w16_net,
-                                   const void* feat16, const int32_t* feat_index, int64_t feat_stride, const uint8_t* sel, const float* dout,
-                                   float* grad, int32_t* overflow_flag, int32_t* headroom_state, void* workspace, int64_t workspace_bytes,
-                                   int64_t n, const int64_t* n_dev, int dtype, const perf_step_book* book, void* stream) {
+static int perf_field_bwd_book_impl(const perf_grid_desc* grid, const perf_mlp_desc* mlp, const float* x01, const void* w16_net,
+                                    const void* feat16, const int32_t* feat_index, int64_t feat_stride, const uint8_t* sel, const float* dout,
+                                    float* grad, int32_t* overflow_flag, int32_t* headroom_state, void* workspace, int64_t workspace_bytes,
+                                    int64_t n, const int64_t* n_dev, int dtype, const perf_step_book* book, void* stream,
+                                    const perf_rider_draw* draw, const perf_rider_count* count) {
     PERF_REQUIRE(book && overflow_flag && headroom_state, "perf_field_bwd_book: NULL pointer");
     PERF_REQUIRE(book->overflow_flag == overflow_flag, "perf_field_bwd_book: book->overflow_flag must be the call's overflow_flag");
     PERF_REQUIRE(n > 0, "perf_field_bwd_book: n == 0");
     return field_bwd_chain(grid, mlp, x01, w16_net, feat16, feat_index, feat_stride, sel, dout, grad, 1, 1, overflow_flag, headroom_state,
-                           workspace, workspace_bytes, n, n_dev, dtype, book, stream);
+                           workspace, workspace_bytes, n, n_dev, dtype, book, stream, draw, count);
+}
+
+extern "C" int perf_field_bwd_book(const perf_grid_desc* grid, const perf_mlp_desc* mlp, const float* x01, const void* w16_net,
+                                   const void* feat16, const int32_t* feat_index, int64_t feat_stride, const uint8_t* sel, const float* dout,
+                                   float* grad, int32_t* overflow_flag, int32_t* headroom_state, void* workspace, int64_t workspace_bytes,
+                                   int64_t n, const int64_t* n_dev, int dtype, const perf_step_book* book, void* stream) {
+    return perf_field_bwd_book_impl(grid, mlp, x01, w16_net, feat16, feat_index, feat_stride, sel, dout, grad, overflow_flag, headroom_state, workspace,
+                                    workspace_bytes, n, n_dev, dtype, book, stream, nullptr, nullptr);
+}
+
+// ... whose grid backward carries stages A and B of the step riders (include/perf_hip_riders.h)
+extern "C" int perf_field_bwd_riders(const perf_grid_desc* grid, const perf_mlp_desc* mlp, const float* x01, const void* w16_net,
+                                     const void* feat16, const int32_t* feat_index, int64_t feat_stride, const uint8_t* sel, const float* dout,
+                                     float* grad, int32_t fixed, int32_t redo, int32_t* overflow_flag, int32_t* headroom_state,
+                                     void* workspace, int64_t workspace_bytes, int64_t n, const int64_t* n_dev, int dtype, const perf_step_book* book,
+                                     const perf_rider_draw* draw, const perf_rider_count* count, void* stream) {
+    if (book)
+        return perf_field_bwd_book_impl(grid, mlp, x01, w16_net, feat16, feat_index, feat_stride, sel, dout, grad, overflow_flag, headroom_state, workspace,
+                                        workspace_bytes, n, n_dev, dtype, book, stream, draw, count);
+    return field_bwd_chain(grid, mlp, x01, w16_net, feat16, feat_index, feat_stride, sel, dout, grad, fixed, redo, overflow_flag, headroom_state,
+                           workspace, workspace_bytes, n, n_dev, dtype, nullptr, stream, draw, count);
 }
 
 static int field_bwd_chain(const perf_grid_desc* grid, const perf_mlp_desc* mlp, const float* x01, const void* w16_net,
                            const void* feat16, const int32_t* feat_index, int64_t feat_stride, const uint8_t* sel, const float* dout,
                            float* grad, int32_t fixed, int32_t redo, int32_t* overflow_flag, int32_t* headroom_state,
                            void* workspace, int64_t workspace_bytes, int64_t n, const int64_t* n_dev, int dtype, const perf_step_book* book,
-                           void* stream) {
+                           void* stream, const perf_rider_draw* draw, const perf_rider_count* count) {
     PERF_REQUIRE(grid && mlp && grad && workspace, "NULL pointer");
+    perf::RiderDrawJob draw_job;
+    perf::RiderCountJob count_job;
+    {
+        int rrc = perf_internal_rider_draw_job(draw, &draw_job);
+        if (!rrc) rrc = perf_internal_rider_count_job(count, &count_job);
+        if (rrc) return rrc;
+        PERF_REQUIRE(!(draw_job.n_blocks || count_job.n_blocks) || grid->layout == PERF_LAYOUT_TCNN, "perf_field_bwd_riders: the riders need the tcnn table layout");
+    }
     PERF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "perf_field_bwd: the workspace must be 16-byte aligned");
     int nh, ks;
     int rc = check_mlp(mlp, &nh, &ks);
@@ -208,9 +239,14 @@ static int field_bwd_chain(const perf_grid_desc* grid, const perf_mlp_desc* mlp,
                                stream, &job);
     if (rc) return rc;
     // (the grid part by table layout: the line-local layouts take perf_hashgrid_bwd_lines)
-    auto grid_bwd = grid->layout == PERF_LAYOUT_TCNN ? &perf_internal_hashgrid_bwd : &perf_internal_hashgrid_bwd_lines;
-    rc = grid_bwd(grid, x01, dfeat, grad + n_net, n, n_dev, 0, fixed ? amax : nullptr, fixed ? overflow_flag : nullptr,
-                  fixed ? headroom_state : nullptr, nullptr, 0, nullptr, grid_ws, b16, stream, &job, nullptr);
+    // (the tcnn layout's entry takes the riders' jobs -- empty ones: the launches are what they are without)
+    const bool tcnn = grid->layout == PERF_LAYOUT_TCNN;
+    auto grid_bwd = tcnn ? &perf_internal_hashgrid_bwd : &perf_internal_hashgrid_bwd_lines;
+    rc = tcnn ? perf_internal_hashgrid_bwd_riders(grid, x01, dfeat, grad + n_net, n, n_dev, 0, fixed ? amax : nullptr, fixed ? overflow_flag : nullptr,
+                                                  fixed ? headroom_state : nullptr, nullptr, 0, nullptr, grid_ws, b16, stream, &job, nullptr, &draw_job,
+                                                  &count_job)
+              : grid_bwd(grid, x01, dfeat, grad + n_net, n, n_dev, 0, fixed ? amax : nullptr, fixed ? overflow_flag : nullptr,
+                         fixed ? headroom_state : nullptr, nullptr, 0, nullptr, grid_ws, b16, stream, &job, nullptr);
     if (rc) return rc;
     if (fixed && redo)
         rc = grid_bwd(grid, x01, dfeat, grad + n_net, n, n_dev, 0, nullptr, nullptr, headroom_state, nullptr, 0, overflow_flag, nullptr, 0,

@@ -77,4 +77,11 @@ PERF_INTERNAL int perf_internal_hashgrid_bwd_lines(const perf_grid_desc* grid, c
                                                    int32_t* headroom_state, const int32_t* shifts_dev, int raw_fields, const int32_t* redo_flag,
                                                    void* workspace, int64_t workspace_bytes, void* stream, const perf::MlpReduceJob* job,
                                                    const perf_step_book* book = nullptr);
+namespace perf { struct RiderDrawJob; struct RiderCountJob; }
+// ... with stages A and B of the step riders (step_riders_device.hpp; tcnn layout)
+PERF_INTERNAL int perf_internal_hashgrid_bwd_riders(const perf_grid_desc* grid, const float* x01, const float* dfeat, float* grad_table, int64_t n,
+                                                    const int64_t* n_dev, int accumulate, const float* level_absmax, int32_t* overflow_flag,
+                                                    int32_t* headroom_state, const int32_t* shifts_dev, int raw_fields, const int32_t* redo_flag,
+                                                    void* workspace, int64_t workspace_bytes, void* stream, const perf::MlpReduceJob* job,
+                                                    const perf_step_book* book, const perf::RiderDrawJob* draw, const perf::RiderCountJob* count);
 PERF_INTERNAL void perf_internal_launch_mlp_reduce(const perf::MlpReduceJob& job, void* stream);

@@ -183,7 +183,7 @@ class OccGridEstimator(nn.Module):
     def sampling_ex(self, rays_o, rays_d, sigma_fn=None, near_plane=0.0, far_plane=1e10, render_step_size=1e-3,
                     early_stop_eps=1e-4, alpha_thre=0.0, stratified=False, cone_angle=0.0, alpha_fn=None,
                     t_min=None, t_max=None, jitter=None, max_steps=None, capacity=None, points_aabb=None,
-                    sigma_points_fn=None, head_samples=None, lattice=None):
+                    sigma_points_fn=None, head_samples=None, lattice=None, marched=None):
         """sampling() returning a Samples record: ray_indices, t_starts, t_ends, packed (packed_info), sig (sigmas of the
         kept samples from the visibility pass, or None), x01 / sel (sample positions normalised to points_aabb, or None),
         n_dev (device int64 [1]: number of live samples when the arrays are capacity-sized, else None), n_marched_dev.
@@ -201,7 +201,10 @@ class OccGridEstimator(nn.Module):
           samples (Samples.feat) so that a gradient pass on the kept samples need not encode them again -- compacted along
           (two-phase sampler) or, from the one-phase sampler, as an ops.IndexedFeat: the uncompacted array plus the row of
           every kept sample, which ops.mlp_bwd reads in place (.materialize() gives the compacted copy).
-        lattice: 'repeated' (t_{k+1} = fl(t_k + step), the default: None) or 'single' (t_k = fl(t0 + fl(k step))): PERF_LATTICE_*."""
+        lattice: 'repeated' (t_{k+1} = fl(t_k + step), the default: None) or 'single' (t_k = fl(t0 + fl(k step))): PERF_LATTICE_*.
+        marched (sync-free one-phase sampler): what ops.occ_march(..., capacity, points_aabb) returned for these rays -- (ray_indices,
+          t_starts, t_ends, packed, total, x01, sel) --, produced ahead of time (step_riders.MarchSet): the march is skipped, the
+          density pass and the compaction run on it."""
         if cone_angle != 0.0 or alpha_fn is not None or t_min is not None or t_max is not None:
             raise NotImplementedError('PeRF samples with cone_angle=0 and a sigma_fn (nerf_renderer.py:145-155)')
         if alpha_thre != 0.0:
@@ -223,7 +226,11 @@ class OccGridEstimator(nn.Module):
             anchor = torch.clamp(t_in, min=float(near_plane)).nan_to_num(posinf=float(near_plane))
         # lattice origin near + u * step: formed inside the marching kernels from (u, step, near) -- see ops._origin; only the
         # anchored case (rays that start outside the box, never PeRF's) materialises it
-        if stratified:
+        if marched is not None:
+            if capacity is None or head_samples or points_aabb is None:
+                raise ValueError('a march handed in needs the sync-free one-phase sampler with points_aabb')
+            t0 = None
+        elif stratified:
             u = torch.rand(R, device=dev) if jitter is None else jitter.contiguous()
             t0 = (u, float(render_step_size), float(near_plane)) if anchor is None else u * render_step_size + anchor
         else:
@@ -246,8 +253,9 @@ class OccGridEstimator(nn.Module):
             if compacts and head_samples:
                 return self._sample_two_phase(sm, rays_o, rays_d, t0, float(far_plane), float(render_step_size), max_steps,
                                               int(capacity), points_aabb, sigma_points_fn, early_stop_eps, int(head_samples), lattice)
-            out = ops.occ_march(rays_o, rays_d, t0, self.occ_bits(), res, aabb, float(far_plane), float(render_step_size),
-                                max_steps, capacity=capacity, occ_coarse=self.occ_coarse(), points_aabb=points_aabb, lattice=lattice)
+            out = marched if marched is not None else ops.occ_march(
+                rays_o, rays_d, t0, self.occ_bits(), res, aabb, float(far_plane), float(render_step_size),
+                max_steps, capacity=capacity, occ_coarse=self.occ_coarse(), points_aabb=points_aabb, lattice=lattice)
             ri, ts, te, packed, total = out[:5]
             x01, sel = out[5:] if points_aabb is not None else (None, None)
             sm.n_marched_dev = total

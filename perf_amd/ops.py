@@ -111,11 +111,20 @@ def adam_step(p, m, v, g, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, w16=None, 
 
 
 def adam_step_dev(p, m, v, g, step_dev, lr_dev, beta1=0.9, beta2=0.999, eps=1e-8, w16=None, zero_grad=False, gate=None, clear_flag=None,
-                  pair=None):
+                  pair=None, rider=None):
     """gate: device int64 [1]; the update is skipped when it holds 0 (a batch without samples).  clear_flag (device int32 [1]): zeroed by
     the launch, taken or not -- how the overflow flag is consumed when the bookkeeping rode in the repair launch (field_bwd(book=...)).
     pair = (pair table, field, n_net): p is [network (n_net) | table] and the step keeps that field's half of the pair table current too."""
     code = dtype_code(w16.dtype) if w16 is not None else 0
+    if rider is not None:
+        # rider (rider_write(...)): the launch carries stage C of the step riders -- the next batch's offsets and write pass
+        table, field, n_net = pair if pair is not None else (None, 0, 0)
+        if w16 is None or (table is not None and (table.dtype != torch.int32 or table.numel() != p.numel() - n_net)):
+            raise _lib.PerfError('adam_step_dev: a rider needs w16 (and pair = (int32 [entries, 2] pair table, field, n_net) of (n - n_net) / 2 entries)')
+        _call('perf_adam_step_dev_riders', _p(_f32(p, 'p')), _p(_f32(m, 'm')), _p(_f32(v, 'v')), _p(_f32(g, 'g')), _p(w16),
+              p.numel(), code, _p(step_dev), _p(lr_dev), _nd(gate), float(beta1), float(beta2), float(eps), int(bool(zero_grad)),
+              _p(clear_flag), _p(table), int(field), int(n_net), ctypes.byref(rider), _stream())
+        return
     if pair is not None:
         # (perf_adam_step_dev_pair: the same step, which also stores every table entry into its field's half of the pair table)
         table, field, n_net = pair
@@ -383,11 +392,13 @@ class Workspace:
 
 
 def field_bwd(grid: GridConfig, mlp: MlpConfig, x01, w16_net, feat16, dout, sel=None, fixed=True, redo=True, hr_state=None, n_dev=None,
-              grad=None, extra=0, book=None, ws=None):
+              grad=None, extra=0, book=None, ws=None, riders=None):
     """The whole backward of one field in ONE boundary call (perf_field_bwd: MLP backward -> grid backward -> predicated fp32 repair)
     -> flat fp32 gradient [network | grid (+ `extra` trailing slots)].  feat16: [L, n, 2] or an IndexedFeat.  ws (a Workspace): the
     holder of the call's scratch memory (MLP partials, tile codes, dfeat), grown on demand: consecutive backwards on one stream reuse
-    it -- do not overlap two backwards with one holder on different streams.  ws=None: a block of this call's own."""
+    it -- do not overlap two backwards with one holder on different streams.  ws=None: a block of this call's own.
+    riders = (rider_draw(...) or None, rider_count(...) or None): stages A and B of the step riders in the grid backward's launches
+    (perf_field_bwd_riders); needs the one-call path -- a per-launch timing pass cannot carry them."""
     index, stride = None, 0
     if isinstance(feat16, IndexedFeat):
         feat16, index = feat16.feat, feat16.index
@@ -397,6 +408,8 @@ def field_bwd(grid: GridConfig, mlp: MlpConfig, x01, w16_net, feat16, dout, sel=
     n_all = mlp.n_params + grid.n_params
     if grad is None:
         grad = torch.empty(n_all + extra, dtype=torch.float32, device=dev)
+    if riders is not None and (_PROF is not None or not FIELD_BWD_ONE_CALL):
+        raise _lib.PerfError('field_bwd: riders need the one-call backward (no per-launch timing pass)')
     if _PROF is not None or not FIELD_BWD_ONE_CALL:
         # per-launch timing (start_kernel_timing: bench.py's `kernels` / `roofline` blocks): the same three entry points one by one,
         # so that each is bracketed by its own pair of events
@@ -412,19 +425,25 @@ def field_bwd(grid: GridConfig, mlp: MlpConfig, x01, w16_net, feat16, dout, sel=
     if nbytes < 0:
         raise _lib.PerfError('perf_field_bwd_workspace_bytes: bad arguments')
     ws = (ws or Workspace()).get(nbytes, dev)
-    if book is not None and fixed and redo and hr_state is not None and n > 0 and book.args['overflow'] is not None \
-            and book.args['overflow'].data_ptr() == overflow_flag(dev).data_ptr():
-        # book (a StepBook): the step's bookkeeping rides in the repair launch (perf_field_bwd_book) -- one launch per step fewer; the flag
-        # stays for adam_step_dev(clear_flag=...)
-        sb = book.struct()
-        _call('perf_field_bwd_book', ctypes.byref(gd), ctypes.byref(md), _p(_f32(x01, 'x01')), _p(w16_net), _p(feat16), _p(index), stride, _p(sel),
-              _p(_f32(dout, 'dout')), _p(grad), _p(overflow_flag(dev)), _p(hr_state), _p(ws), ws.numel() * 4, n, _nd(n_dev),
-              dtype_code(w16_net.dtype), ctypes.byref(sb), _stream())
+    with_book = (book is not None and fixed and redo and hr_state is not None and n > 0 and book.args['overflow'] is not None
+                 and book.args['overflow'].data_ptr() == overflow_flag(dev).data_ptr())
+    # book (a StepBook): the step's bookkeeping rides in the repair launch (perf_field_bwd_book) -- one launch per step fewer; the flag
+    # stays for adam_step_dev(clear_flag=...)
+    sb = book.struct() if with_book else None
+    head = (ctypes.byref(gd), ctypes.byref(md), _p(_f32(x01, 'x01')), _p(w16_net), _p(feat16), _p(index), stride, _p(sel), _p(_f32(dout, 'dout')), _p(grad))
+    flags = (int(bool(fixed)), int(bool(fixed and redo)))
+    state = (_p(overflow_flag(dev)) if fixed else None, _p(hr_state) if fixed else None)
+    tail = (_p(ws), ws.numel() * 4, n, _nd(n_dev), dtype_code(w16_net.dtype))
+    if riders is not None:
+        draw, count = riders
+        _call('perf_field_bwd_riders', *head, *flags, *state, *tail, ctypes.byref(sb) if with_book else None,
+              ctypes.byref(draw) if draw is not None else None, ctypes.byref(count) if count is not None else None, _stream())
+    elif with_book:
+        _call('perf_field_bwd_book', *head, *state, *tail, ctypes.byref(sb), _stream())
+    else:
+        _call('perf_field_bwd', *head, *flags, *state, *tail, _stream())
+    if with_book:
         book.done = True
-        return grad
-    _call('perf_field_bwd', ctypes.byref(gd), ctypes.byref(md), _p(_f32(x01, 'x01')), _p(w16_net), _p(feat16), _p(index), stride, _p(sel),
-          _p(_f32(dout, 'dout')), _p(grad), int(bool(fixed)), int(bool(fixed and redo)), _p(overflow_flag(dev)) if fixed else None,
-          _p(hr_state) if fixed else None, _p(ws), ws.numel() * 4, n, _nd(n_dev), dtype_code(w16_net.dtype), _stream())
     return grad
 
 
@@ -1960,6 +1979,43 @@ def draw_train_batch(seed, counter, pool_lo, pool_hi, n_local, first_global, o_a
           _p(normal_all), _p(out['o']), _p(out['d']), _p(out['color']), _p(out['dist']), _p(out['normal']), _p(out['indices']),
           _p(out['jitter']), _p(out['noise']), _p(out['bg']), _stream())
     return out
+
+
+# ---- step riders (include/perf_hip_riders.h): the argument blocks of the three stages.  The tensors are the caller's to keep alive. ----
+def _q(t):
+    return None if t is None else _p(t).value
+
+
+def rider_draw(seed, counter, pool_lo, pool_hi, n_local, first_global, o_all, d_all, color_all, dist_all, normal_all, out, t0_scale, t0_base,
+               step, max_steps, runs, marched_live=None, marched_keep=None):
+    """Stage A: draw_train_batch(...) into the tensors of `out` (a dict as draw_train_batch returns) + lattice_runs((out['jitter'], t0_scale,
+    t0_base), step, max_steps) into `runs`; [marched_keep = marched_live first]."""
+    _nd(counter)
+    return _lib.RiderDraw(int(seed) & 0xFFFFFFFFFFFFFFFF, _q(counter), _q(_ticket(o_all.device)), int(pool_lo), int(pool_hi), int(n_local), int(first_global),
+                          _q(_f32(o_all, 'o')), _q(_f32(d_all, 'd')), _q(_f32(color_all, 'color')), _q(_f32(dist_all, 'dist')), _q(normal_all),
+                          _q(out['o']), _q(out['d']), _q(out['color']), _q(out['dist']), _q(out['normal']), _q(out.get('indices')),
+                          _q(out['jitter']), _q(out['noise']), _q(out['bg']), float(t0_scale), float(t0_base), float(step), int(max_steps), _q(runs),
+                          _q(marched_live), _q(marched_keep))
+
+
+def rider_count(rays_o, rays_d, t0, occ_bits, res, aabb, far_plane, step, max_steps, occ_coarse, masks, counts):
+    """Stage B: occ_march_count(rays_o, rays_d, t0 = (u, scale, base, runs), ...) into `masks` / `counts`."""
+    u, scale, base, runs = t0
+    a = _aabb6(aabb)
+    return _lib.RiderCount(_q(_f32(rays_o, 'rays_o')), _q(_f32(rays_d, 'rays_d')), _q(_f32(u, 't0')), float(scale), float(base), int(rays_o.shape[0]),
+                           _q(occ_bits), _q(occ_coarse), int(res), a, float(far_plane), float(step),
+                           int(max_steps), _q(runs), _q(masks), _q(counts))
+
+
+def rider_write(t0, masks, counts, offsets, total, capacity, step, max_steps, rays_o, rays_d, points_aabb, ri, ts, te, packed, x01, sel):
+    """Stage C: exclusive_scan_i32(counts) into `offsets` / `total` + occ_march_write(t0 = (u, scale, base, runs), ..., points_aabb) into the
+    sample arrays."""
+    u, scale, base, runs = t0
+    a = _aabb6(points_aabb)
+    _nd(total)
+    return _lib.RiderWrite(_q(_f32(u, 't0')), float(scale), float(base), int(counts.shape[0]), float(step), int(max_steps), _q(runs), _q(masks), _q(counts),
+                           _q(offsets), _q(total), int(capacity), _q(ri), _q(ts), _q(te), _q(packed), _q(rays_o), _q(rays_d),
+                           a, _q(x01), _q(sel))
 
 
 def pdf_resample(s_in, cdf, n_out, tau=None):

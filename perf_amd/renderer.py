@@ -72,7 +72,7 @@ class NeRFOCCRenderer(nn.Module):
     # The render is cut in two stages so that a data-parallel trainer can overlap the gradient all-reduce of step k
     # with everything of step k+1 that does not depend on the parameters being updated (scene.py).
     def stage_sample(self, nerf: NGPNeRF, estimator: OccGridEstimator, rays_o, rays_d, rand=None, with_rgb=False,
-                     keep_features=False, pair=None):
+                     keep_features=False, pair=None, marched=None):
         """Sampling (marching, the no-grad density pass and visibility compaction of nerf_renderer.py:145-155), sample
         positions and -- with_rgb -- the colour field without gradient.  Returns a dict consumed by stage_composite, or
         None when the batch has no sample.  With self.sample_capacity set every per-sample array has that many rows and
@@ -81,7 +81,9 @@ class NeRFOCCRenderer(nn.Module):
         the sampler's own density pass.
         pair (a fields.PairTable with both halves current; one-phase sync-free sampler): the density pass encodes BOTH fields with one
         gather per table entry; st['feat0'] as with keep_features, st['feat0_b'] = the colour field's features of the kept samples (rows
-        of the marched samples' array), and -- with_rgb -- the colour render is computed from them without a second encode."""
+        of the marched samples' array), and -- with_rgb -- the colour render is computed from them without a second encode.
+        marched: the march of these rays (draw-independent front end: lattice tables, counting pass, offsets, write pass) done ahead of
+        time -- OccGridEstimator.sampling_ex(marched=...); this call then is the density pass and the compaction only."""
         rays_o = rays_o.contiguous().float(); rays_d = rays_d.contiguous().float()
         rand = rand or {}
         if pair is not None and (self.sample_capacity is None or self.head_samples is not None or self.early_stop_eps <= 0):
@@ -98,7 +100,7 @@ class NeRFOCCRenderer(nn.Module):
             rays_o, rays_d, sigma_points_fn=sigma_points_fn, near_plane=self.near_plane, far_plane=self.far_plane,
             render_step_size=self.render_step_size, early_stop_eps=self.early_stop_eps, stratified=nerf.training,
             cone_angle=0., alpha_thre=0., jitter=rand.get('jitter'), max_steps=self.max_steps, capacity=self.sample_capacity,
-            points_aabb=nerf._aabb_host, head_samples=self.head_samples, lattice=self.lattice)
+            points_aabb=nerf._aabb_host, head_samples=self.head_samples, lattice=self.lattice, marched=marched)
         if sm.n_dev is None and sm.ray_indices.numel() <= 0:
             return None
         x01, sel = sm.x01, sm.sel

@@ -387,13 +387,14 @@ class FusedAdam:
 
     book_in_repair_launch = os.environ.get('PERF_BOOK_IN_REPAIR_LAUNCH', '1') != '0'
 
-    def step(self, gate=None, counters=None, n_marched=None, n_kept=None, capacity=0, remote_flags=None, book=None):
+    def step(self, gate=None, counters=None, n_marched=None, n_kept=None, capacity=0, remote_flags=None, book=None, rider=None):
         """gate (device int64 [1], optional): the number of samples behind this gradient.  The step is TAKEN unless the gate
         is 0 (the reference skips batches without samples, nerf.py:204-206), the fixed-point grid backward raised its
         overflow flag, or the batch was truncated at `capacity` samples -- decided on the device by perf_step_bookkeeping,
         which also advances the step count and accumulates `counters` (THIS rank's statistics; n_kept defaults to the gate)."""
         p = self.net.params
         if p.grad is None:
+            assert rider is None, 'a rider needs the launch it rides in'
             return
         g = self.param_groups[0]
         self.refresh_lr()
@@ -409,7 +410,7 @@ class FusedAdam:
         half = getattr(self.net, '_pair_half', None)        # (fields.NGPNeRF.use_pair: this network's half of a pair table)
         ops.adam_step_dev(p.data, self.exp_avg, self.exp_avg_sq, p.grad[:p.numel()], self.step_dev, self.lr_dev, g['betas'][0],
                           g['betas'][1], g['eps'], w16=self.w16, zero_grad=False, gate=self.eff_gate, clear_flag=flag if rode else None,
-                          pair=(half[0].buf, half[1], self.net.mlp.n_params) if half is not None else None)
+                          pair=(half[0].buf, half[1], self.net.mlp.n_params) if half is not None else None, rider=rider)
         p.grad = None                              # the next backward installs a fresh gradient (no accumulate pass)
         self.net.set_working_copy(self.w16)        # the kernel wrote the refreshed 16-bit copy
         if half is not None:
@@ -517,6 +518,12 @@ class NeRFScene:
         # encode; the colour step has one evaluation of each field in either order and always pairs in the sampler's pass.
         self.pair_encode = True
         self._geo_pre = None
+        # Step riders (perf_amd/step_riders.py): the fused geometry step of a single process consumes a batch whose draw and march were
+        # produced while the PREVIOUS step's backward ran -- as workgroups riding in its launches -- and has its own backward produce the
+        # next one.  Bit-identical training (tests/test_gpu_step_riders_train.py); PERF_STEP_RIDERS=0 keeps the stand-alone chain (A/B runs).
+        # ('ab': stages A and B ride, offsets + write pass stay stand-alone launches at the head of the consuming step -- the A/B of stage C)
+        self.step_riders = {'0': False, 'ab': 'ab'}.get(os.environ.get('PERF_STEP_RIDERS', '1'), True)
+        self._march_set = None
         self._ratio_dev = torch.zeros((), dtype=torch.float32, device='cuda')   # distortion-loss ramp min(2*progress, 1)
         # device-side statistics of perf_step_bookkeeping (int64 [8]): {marched, kept, steps, largest batch, steps skipped for
         # fixed-point overflow, steps skipped for truncation}.  bench.py reads them once after the timed region: throughput is
@@ -647,6 +654,7 @@ class NeRFScene:
 
     def prepare_occupancy(self, sup_pool, warmup='direct'):
         self._geo_pre = None           # a batch prefetched under the previous episode's pool / occupancy must not be consumed
+        self._riders_drop()
         self._restore_capacity()
         self.estimator = OccGridEstimator(roi_aabb=self.aabb, resolution=256, levels=1).cuda()
         self.estimator.train()
@@ -775,6 +783,7 @@ class NeRFScene:
             self._log_scalars(kind, self.lr_at(conf, iter_i / n_iters))
             if callback:
                 callback(kind, iter_i)
+        self._riders_drop()            # (the batch the last step's riders produced: nobody consumes it, its draw is taken back)
 
     def _log_scalars(self, kind, lr):
         """nerf.py:213,238,255 (geometry step) / :286,295 (colour step): the step's loss terms and learning rate, tagged with the
@@ -817,6 +826,7 @@ class NeRFScene:
         [, normals: with_normals])."""
         dist, rank, world = self._dist()
         self._check_dp_layout(dist)
+        self._riders_drop()            # (a batch produced ahead by the riders is not the next one of the stream any more)
         if self._rng_counter is None:
             self._rng_seed = int(torch.initial_seed())
             self._rng_counter = torch.zeros(1, dtype=torch.int64, device=sup_pool.all_sup_colors.device)
@@ -926,6 +936,55 @@ class NeRFScene:
                 st = st if st is not None else False
         return {'rays': rays, 'gt_depths': gt_depths, 'gt_normals': gt_normals, 'bs': bs, 'dist_info': dist_info, 'st': st, 'rand': rand}
 
+    # ---- step riders: the next batch's draw and march inside this step's backward (perf_amd/step_riders.py) ------------------------
+    def _riders_drop(self):
+        """Forget the batch the riders produced ahead (occupancy update, new pool / phase / episode, capacity change, another consumer of the
+        draw stream): its draw is taken back -- the device generator is a pure function of (seed, counter) --, so the k-th batch consumed
+        stays the k-th batch drawn; the next step falls back to the stand-alone chain."""
+        ms = getattr(self, '_march_set', None)
+        self._march_set = None
+        if ms is not None:
+            self._rng_counter -= 1
+
+    def _riders_ok(self, optimizer, rand, generator):
+        """On by default only where it was built and measured: single process, fused geometry step, sample capacity set, one-phase
+        sampler, per-ray origins, fused Adam behind the one-call backward."""
+        from . import step_riders
+        net = self.nerf.geo_mlp
+        return (self.step_riders and self.fused_steps and isinstance(optimizer, FusedAdam) and self._dist()[0] is None
+                and self._use_device_rng(rand, generator) and self.nerf.training and getattr(self, 'estimator', None) is not None
+                and step_riders.supported(self.renderer, self.estimator, self.train_conf.pixel_loss_batch_size)
+                and self._layout() == 'tcnn' and (net.grid_grad_accum != 'fixed' or net.redo_supported)
+                and ops._PROF is None and ops.FIELD_BWD_ONE_CALL and net.params.numel() >= 1024
+                # (what perf_adam_step_dev_riders needs of its arrays: four elements per thread)
+                and all(t.data_ptr() % 16 == 0 for t in (net.params.data, optimizer.exp_avg, optimizer.exp_avg_sq))
+                and optimizer.w16 is not None and optimizer.w16.data_ptr() % 8 == 0)
+
+    def _march_ready(self, sup_pool):
+        """The MarchSet the next geometry step consumes: the one the previous step's riders filled when nothing it depends on has changed
+        since, else a fresh one filled by the stand-alone kernels."""
+        from . import step_riders
+        r, est = self.renderer, self.estimator
+        if self._rng_counter is None:
+            self._rng_seed = int(torch.initial_seed())
+            self._rng_counter = torch.zeros(1, dtype=torch.int64, device=sup_pool.all_sup_colors.device)
+        bs = self.train_conf.pixel_loss_batch_size
+        mode = self.pixel_sup_rand_mode
+        lo, hi = (0, len(sup_pool)) if mode == 'by_all_pixels' else sup_pool._ranges[0 if mode == 'only_first' else -1]
+        bits = est.occ_bits()
+        sampling = (float(r.near_plane), float(r.far_plane), float(r.render_step_size), step_riders.max_steps_of(r, est), r.lattice)
+        key = (id(sup_pool), sup_pool.all_sup_colors.data_ptr(), lo, hi, bs, self._rng_seed, id(est), bits.data_ptr(), est._bits_version, sampling,
+               int(r.sample_capacity), tuple(float(v) for v in self.nerf._aabb_host), self.step_riders)
+        ms = self._march_set
+        if ms is not None and ms.key == key:
+            return ms
+        self._riders_drop()
+        pool_args = (lo, hi, 0, sup_pool.all_sup_rays.o, sup_pool.all_sup_rays.d, sup_pool.all_sup_colors, sup_pool.all_sup_distances,
+                     sup_pool.all_sup_normals, False)
+        self._march_set = step_riders.MarchSet(key, pool_args, self._rng_seed, self._rng_counter, bs, est, sampling, int(r.sample_capacity),
+                                               self.nerf._aabb_host, stage_c=self.step_riders != 'ab').fill()
+        return self._march_set
+
     @staticmethod
     def _rand_rows(rows, n_local, dist_info, device):
         """torch.rand(rows, n_local) single-process; with W ranks the rank's column slice of torch.rand(rows, W * n_local)."""
@@ -953,7 +1012,7 @@ class NeRFScene:
 
     DP_EXTRA = 3           # trailing slots of the data-parallel gradient buffer: [sample count, overflow flag, truncated]
 
-    def _apply_grad(self, net, grad, optimizer, dist_info, overlap, n_kept=None, n_marched=None, book=None):
+    def _apply_grad(self, net, grad, optimizer, dist_info, overlap, n_kept=None, n_marched=None, book=None, rider=None):
         """[one RCCL all-reduce of the flat gradient] -> Adam.  n_kept: number of samples behind `grad` (device int64 [1], or a
         host int in the eager variable-count path).  Under data parallelism three trailing slots of the gradient buffer travel
         with it: the sample count -- the optimizer step is skipped when NO rank had samples (the reference's
@@ -1010,7 +1069,7 @@ class NeRFScene:
         if isinstance(optimizer, FusedAdam):
             optimizer.step(gate=gate, counters=self.sample_counters, n_marched=n_marched,
                            n_kept=n_kept if torch.is_tensor(n_kept) else None, capacity=self.renderer.sample_capacity or 0,
-                           remote_flags=remote, book=book)
+                           remote_flags=remote, book=book, rider=rider)
         else:
             if gate is None or int(gate.item()) > 0:
                 optimizer.step()
@@ -1057,13 +1116,18 @@ class NeRFScene:
         net.params.grad = None
         self._poll_health(net)
 
-    def _backward_and_step(self, net, optimizer, dist_info, st, w16, feat, dout, beside_stats=None, beside_grads=None):
+    def _backward_and_step(self, net, optimizer, dist_info, st, w16, feat, dout, beside_stats=None, beside_grads=None, riders=None):
         """The tail of a fused step: backward of `net` (tcnn.field_backward) -> [gradient exchange] -> optimizer.  st: the sampler's
         stage of this step; falsy: this rank has no sample at all (it still takes part in every collective: the collectives stay
         matched across ranks).  beside_stats / beside_grads: callables run while the statistics all-gather (sharded mode) / the
-        gradient exchange are in flight."""
+        gradient exchange are in flight.  riders (a step_riders.MarchSet; single process): the backward's launches and the optimizer's carry
+        the stages that refill it."""
         dp = dist_info[0] is not None
         sharded = self._sharded(dist_info, optimizer)
+        assert riders is None or (st and not dp), 'step riders: single process, a batch with sample arrays'
+        rd = riders.riders() if riders is not None else None
+        if riders is not None:
+            riders.stale = True        # (from here on the set's marched samples belong to the batch the riders produce)
         if not st:
             if sharded:
                 self._dp_sharded_step(net, optimizer, dist_info, None, None, None, None, None, None, None)
@@ -1077,9 +1141,9 @@ class NeRFScene:
         book = self._step_book(optimizer, dist_info, n_dev, n_marched)
         # (torch.optim.Adam has no perf_step_bookkeeping behind it to consume the overflow flag)
         grad = _tcnn.field_backward(net, x01, w16, feat, sel, dout, n_dev=n_dev, extra=self.DP_EXTRA if dp else 0, book=book,
-                                    consume_flag=not self.fused_adam)
+                                    consume_flag=not self.fused_adam, riders=rd[:2] if rd is not None else None)
         self._apply_grad(net, grad, optimizer, dist_info, beside_grads if dp else None, n_kept=n_dev if n_dev is not None else x01.shape[0],
-                         n_marched=n_marched, book=book)
+                         n_marched=n_marched, book=book, rider=rd[2] if rd is not None else None)
 
     def sync_params(self):
         """Sharded data parallelism keeps the fp32 master of a table slice only on its owner: refresh the replicas (one fp32
@@ -1106,7 +1170,16 @@ class NeRFScene:
         reads the device: sample counts stay in device memory (st['n_dev'])."""
         tc = self.train_conf
         rand = rand or {}
-        pre = self._geo_pre or self._geo_prefetch(sup_pool, rand, generator)
+        ms = None
+        if self._geo_pre is None and self._riders_ok(optimizer, rand, generator):
+            # step riders: this batch was drawn and marched inside the previous step's backward (or, the first time, just now by the
+            # stand-alone kernels); the backward below refills the set for the next step
+            ms = self._march_ready(sup_pool)
+            g = ms.draw
+            pre = {'rays': Rays(g['o'], g['d']), 'gt_depths': g['dist'], 'gt_normals': g['normal'], 'bs': self.train_conf.pixel_loss_batch_size,
+                   'dist_info': (None, 0, 1), 'st': None, 'rand': {'jitter': g['jitter'], 'noise': g['noise'], 'bg': g['bg']}}
+        else:
+            pre = self._geo_pre or self._geo_prefetch(sup_pool, rand, generator)
         self._geo_pre = None
         rays, gt_depths, bs, dist_info = pre['rays'], pre['gt_depths'], pre['bs'], pre['dist_info']
         st = pre['st']
@@ -1121,14 +1194,16 @@ class NeRFScene:
             strict_pair = pair if not self.reuse_sampling_features else None
             st = self.renderer.stage_sample(self.nerf, self.estimator, rays.o, rays.d, rand, with_rgb=with_rgb and strict_pair is None,
                                             keep_features=self.reuse_sampling_features and self.renderer.sample_capacity is not None,
-                                            pair=pair if strict_pair is None else None)
+                                            pair=pair if strict_pair is None else None,
+                                            marched=ms.marched(force=self._capturing) if ms is not None else None)
         else:
             strict_pair = None
         geo = self.nerf.geo_mlp
         if not st:                             # (None, or False from the prefetch: no samples on this rank)
             return self._backward_and_step(geo, optimizer, dist_info, None, None, None, None)
         x01, sel, packed, ts, te, n_dev = st['x01'], st['sel'], st['packed'], st['t_starts'], st['t_ends'], st['n_dev']
-        self._last_counts = (st['n_marched_dev'], n_dev)
+        # (riders: stage C replaces the marched count by the next batch's before the step ends; stage A keeps this batch's for the reports)
+        self._last_counts = (ms.keep if (ms is not None and ms.stage_c) else st['n_marched_dev'], n_dev)
         n_net = geo.mlp.n_params
         w16 = geo.working_copy()
         feat = st.get('feat0')
@@ -1187,7 +1262,7 @@ class NeRFScene:
         # (a callable makes the collective asynchronous: the sharded exchange gets one only when there is something to run)
         busy = self.overlap_comm and dist_info[0] is not None and (not sharded or (defer_color and not exact) or want_prefetch)
         self._backward_and_step(geo, optimizer, dist_info, st, w16, feat, dsig.view(-1, 1),
-                                beside_stats=color_now if (defer_color and exact) else None, beside_grads=beside_grads if busy else None)
+                                beside_stats=color_now if (defer_color and exact) else None, beside_grads=beside_grads if busy else None, riders=ms)
 
     @torch.no_grad()
     def _app_step_fused(self, optimizer, sup_pool, progress, rand, generator):
@@ -1377,6 +1452,12 @@ class NeRFScene:
                 raise RuntimeError('make_graphed_step: a prefetched batch is pending; run the last eager geometry step with prefetch_next=False')
             self._rng_counter -= 1
             self._geo_pre = None
+        if kind == 'geo' and self._riders_ok(optimizer, None, None):
+            # step riders: the captured step consumes the set its previous replay refilled -- the first replay's batch must be there before
+            # the capture (left by the last eager step's riders, or filled here by the stand-alone kernels)
+            self._march_ready(sup_pool)
+        else:
+            self._riders_drop()        # (inside the capture the draw taken back would be baked into every replay)
         torch.cuda.synchronize()
         count = getattr(self, 'count_graph_nodes', False)
         graph = torch.cuda.CUDAGraph(keep_graph=True) if count else torch.cuda.CUDAGraph()
@@ -1396,14 +1477,26 @@ class NeRFScene:
 
         # bwd_ws: the backward workspace the captured launches were recorded with -- the network's holder may grow past it (an eager
         # step with more samples), and the block must not go back to the allocator while the graph can still be replayed
+        # set: the MarchSet whose addresses the captured riders and the captured density pass hold (step riders; None otherwise) -- kept
+        # alive like the workspace, and the ONLY set this graph may be replayed on: see replay()
         state = {'graph': graph, 'n': 0, 'counts': self._last_counts, 'capacity': self.renderer.sample_capacity,
-                 'mode': optimizer.net.grid_grad_accum, 'bwd_ws': optimizer.net.bwd_workspace.block}
+                 'mode': optimizer.net.grid_grad_accum, 'bwd_ws': optimizer.net.bwd_workspace.block,
+                 'set': self._march_set if kind == 'geo' else None}
 
         def replay(lr=None, progress=None):
             if optimizer.sched_table is None:                    # no device-side schedule: refresh the two scalars
                 optimizer.lr_dev.fill_(lr)
                 if kind == 'geo':
                     self._ratio_dev.fill_(float(np.min([progress * 2., 1])))
+            if state['set'] is None:
+                self._riders_drop()    # (this graph draws for itself: a batch some other step's riders produced ahead is not the next of the stream)
+            elif self._march_set is not state['set']:
+                # Step riders: the set this graph consumes and refills was dropped since its last replay (another consumer of the draw stream --
+                # a colour step, an eager step under per-launch timing --, a new occupancy, the end of a phase) and its draw taken back:
+                # replayed as it is, the graph would train on a batch whose draw number somebody else has used.  Capture again: the
+                # new graph starts from a set filled by the stand-alone kernels with the draw that is next in the stream.
+                new = self.make_graphed_step(kind, optimizer, sup_pool, warmup=0)
+                state.update(new.state)
             state['graph'].replay()
             state['n'] += 1
             if kind == 'geo':

@@ -89,13 +89,14 @@ def field_apply(module, x01, params, sel=None, n_dev=None):
     return _FieldFn.apply(x01, params, sel, module, n_dev)
 
 
-def field_backward(module, x01, w16, feat, sel, dout, n_dev=None, extra=0, book=None, consume_flag=False):
+def field_backward(module, x01, w16, feat, sel, dout, n_dev=None, extra=0, book=None, consume_flag=False, riders=None):
     """Flat fp32 gradient [network | grid (+ `extra` trailing slots)] of one field: THE sequence of a field's backward, for the autograd
     Functions and the fused steps alike.  Fixed-point accumulation never costs a step: should a field of the grid gradient near the
     int32 range (device flag), the predicated repair launch right behind the backward rewrites the table gradient with fp32 LDS
     accumulation -- a no-op dispatch otherwise; the host is not asked (no read-back per backward, capturable).  book (a StepBook):
     the step's bookkeeping rides in the repair launch.  consume_flag: the caller has no perf_step_bookkeeping behind it to consume
-    the flag (autograd, torch.optim.Adam) -- left set, every later backward would run its (slow) fp32 repair as well."""
+    the flag (autograd, torch.optim.Adam) -- left set, every later backward would run its (slow) fp32 repair as well.
+    riders: ops.field_bwd's (the one-call sequence only)."""
     n_net = module.mlp.n_params
     fixed = module.grid_grad_accum == 'fixed'
     dout = dout.contiguous().float()
@@ -103,12 +104,13 @@ def field_backward(module, x01, w16, feat, sel, dout, n_dev=None, extra=0, book=
     if not fixed or module.redo_supported:
         # ONE boundary call: MLP backward -> grid backward -> predicated repair launch (perf_field_bwd), the network's own workspace
         grad = ops.field_bwd(module.grid, module.mlp, x01, w16[:n_net], feat, dout, sel, fixed=fixed, redo=True, hr_state=hr_state,
-                             n_dev=n_dev, extra=extra, book=book, ws=module.bwd_workspace)
+                             n_dev=n_dev, extra=extra, book=book, ws=module.bwd_workspace, riders=riders)
         if fixed and consume_flag:
             ops.overflow_flag(x01.device).zero_()
         return grad
     # (grids with levels beyond LDS owners -- BASELINE config 5 -- have no repair launch: a raised flag is the caller's; one with
     #  nothing behind it to consume the flag asks the host and redoes the table gradient in fp32)
+    assert riders is None, 'riders need the one-call backward'
     n_all = n_net + module.grid.n_params
     grad = torch.empty(n_all + extra, dtype=torch.float32, device=x01.device)
     res = ops.mlp_bwd(module.mlp, w16[:n_net], feat, dout, sel, want_absmax=True, n_dev=n_dev, dw_out=grad[:n_net])

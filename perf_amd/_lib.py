@@ -318,6 +318,33 @@ _SIGS_RIDERS = {
     'perf_adam_step_dev_riders': (c_int, [P, P, P, P, P, c_int64, c_int, P, P, P, c_float, c_float, c_float, c_int, P, P, c_int, c_int64, POINTER(RiderWrite), P]),
 }
 
+
+def _expects(label):
+    return label + ' version {has}, this binding expects {want}'
+
+
+# The units of the library, each versioned on its own: (signatures, version function, the version this binding was written against, what
+# a mismatch is reported as after "<library> has ", ((size function, the bytes this binding expects), ...)).  A new unit adds one entry.
+_UNITS = (
+    (_SIGS, 'perf_version', ABI_VERSION, _expects('ABI'), ()),
+    (_SIGS_EXT, 'perf_ext_version', EXT_ABI_VERSION, _expects('extension ABI'), ()),
+    (_SIGS_SPHERE, 'perf_sphere_version', SPHERE_ABI_VERSION, _expects('sphere-field ABI'), ()),
+    (_SIGS_PAIR, 'perf_pair_version', PAIR_ABI_VERSION, _expects('pair-table ABI'), ()),
+    (_SIGS_JOINT, 'perf_joint_version', JOINT_ABI_VERSION, _expects('joint-alignment ABI'), ()),
+    (_SIGS_MESH, 'perf_mesh_version', MESH_ABI_VERSION, _expects('mesh ABI'), ()),
+    (_SIGS_BRICKMESH, 'perf_brickmesh_version', BRICKMESH_ABI_VERSION, _expects('brick-mesh ABI'), ()),
+    (_SIGS_MESHCC, 'perf_meshcc_version', MESHCC_ABI_VERSION, _expects('mesh-component ABI'), ()),
+    (_SIGS_MESHVIS, 'perf_meshvis_version', MESHVIS_ABI_VERSION,
+     'visibility-cull ABI version {has} and a view of {has_sizes[0]} bytes, this binding expects {want} and {want_sizes[0]}',
+     (('perf_meshvis_sizeof_view', MESHVIS_VIEW_BYTES),)),
+    (_SIGS_MESHSIMP, 'perf_meshsimp_version', MESHSIMP_ABI_VERSION, _expects('mesh-simplification ABI'), ()),
+    (_SIGS_MESHCOLOR, 'perf_meshcolor_version', MESHCOLOR_ABI_VERSION, _expects('mesh-colouring ABI'), ()),
+    (_SIGS_MESHRAY, 'perf_meshray_version', MESHRAY_ABI_VERSION, _expects('mesh ray-casting ABI'), ()),
+    (_SIGS_RIDERS, 'perf_riders_version', RIDERS_ABI_VERSION, 'step-rider ABI version {has} or other argument blocks than this binding ({want})',
+     (('perf_sizeof_rider_draw', ctypes.sizeof(RiderDraw)), ('perf_sizeof_rider_count', ctypes.sizeof(RiderCount)),
+      ('perf_sizeof_rider_write', ctypes.sizeof(RiderWrite)))),
+)
+
 _lib = None
 
 
@@ -333,53 +360,19 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SPHERE.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_JOINT.items()) + list(_SIGS_MESH.items()) + list(_SIGS_BRICKMESH.items()) + list(_SIGS_MESHCC.items()) + list(_SIGS_MESHVIS.items()) + list(_SIGS_MESHSIMP.items()) + list(_SIGS_MESHCOLOR.items()) + list(_SIGS_MESHRAY.items()) + list(_SIGS_RIDERS.items()):
-        fn = getattr(lib, name, None)
-        if fn is None:
-            raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
-        fn.restype = res
-        fn.argtypes = args
-    # the binding and the library must agree on the ABI version and on the layout of the POD descriptors
-    if lib.perf_version() != ABI_VERSION:
-        raise PerfError(f'{LIB_PATH} has ABI version {lib.perf_version()}, this binding expects {ABI_VERSION}: '
-                        'rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_ext_version() != EXT_ABI_VERSION:
-        raise PerfError(f'{LIB_PATH} has extension ABI version {lib.perf_ext_version()}, this binding expects {EXT_ABI_VERSION}: '
-                        'rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_sphere_version() != SPHERE_ABI_VERSION:
-        raise PerfError(f'{LIB_PATH} has sphere-field ABI version {lib.perf_sphere_version()}, this binding expects {SPHERE_ABI_VERSION}: '
-                        'rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_pair_version() != PAIR_ABI_VERSION:
-        raise PerfError(f'{LIB_PATH} has pair-table ABI version {lib.perf_pair_version()}, this binding expects {PAIR_ABI_VERSION}: '
-                        'rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_joint_version() != JOINT_ABI_VERSION:
-        raise PerfError(f'{LIB_PATH} has joint-alignment ABI version {lib.perf_joint_version()}, this binding expects {JOINT_ABI_VERSION}: '
-                        'rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_mesh_version() != MESH_ABI_VERSION:
-        raise PerfError(f'{LIB_PATH} has mesh ABI version {lib.perf_mesh_version()}, this binding expects {MESH_ABI_VERSION}: '
-                        'rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_brickmesh_version() != BRICKMESH_ABI_VERSION:
-        raise PerfError(f'{LIB_PATH} has brick-mesh ABI version {lib.perf_brickmesh_version()}, this binding expects {BRICKMESH_ABI_VERSION}: '
-                        'rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_meshcc_version() != MESHCC_ABI_VERSION:
-        raise PerfError(f'{LIB_PATH} has mesh-component ABI version {lib.perf_meshcc_version()}, this binding expects {MESHCC_ABI_VERSION}: '
-                        'rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_meshvis_version() != MESHVIS_ABI_VERSION or lib.perf_meshvis_sizeof_view() != MESHVIS_VIEW_BYTES:
-        raise PerfError(f'{LIB_PATH} has visibility-cull ABI version {lib.perf_meshvis_version()} and a view of {lib.perf_meshvis_sizeof_view()} bytes, this binding '
-                        f'expects {MESHVIS_ABI_VERSION} and {MESHVIS_VIEW_BYTES}: rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_meshsimp_version() != MESHSIMP_ABI_VERSION:
-        raise PerfError(f'{LIB_PATH} has mesh-simplification ABI version {lib.perf_meshsimp_version()}, this binding expects {MESHSIMP_ABI_VERSION}: '
-                        'rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_meshcolor_version() != MESHCOLOR_ABI_VERSION:
-        raise PerfError(f'{LIB_PATH} has mesh-colouring ABI version {lib.perf_meshcolor_version()}, this binding expects {MESHCOLOR_ABI_VERSION}: '
-                        'rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_meshray_version() != MESHRAY_ABI_VERSION:
-        raise PerfError(f'{LIB_PATH} has mesh ray-casting ABI version {lib.perf_meshray_version()}, this binding expects {MESHRAY_ABI_VERSION}: '
-                        'rebuild with `python -m perf_amd.build --force`')
-    if lib.perf_riders_version() != RIDERS_ABI_VERSION or (lib.perf_sizeof_rider_draw(), lib.perf_sizeof_rider_count(), lib.perf_sizeof_rider_write()) != (
-            ctypes.sizeof(RiderDraw), ctypes.sizeof(RiderCount), ctypes.sizeof(RiderWrite)):
-        raise PerfError(f'{LIB_PATH} has step-rider ABI version {lib.perf_riders_version()} or other argument blocks than this binding ({RIDERS_ABI_VERSION}): '
-                        'rebuild with `python -m perf_amd.build --force`')
+    for sigs, *_ in _UNITS:
+        for name, (res, args) in sigs.items():
+            fn = getattr(lib, name, None)
+            if fn is None:
+                raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
+            fn.restype = res
+            fn.argtypes = args
+    # the binding and the library must agree on every unit's ABI version and on the layout of the POD descriptors
+    for _, version, want, text, sizes in _UNITS:
+        has, has_sizes, want_sizes = getattr(lib, version)(), [getattr(lib, fn)() for fn, _ in sizes], [n for _, n in sizes]
+        if has != want or has_sizes != want_sizes:
+            raise PerfError(f'{LIB_PATH} has ' + text.format(has=has, want=want, has_sizes=has_sizes, want_sizes=want_sizes)
+                            + ': rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):
         raise PerfError('descriptor layout mismatch between perf_amd/_lib.py and include/perf_hip.h')

@@ -1,8 +1,9 @@
 // What the mesh units (mesh.hip, brickmesh.hip, meshcc.hip, meshvis.hip, meshsimp.hip) compact their streams with: the exclusive scan
-// of uint64 words in levels of 256, the rank of a flagged thread inside its workgroup of 256, and the check of a caller's workspace.
+// of uint64 words in levels of 256 and the rank of a flagged thread inside its workgroup of 256 (the host checks are mesh_check_host.hpp's).
 // The kernels have internal linkage: every unit that includes this header registers its own copies with the runtime.
 #pragma once
 #include "common.hpp"
+#include "mesh_check_host.hpp"
 
 namespace perf {
 
@@ -104,14 +105,6 @@ __device__ __forceinline__ int32_t group_rank(bool flag, uint64_t* __restrict__ 
     }
     if (sums && threadIdx.x == 0) sums[blockIdx.x] = (uint64_t)total;
     return before + __popcll(mask & ((1ull << lane) - 1));
-}
-
-// need: what the unit's perf_*_workspace_bytes returns for the call's sizes
-static int workspace_check(const char* who, int64_t need, const void* workspace, int64_t workspace_bytes) {
-    PERF_REQUIRE(workspace, "%s: NULL workspace", who);
-    PERF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
-    PERF_REQUIRE(workspace_bytes >= need, "%s: the workspace holds %lld bytes, %lld are needed", who, (long long)workspace_bytes, (long long)need);
-    return PERF_OK;
 }
 
 }  // namespace perf

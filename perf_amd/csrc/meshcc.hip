@@ -334,11 +334,7 @@ __global__ void __launch_bounds__(kCcGroup) meshcc_keep_faces_kernel(const int32
 
 // ---- the checks of the entry points -------------------------------------------------------------------------------------------------------
 static int cc_counts_check(const char* who, int64_t n_vertices, int64_t n_faces) {
-    PERF_REQUIRE(n_vertices >= 0, "%s: a negative number of vertices (%lld)", who, (long long)n_vertices);
-    PERF_REQUIRE(n_faces >= 0, "%s: a negative number of faces (%lld)", who, (long long)n_faces);
-    PERF_REQUIRE(n_vertices <= PERF_MESHCC_MAX_VERTICES, "%s: %lld vertices are more than 2^30 (vertex indices are int32)", who, (long long)n_vertices);
-    PERF_REQUIRE(n_faces <= PERF_MESHCC_MAX_FACES, "%s: %lld faces are more than 2^38", who, (long long)n_faces);
-    return PERF_OK;
+    return mesh_counts_check(who, n_vertices, n_faces, PERF_MESHCC_MAX_VERTICES, PERF_MESHCC_MAX_FACES, "2^38");
 }
 
 static int cc_components_check(const char* who, int64_t n_components, int64_t n_vertices) {

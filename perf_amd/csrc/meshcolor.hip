@@ -1,7 +1,9 @@
 // Colour a mesh's vertices from the registered panoramas and build vertex normals from its faces (include/perf_hip_meshcolor.h):
-// normal sums (int64 atomics) -> unit normals; the blend (one launch for all views).  The look-up of the blend is vis_lookup of
-// meshvis.hip restated line for line, keeping the taps and the weights it throws away.
+// normal sums (int64 atomics) -> unit normals; the blend (one launch for all views).  The pixel of the blend's look-up is
+// pano_lookup_device.hpp's, the one the cull (meshvis.hip) runs; this unit keeps the taps and the weights the cull throws away.
 #include "common.hpp"
+#include "mesh_check_host.hpp"
+#include "pano_lookup_device.hpp"
 #include "../../include/perf_hip_meshcolor.h"
 
 namespace perf {
@@ -59,35 +61,15 @@ struct ColTaps {
     float w[4];
 };
 
-// dist and proj of one point in one view: vis_lookup's lines (meshvis.hip), in its order
+// dist and proj of one point in one view: the pixel is pano_lookup_device.hpp's; the taps of pano_tap are kept for the colour maps
 __device__ __forceinline__ void col_lookup(float x, float y, float z, const perf_meshvis_view& pf, float& dist_out, float& proj_out, ColTaps& taps) {
-    const float px = sub_rn(x, pf.t[0]), py = sub_rn(y, pf.t[1]), pz = sub_rn(z, pf.t[2]);
-    float l[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) l[a] = add_rn(add_rn(mul_rn(pf.rt[3 * a], px), mul_rn(pf.rt[3 * a + 1], py)), mul_rn(pf.rt[3 * a + 2], pz));
-    const float dist = sqrtf(add_rn(add_rn(mul_rn(l[0], l[0]), mul_rn(l[1], l[1])), mul_rn(l[2], l[2])));
-    float d[3] = {__fdiv_rn(l[0], dist), __fdiv_rn(l[1], dist), __fdiv_rn(l[2], dist)};
-    const float nn = sqrtf(add_rn(add_rn(mul_rn(d[0], d[0]), mul_rn(d[1], d[1])), mul_rn(d[2], d[2])));
-#pragma unroll
-    for (int a = 0; a < 3; ++a) d[a] = __fdiv_rn(d[a], nn);
-    const float kPi = 3.14159265358979323846f;
-    const float beta = asinf(d[2]), alpha = atan2f(d[1], d[0]);
-    const float row = add_rn(__fdiv_rn(-beta, kPi), 0.5f);
-    const float col = add_rn(-__fdiv_rn(alpha, mul_rn(2.0f, kPi)), 0.5f);
-    const float gx = sub_rn(mul_rn(col, 2.0f), 1.0f), gy = sub_rn(mul_rn(row, 2.0f), 1.0f);
     const int32_t h = pf.height, w = pf.width;
-    float ix = __fdiv_rn(sub_rn(mul_rn(add_rn(gx, 1.0f), (float)w), 1.0f), 2.0f);
-    float iy = __fdiv_rn(sub_rn(mul_rn(add_rn(gy, 1.0f), (float)h), 1.0f), 2.0f);
-    ix = fminf(fmaxf(ix, 0.0f), (float)(w - 1));            // (a NaN becomes 0: fmaxf returns the other operand)
-    iy = fminf(fmaxf(iy, 0.0f), (float)(h - 1));
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = x0 + 1, y1 = y0 + 1;
-    const float wx1 = sub_rn(ix, fx0), wy1 = sub_rn(iy, fy0), wx0 = sub_rn(1.0f, wx1), wy0 = sub_rn(1.0f, wy1);
+    const PanoPixel p = pano_pixel(x, y, z, pf.rt, pf.t, h, w);
+    const float dist = p.dist;
     const float* __restrict__ dmap = pf.distance_map;
     auto where = [&](int yy, int xx) { return (yy >= 0 && yy < h && xx >= 0 && xx < w) ? (int64_t)yy * w + xx : (int64_t)-1; };
-    taps.at[0] = where(y0, x0); taps.at[1] = where(y0, x1); taps.at[2] = where(y1, x0); taps.at[3] = where(y1, x1);
-    taps.w[0] = mul_rn(wx0, wy0); taps.w[1] = mul_rn(wx1, wy0); taps.w[2] = mul_rn(wx0, wy1); taps.w[3] = mul_rn(wx1, wy1);
+    taps.at[0] = where(p.y0, p.x0); taps.at[1] = where(p.y0, p.x1); taps.at[2] = where(p.y1, p.x0); taps.at[3] = where(p.y1, p.x1);
+    taps.w[0] = mul_rn(p.wx0, p.wy0); taps.w[1] = mul_rn(p.wx1, p.wy0); taps.w[2] = mul_rn(p.wx0, p.wy1); taps.w[3] = mul_rn(p.wx1, p.wy1);
     auto at = [&](int t) { return taps.at[t] >= 0 ? dmap[taps.at[t]] : 0.0f; };
     float proj = mul_rn(at(0), taps.w[0]);
     proj = add_rn(proj, mul_rn(at(1), taps.w[1]));
@@ -187,11 +169,7 @@ __global__ void __launch_bounds__(kColGroup) meshcolor_blend_kernel(const float*
 
 // ---- the checks of the entry points -------------------------------------------------------------------------------------------------------
 static int col_counts_check(const char* who, int64_t n_vertices, int64_t n_faces) {
-    PERF_REQUIRE(n_vertices >= 0, "%s: a negative number of vertices (%lld)", who, (long long)n_vertices);
-    PERF_REQUIRE(n_faces >= 0, "%s: a negative number of faces (%lld)", who, (long long)n_faces);
-    PERF_REQUIRE(n_vertices <= PERF_MESHCOLOR_MAX_VERTICES, "%s: %lld vertices are more than 2^30 (vertex indices are int32)", who, (long long)n_vertices);
-    PERF_REQUIRE(n_faces <= PERF_MESHCOLOR_MAX_FACES, "%s: %lld faces are more than 2^31 - 1", who, (long long)n_faces);
-    return PERF_OK;
+    return mesh_counts_check(who, n_vertices, n_faces, PERF_MESHCOLOR_MAX_VERTICES, PERF_MESHCOLOR_MAX_FACES, "2^31 - 1");
 }
 
 static inline unsigned col_groups(int64_t n) { return (unsigned)div_up(n, kColGroup); }

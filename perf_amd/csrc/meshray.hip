@@ -2,6 +2,7 @@
 // the closest hit and the any hit of a batch of rays, the occlusion of the segments from the vertices to the views' centres.  The rule of
 // one face is the header's, line for line, in double; the grid only decides which faces are tested.
 #include "common.hpp"
+#include "mesh_check_host.hpp"
 #include "../../include/perf_hip_meshray.h"
 #include <math.h>
 
@@ -227,10 +228,7 @@ __global__ void __launch_bounds__(kRayGroup) meshray_occluded_kernel(RayGrid g, 
 
 // ---- the checks of the entry points -------------------------------------------------------------------------------------------------------
 static int ray_mesh_check(const char* who, const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces) {
-    PERF_REQUIRE(n_vertices >= 0, "%s: a negative number of vertices (%lld)", who, (long long)n_vertices);
-    PERF_REQUIRE(n_faces >= 0, "%s: a negative number of faces (%lld)", who, (long long)n_faces);
-    PERF_REQUIRE(n_vertices <= PERF_MESHRAY_MAX_VERTICES, "%s: %lld vertices are more than 2^30 (vertex indices are int32)", who, (long long)n_vertices);
-    PERF_REQUIRE(n_faces <= PERF_MESHRAY_MAX_FACES, "%s: %lld faces are more than 2^31 - 1", who, (long long)n_faces);
+    if (int rc = mesh_counts_check(who, n_vertices, n_faces, PERF_MESHRAY_MAX_VERTICES, PERF_MESHRAY_MAX_FACES, "2^31 - 1")) return rc;
     PERF_REQUIRE(vertices || n_vertices == 0, "%s: NULL input (vertices) with vertices", who);
     PERF_REQUIRE(faces || n_faces == 0, "%s: NULL input (faces) with faces", who);
     return PERF_OK;

@@ -417,11 +417,7 @@ __global__ void __launch_bounds__(kSgGroup) meshsimp_resolve_kernel(const uint32
 
 // ---- the checks of the entry points -----------------------------------------------------------------------------------------------------------
 static int sg_counts_check(const char* who, int64_t n_vertices, int64_t n_faces) {
-    PERF_REQUIRE(n_vertices >= 0, "%s: a negative number of vertices (%lld)", who, (long long)n_vertices);
-    PERF_REQUIRE(n_faces >= 0, "%s: a negative number of faces (%lld)", who, (long long)n_faces);
-    PERF_REQUIRE(n_vertices <= PERF_MESHSIMP_MAX_VERTICES, "%s: %lld vertices are more than 2^30 (vertex indices are int32)", who, (long long)n_vertices);
-    PERF_REQUIRE(n_faces <= PERF_MESHSIMP_MAX_FACES, "%s: %lld faces are more than 2^31 - 1 (the face set holds int32 face indices)", who, (long long)n_faces);
-    return PERF_OK;
+    return mesh_counts_check(who, n_vertices, n_faces, PERF_MESHSIMP_MAX_VERTICES, PERF_MESHSIMP_MAX_FACES, "2^31 - 1 (the face set holds int32 face indices)");
 }
 
 static int sg_grid_check(const char* who, const float* lo, float h, int32_t nx, int32_t ny, int32_t nz, SgGrid* grid) {

@@ -1,8 +1,9 @@
 // Cull the faces of a mesh no registered panorama saw (include/perf_hip_meshvis.h): vertex bits (one launch for all views) -> face rule ->
-// compaction by the face mask (mark -> rank -> scan -> write).  The look-up of stage 1 is the arithmetic of pano_reproject_kernel
-// (visibility.hip) restated line for line; the scan and the group rank are mesh_scan_device.hpp's, the compaction mesh_filter_device.hpp's.
+// compaction by the face mask (mark -> rank -> scan -> write).  The look-up of stage 1 is pano_lookup_device.hpp's, the one
+// pano_reproject_kernel (visibility.hip) runs; the scan and the group rank are mesh_scan_device.hpp's, the compaction mesh_filter_device.hpp's.
 #include "common.hpp"
 #include "mesh_filter_device.hpp"
+#include "pano_lookup_device.hpp"
 #include "../../include/perf_hip_meshvis.h"
 
 namespace perf {
@@ -12,39 +13,12 @@ constexpr int kVisViewWords = sizeof(perf_meshvis_view) / 4;
 static_assert(sizeof(perf_meshvis_view) == 64 && alignof(perf_meshvis_view) == 8, "the view descriptor is 64 bytes");
 
 // ---- stage 1 ----------------------------------------------------------------------------------------------------------------------------
-// dist and proj of one point in one view: pano_reproject_kernel's lines, in its order
+// dist and proj of one point in one view
 __device__ __forceinline__ void vis_lookup(float x, float y, float z, const perf_meshvis_view& pf, float& dist_out, float& proj_out) {
-    const float px = sub_rn(x, pf.t[0]), py = sub_rn(y, pf.t[1]), pz = sub_rn(z, pf.t[2]);
-    float l[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) l[a] = add_rn(add_rn(mul_rn(pf.rt[3 * a], px), mul_rn(pf.rt[3 * a + 1], py)), mul_rn(pf.rt[3 * a + 2], pz));
-    const float dist = sqrtf(add_rn(add_rn(mul_rn(l[0], l[0]), mul_rn(l[1], l[1])), mul_rn(l[2], l[2])));
-    float d[3] = {__fdiv_rn(l[0], dist), __fdiv_rn(l[1], dist), __fdiv_rn(l[2], dist)};
-    const float nn = sqrtf(add_rn(add_rn(mul_rn(d[0], d[0]), mul_rn(d[1], d[1])), mul_rn(d[2], d[2])));
-#pragma unroll
-    for (int a = 0; a < 3; ++a) d[a] = __fdiv_rn(d[a], nn);
-    const float kPi = 3.14159265358979323846f;
-    const float beta = asinf(d[2]), alpha = atan2f(d[1], d[0]);
-    const float row = add_rn(__fdiv_rn(-beta, kPi), 0.5f);
-    const float col = add_rn(-__fdiv_rn(alpha, mul_rn(2.0f, kPi)), 0.5f);
-    const float gx = sub_rn(mul_rn(col, 2.0f), 1.0f), gy = sub_rn(mul_rn(row, 2.0f), 1.0f);
     const int32_t h = pf.height, w = pf.width;
-    float ix = __fdiv_rn(sub_rn(mul_rn(add_rn(gx, 1.0f), (float)w), 1.0f), 2.0f);
-    float iy = __fdiv_rn(sub_rn(mul_rn(add_rn(gy, 1.0f), (float)h), 1.0f), 2.0f);
-    ix = fminf(fmaxf(ix, 0.0f), (float)(w - 1));            // (a NaN becomes 0: fmaxf returns the other operand)
-    iy = fminf(fmaxf(iy, 0.0f), (float)(h - 1));
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = x0 + 1, y1 = y0 + 1;
-    const float wx1 = sub_rn(ix, fx0), wy1 = sub_rn(iy, fy0), wx0 = sub_rn(1.0f, wx1), wy0 = sub_rn(1.0f, wy1);
-    const float* __restrict__ dmap = pf.distance_map;
-    auto at = [&](int yy, int xx) { return (yy >= 0 && yy < h && xx >= 0 && xx < w) ? dmap[(int64_t)yy * w + xx] : 0.0f; };
-    float proj = mul_rn(at(y0, x0), mul_rn(wx0, wy0));
-    proj = add_rn(proj, mul_rn(at(y0, x1), mul_rn(wx1, wy0)));
-    proj = add_rn(proj, mul_rn(at(y1, x0), mul_rn(wx0, wy1)));
-    proj = add_rn(proj, mul_rn(at(y1, x1), mul_rn(wx1, wy1)));
-    dist_out = dist;
-    proj_out = proj;
+    const PanoPixel p = pano_pixel(x, y, z, pf.rt, pf.t, h, w);
+    dist_out = p.dist;
+    proj_out = pano_tap(pf.distance_map, h, w, p);
 }
 
 // A workgroup stages its 256 vertices (768 consecutive floats, loaded in three coalesced passes) and the views' descriptors in LDS; a
@@ -183,11 +157,7 @@ __global__ void meshvis_totals_kernel(const uint64_t* __restrict__ first, const 
 
 // ---- the checks of the entry points -------------------------------------------------------------------------------------------------------
 static int vis_counts_check(const char* who, int64_t n_vertices, int64_t n_faces) {
-    PERF_REQUIRE(n_vertices >= 0, "%s: a negative number of vertices (%lld)", who, (long long)n_vertices);
-    PERF_REQUIRE(n_faces >= 0, "%s: a negative number of faces (%lld)", who, (long long)n_faces);
-    PERF_REQUIRE(n_vertices <= PERF_MESHVIS_MAX_VERTICES, "%s: %lld vertices are more than 2^30 (vertex indices are int32)", who, (long long)n_vertices);
-    PERF_REQUIRE(n_faces <= PERF_MESHVIS_MAX_FACES, "%s: %lld faces are more than 2^38", who, (long long)n_faces);
-    return PERF_OK;
+    return mesh_counts_check(who, n_vertices, n_faces, PERF_MESHVIS_MAX_VERTICES, PERF_MESHVIS_MAX_FACES, "2^38");
 }
 
 static int vis_views_check(const char* who, int32_t n_views) {

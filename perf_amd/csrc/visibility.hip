@@ -2,10 +2,12 @@
 // (modules/scene/nerf.py:321-358) and SupInfoPool.geo_check (modules/dataset/sup_info.py:261-302).  Per pixel of a rendered
 // panorama: back-projected point -> direction and distance in a registered panorama's frame -> equirect image coordinate
 // (utils/camera_utils.py:134-151) -> bilinear look-up of that panorama's distance map with grid_sample's border padding /
-// align_corners=False arithmetic -> depth test, folded over the panoramas with max (visibility) or min (consistency).
+// align_corners=False arithmetic (these steps are pano_lookup_device.hpp's, shared with the mesh cull and the mesh colouring)
+// -> depth test, folded over the panoramas with max (visibility) or min (consistency).
 // Then binary morphology with OpenCV's elliptical structuring elements.  One thread per pixel, fully coalesced; the
 // reference runs ~15 torch kernels per registered panorama and two kornia convolutions.
 #include "common.hpp"
+#include "pano_lookup_device.hpp"
 
 namespace perf {
 
@@ -16,37 +18,8 @@ __global__ __launch_bounds__(256) void pano_reproject_kernel(const float* __rest
                                                              float eps, float* __restrict__ mask) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float px = sub_rn(pts[3 * i], pf.t[0]), py = sub_rn(pts[3 * i + 1], pf.t[1]), pz = sub_rn(pts[3 * i + 2], pf.t[2]);
-    // apply_rot(p - t, R^T): matmul row by row (utils/camera_utils.py:44-46)
-    float l[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) l[a] = add_rn(add_rn(mul_rn(pf.rt[3 * a], px), mul_rn(pf.rt[3 * a + 1], py)), mul_rn(pf.rt[3 * a + 2], pz));
-    const float dist = sqrtf(add_rn(add_rn(mul_rn(l[0], l[0]), mul_rn(l[1], l[1])), mul_rn(l[2], l[2])));
-    float d[3] = {__fdiv_rn(l[0], dist), __fdiv_rn(l[1], dist), __fdiv_rn(l[2], dist)};
-    // direction_to_img_coord normalises once more
-    const float nn = sqrtf(add_rn(add_rn(mul_rn(d[0], d[0]), mul_rn(d[1], d[1])), mul_rn(d[2], d[2])));
-#pragma unroll
-    for (int a = 0; a < 3; ++a) d[a] = __fdiv_rn(d[a], nn);
-    const float kPi = 3.14159265358979323846f;
-    const float beta = asinf(d[2]), alpha = atan2f(d[1], d[0]);
-    const float row = add_rn(__fdiv_rn(-beta, kPi), 0.5f);
-    const float col = add_rn(-__fdiv_rn(alpha, mul_rn(2.0f, kPi)), 0.5f);
-    // img_coord_to_sample_coord: x = col*2-1, y = row*2-1; grid_sample (align_corners=False): ix = ((x+1)*W - 1)/2, border = clamp
-    const float gx = sub_rn(mul_rn(col, 2.0f), 1.0f), gy = sub_rn(mul_rn(row, 2.0f), 1.0f);
-    float ix = __fdiv_rn(sub_rn(mul_rn(add_rn(gx, 1.0f), (float)w), 1.0f), 2.0f);
-    float iy = __fdiv_rn(sub_rn(mul_rn(add_rn(gy, 1.0f), (float)h), 1.0f), 2.0f);
-    ix = fminf(fmaxf(ix, 0.0f), (float)(w - 1));
-    iy = fminf(fmaxf(iy, 0.0f), (float)(h - 1));
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = x0 + 1, y1 = y0 + 1;
-    const float wx1 = sub_rn(ix, fx0), wy1 = sub_rn(iy, fy0), wx0 = sub_rn(1.0f, wx1), wy0 = sub_rn(1.0f, wy1);
-    auto at = [&](int yy, int xx) { return (yy >= 0 && yy < h && xx >= 0 && xx < w) ? dmap[(int64_t)yy * w + xx] : 0.0f; };
-    // torch's bilinear accumulation order: nw, ne, sw, se
-    float proj = mul_rn(at(y0, x0), mul_rn(wx0, wy0));
-    proj = add_rn(proj, mul_rn(at(y0, x1), mul_rn(wx1, wy0)));
-    proj = add_rn(proj, mul_rn(at(y1, x0), mul_rn(wx0, wy1)));
-    proj = add_rn(proj, mul_rn(at(y1, x1), mul_rn(wx1, wy1)));
+    const PanoPixel p = pano_pixel(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], pf.rt, pf.t, h, w);
+    const float dist = p.dist, proj = pano_tap(dmap, h, w, p);
     if (mode == 0) {            // visibility: seen by this panorama if not behind what it stored (+ 1/256)
         const float v = (dist < add_rn(proj, eps)) ? 1.0f : 0.0f;
         mask[i] = fmaxf(mask[i], v);

@@ -757,6 +757,31 @@ def joint_tv(m, weight=1.0, grad=None, value=None, ws=None):
     return value, grad
 
 
+# ---- what the mesh units' bindings share ------------------------------------------------------------------------------------------------
+def _mesh_ws(query, sizes, ws, device):
+    """The int64 workspace of at least perf_*_workspace_bytes(*sizes) bytes on device: ws itself when it serves, else a new one."""
+    nbytes = getattr(_lib.load(), query)(*sizes)
+    if nbytes < 0:
+        _lib.check(-1, query)
+    if ws is None or ws.numel() * 8 < nbytes or ws.device != device:
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+    return ws
+
+
+def _mask_u8(mask):
+    """A bool or uint8 mask, contiguous, as the uint8 the library reads."""
+    m = mask.contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def _box3(who, lo, hi):
+    """The bounds of a box, three values each, as the float [3] arguments of the library."""
+    lo3, hi3 = [float(v) for v in lo], [float(v) for v in hi]
+    if len(lo3) != 3 or len(hi3) != 3:
+        raise _lib.PerfError(f'{who}: lo and hi hold three values each')
+    return (ctypes.c_float * 3)(*lo3), (ctypes.c_float * 3)(*hi3)
+
+
 # ---- surface nets on a dense lattice (include/perf_hip_mesh.h) -------------------------------------------------------------------------
 def _mesh_cells(who, field):
     if field.dim() != 3 or min(field.shape) < 2:
@@ -768,11 +793,7 @@ def mesh_count(field, thr, ws=None):
     """Classify the cells of a lattice of fp32 corner values [nx+1, ny+1, nz+1] against thr (perf_mesh_count) -> (counts, ws): counts =
     int64 [2] ON THE DEVICE (vertices, triangles), ws = the int64 workspace that mesh_write needs (pass one back in to reuse it)."""
     nx, ny, nz = _mesh_cells('mesh_count', field)
-    nbytes = _lib.load().perf_mesh_workspace_bytes(nx, ny, nz)
-    if nbytes < 0:
-        _lib.check(-1, 'perf_mesh_workspace_bytes')
-    if ws is None or ws.numel() * 8 < nbytes or ws.device != field.device:
-        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=field.device)
+    ws = _mesh_ws('perf_mesh_workspace_bytes', (nx, ny, nz), ws, field.device)
     counts = torch.empty(2, dtype=torch.int64, device=field.device)
     _call('perf_mesh_count', _p(_f32(field, 'field')), nx, ny, nz, float(thr), _p(ws), ws.numel() * 8, _p(counts), _stream())
     return counts, ws
@@ -783,12 +804,10 @@ def mesh_write(field, thr, lo, hi, ws, n_vertices, n_faces):
     same field and thr.  lo, hi: the box's bounds, three values each.  The two counts are what the caller read from mesh_count's totals:
     smaller ones are refused."""
     nx, ny, nz = _mesh_cells('mesh_write', field)
-    lo3, hi3 = [float(v) for v in lo], [float(v) for v in hi]
-    if len(lo3) != 3 or len(hi3) != 3:
-        raise _lib.PerfError('mesh_write: lo and hi hold three values each')
+    lo3, hi3 = _box3('mesh_write', lo, hi)
     vertices = torch.empty(int(n_vertices), 3, dtype=torch.float32, device=field.device)
     faces = torch.empty(int(n_faces), 3, dtype=torch.int32, device=field.device)
-    _call('perf_mesh_write', _p(_f32(field, 'field')), nx, ny, nz, float(thr), (ctypes.c_float * 3)(*lo3), (ctypes.c_float * 3)(*hi3), _p(ws),
+    _call('perf_mesh_write', _p(_f32(field, 'field')), nx, ny, nz, float(thr), lo3, hi3, _p(ws),
           ws.numel() * 8, _p(vertices) if n_vertices else None, int(n_vertices), _p(faces) if n_faces else None, int(n_faces), _stream())
     return vertices, faces
 
@@ -817,17 +836,7 @@ def _brick_occ(who, binaries):
     """binaries: bool or uint8 [..., R, R, R] -> (uint8 view, R)."""
     if binaries.dtype not in (torch.bool, torch.uint8) or binaries.dim() < 3 or len(set(binaries.shape[-3:])) != 1 or binaries.numel() != binaries.shape[-1] ** 3:
         raise _lib.PerfError(f'{who}: binaries must be bool or uint8 [R, R, R], got {binaries.dtype} {tuple(binaries.shape)}')
-    b = binaries.contiguous()
-    return (b.view(torch.uint8) if b.dtype == torch.bool else b), int(b.shape[-1])
-
-
-def _brick_ws(shape, n_bricks, ws, device):
-    nbytes = _lib.load().perf_brickmesh_workspace_bytes(*shape, int(n_bricks))
-    if nbytes < 0:
-        _lib.check(-1, 'perf_brickmesh_workspace_bytes')
-    if ws is None or ws.numel() * 8 < nbytes or ws.device != device:
-        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
-    return ws
+    return _mask_u8(binaries), int(binaries.shape[-1])
 
 
 def brickmesh_select(binaries, shape, ws=None):
@@ -836,7 +845,7 @@ def brickmesh_select(binaries, shape, ws=None):
     n = _brick_shape('brickmesh_select', shape)
     _brick_dev('brickmesh_select', binaries=binaries)
     occ, res = _brick_occ('brickmesh_select', binaries)
-    ws = _brick_ws(n, 0, ws, occ.device)
+    ws = _mesh_ws('perf_brickmesh_workspace_bytes', (*n, 0), ws, occ.device)
     table = torch.empty(tuple(v // 8 for v in n), dtype=torch.int32, device=occ.device)
     n_live = torch.empty(1, dtype=torch.int64, device=occ.device)
     _call('perf_brickmesh_select', _p(occ), res, *n, _p(table), _p(n_live), _p(ws), ws.numel() * 8, _stream())
@@ -881,7 +890,7 @@ def brickmesh_count(values, ids, table, shape, thr, fill, ws=None):
     """Classify the cells of the live bricks (perf_brickmesh_count) -> (counts, ws): counts = int64 [3] ON THE DEVICE (vertices, triangles,
     violations of the closure rule), ws = the int64 workspace brickmesh_write needs."""
     n, m = _brick_set('brickmesh_count', values, ids, table, shape)
-    ws = _brick_ws(n, m, ws, table.device)
+    ws = _mesh_ws('perf_brickmesh_workspace_bytes', (*n, m), ws, table.device)
     counts = torch.empty(3, dtype=torch.int64, device=table.device)
     _call('perf_brickmesh_count', _p(_f32(values, 'values')) if m else None, _p(_brick_i32(ids, 'ids')) if m else None, _p(_brick_i32(table, 'table')), m, *n, float(thr),
           float(fill), _p(ws), ws.numel() * 8, _p(counts), _stream())
@@ -892,15 +901,13 @@ def brickmesh_write(values, ids, table, shape, thr, fill, lo, hi, ws, n_vertices
     """The vertices [n_vertices, 3] fp32, faces [n_faces, 3] int32 and cells [n_vertices] int64 (each vertex's linear cell of the virtual
     lattice) of what brickmesh_count classified into ws (perf_brickmesh_write).  Counts below the counted totals are refused."""
     n, m = _brick_set('brickmesh_write', values, ids, table, shape)
-    lo3, hi3 = [float(v) for v in lo], [float(v) for v in hi]
-    if len(lo3) != 3 or len(hi3) != 3:
-        raise _lib.PerfError('brickmesh_write: lo and hi hold three values each')
+    lo3, hi3 = _box3('brickmesh_write', lo, hi)
     nv, nf = int(n_vertices), int(n_faces)
     vertices = torch.empty(nv, 3, dtype=torch.float32, device=table.device)
     faces = torch.empty(nf, 3, dtype=torch.int32, device=table.device)
     cells = torch.empty(nv, dtype=torch.int64, device=table.device)
     _call('perf_brickmesh_write', _p(_f32(values, 'values')) if m else None, _p(_brick_i32(ids, 'ids')) if m else None, _p(_brick_i32(table, 'table')), m, *n, float(thr),
-          float(fill), (ctypes.c_float * 3)(*lo3), (ctypes.c_float * 3)(*hi3), _p(ws), ws.numel() * 8, _p(vertices) if nv else None, nv, _p(faces) if nf else None, nf,
+          float(fill), lo3, hi3, _p(ws), ws.numel() * 8, _p(vertices) if nv else None, nv, _p(faces) if nf else None, nf,
           _p(cells) if nv else None, _stream())
     return vertices, faces, cells
 
@@ -915,15 +922,6 @@ def _cc_faces(who, faces, n_vertices):
     if n < 0 or n > _lib.MESHCC_MAX_VERTICES:
         raise _lib.PerfError(f'{who}: {n} vertices are outside 0 .. 2^30')
     return n, int(faces.shape[0])
-
-
-def _cc_ws(n_vertices, n_faces, ws, device):
-    nbytes = _lib.load().perf_meshcc_workspace_bytes(n_vertices, n_faces)
-    if nbytes < 0:
-        _lib.check(-1, 'perf_meshcc_workspace_bytes')
-    if ws is None or ws.numel() * 8 < nbytes or ws.device != device:
-        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
-    return ws
 
 
 def _cc_labels(who, vertex_component, n, device):
@@ -948,7 +946,7 @@ def meshcc_label(faces, n_vertices, ws=None):
     """Label the connected components of faces int32 [F, 3] over n_vertices vertices (perf_meshcc_label) -> (vertex_component int32 [V],
     counts, ws): counts = int64 [2] ON THE DEVICE (C, the first face with an index outside [0, V) or -1)."""
     n, f = _cc_faces('meshcc_label', faces, n_vertices)
-    ws = _cc_ws(n, f, ws, faces.device)
+    ws = _mesh_ws('perf_meshcc_workspace_bytes', (n, f), ws, faces.device)
     vertex_component = torch.empty(n, dtype=torch.int32, device=faces.device)
     counts = torch.empty(2, dtype=torch.int64, device=faces.device)
     _call('perf_meshcc_label', _p(faces) if f else None, f, n, _p(vertex_component) if n else None, _p(counts), _p(ws), ws.numel() * 8, _stream())
@@ -976,8 +974,7 @@ def _cc_keep(who, keep, device):
         raise _lib.PerfError(f'{who}: keep must be a CUDA tensor on the faces\' device')
     if keep.dtype not in (torch.bool, torch.uint8) or keep.dim() != 1:
         raise _lib.PerfError(f'{who}: keep must be bool or uint8 [C], got {keep.dtype} {tuple(keep.shape)}')
-    k = keep.contiguous()
-    return k.view(torch.uint8) if k.dtype == torch.bool else k
+    return _mask_u8(keep)
 
 
 def meshcc_filter_count(faces, vertex_component, keep, ws=None):
@@ -987,7 +984,7 @@ def meshcc_filter_count(faces, vertex_component, keep, ws=None):
     _, f = _cc_faces('meshcc_filter_count', faces, n)
     _cc_labels('meshcc_filter_count', vertex_component, n, faces.device)
     k = _cc_keep('meshcc_filter_count', keep, faces.device)
-    ws = _cc_ws(n, f, ws, faces.device)
+    ws = _mesh_ws('perf_meshcc_workspace_bytes', (n, f), ws, faces.device)
     counts = torch.empty(2, dtype=torch.int64, device=faces.device)
     _call('perf_meshcc_filter_count', _p(faces) if f else None, f, _p(vertex_component) if n else None, n, _p(k) if k.numel() else None, k.numel(), _p(ws),
           ws.numel() * 8, _p(counts), _stream())
@@ -1013,15 +1010,6 @@ def meshcc_filter_write(faces, vertex_component, keep, ws, n_vertices_kept, n_fa
 
 
 # ---- cull the faces no registered panorama saw (include/perf_hip_meshvis.h) ------------------------------------------------------------
-def _vis_ws(n_vertices, n_faces, ws, device):
-    nbytes = _lib.load().perf_meshvis_workspace_bytes(n_vertices, n_faces)
-    if nbytes < 0:
-        _lib.check(-1, 'perf_meshvis_workspace_bytes')
-    if ws is None or ws.numel() * 8 < nbytes or ws.device != device:
-        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
-    return ws
-
-
 def _vis_bits(who, name, bits, n, device):
     if not bits.is_cuda or bits.device != device:
         raise _lib.PerfError(f'{who}: {name} must be a CUDA tensor on the mesh\'s device')
@@ -1103,8 +1091,7 @@ def _vis_keep(who, face_keep, f, device):
         raise _lib.PerfError(f'{who}: face_keep must be a CUDA tensor on the faces\' device')
     if face_keep.dtype not in (torch.bool, torch.uint8) or tuple(face_keep.shape) != (f,):
         raise _lib.PerfError(f'{who}: face_keep must be bool or uint8 [{f}], got {face_keep.dtype} {tuple(face_keep.shape)}')
-    k = face_keep.contiguous()
-    return k.view(torch.uint8) if k.dtype == torch.bool else k
+    return _mask_u8(face_keep)
 
 
 def meshvis_filter_count(faces, n_vertices, face_keep, ws=None, counts=None):
@@ -1113,7 +1100,7 @@ def meshvis_filter_count(faces, n_vertices, face_keep, ws=None, counts=None):
     needs."""
     n, f = _cc_faces('meshvis_filter_count', faces, n_vertices)
     k = _vis_keep('meshvis_filter_count', face_keep, f, faces.device)
-    ws = _vis_ws(n, f, ws, faces.device)
+    ws = _mesh_ws('perf_meshvis_workspace_bytes', (n, f), ws, faces.device)
     if counts is None:
         counts = torch.empty(2, dtype=torch.int64, device=faces.device)
     _call('perf_meshvis_filter_count', _p(faces) if f else None, f, n, _p(k) if f else None, _p(ws), ws.numel() * 8, _p(counts), _stream())
@@ -1136,15 +1123,6 @@ def meshvis_filter_write(faces, n_vertices, face_keep, ws, n_vertices_kept, n_fa
 
 
 # ---- simplify a mesh by vertex clustering (include/perf_hip_meshsimp.h) -----------------------------------------------------------------
-def _simp_ws(n_vertices, n_faces, ws, device):
-    nbytes = _lib.load().perf_meshsimp_workspace_bytes(n_vertices, n_faces)
-    if nbytes < 0:
-        _lib.check(-1, 'perf_meshsimp_workspace_bytes')
-    if ws is None or ws.numel() * 8 < nbytes or ws.device != device:
-        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
-    return ws
-
-
 def _simp_vertices(who, vertices):
     if not torch.is_tensor(vertices) or not vertices.is_cuda:
         raise _lib.PerfError(f'{who}: vertices must be a CUDA tensor (there is no CPU path)')
@@ -1178,7 +1156,7 @@ def meshsimp_cluster(vertices, lo, h, n, n_faces=0, ws=None, counts=None):
     workspace is to serve as well (meshsimp_faces)."""
     vertices, nv = _simp_vertices('meshsimp_cluster', vertices)
     lo3, h, n3 = _simp_grid('meshsimp_cluster', lo, h, n)
-    ws = _simp_ws(nv, int(n_faces), ws, vertices.device)
+    ws = _mesh_ws('perf_meshsimp_workspace_bytes', (nv, int(n_faces)), ws, vertices.device)
     vertex_cluster = torch.empty(nv, dtype=torch.int32, device=vertices.device)
     if counts is None:
         counts = torch.empty(2, dtype=torch.int64, device=vertices.device)
@@ -1216,7 +1194,7 @@ def meshsimp_faces(faces, vertex_cluster, dedupe='oriented', ws=None, flag=None)
         raise _lib.PerfError(f"meshsimp_faces: dedupe is 'oriented', 'unoriented' or None, got {dedupe!r}")
     if f > _lib.MESHSIMP_MAX_FACES:
         raise _lib.PerfError(f'meshsimp_faces: {f} faces are more than 2^31 - 1')
-    ws = _simp_ws(nv, f, ws, faces.device)
+    ws = _mesh_ws('perf_meshsimp_workspace_bytes', (nv, f), ws, faces.device)
     remapped = torch.empty(f, 3, dtype=torch.int32, device=faces.device)
     keep = torch.empty(f, dtype=torch.uint8, device=faces.device)
     if flag is None:

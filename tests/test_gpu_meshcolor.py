@@ -244,6 +244,67 @@ def test_a_pool_with_masks_is_accepted():
     assert torch.equal(a.colors, b.colors) and torch.equal(a.weight, b.weight) and torch.equal(a.used, b.used) and torch.equal(a.best_view, b.best_view)
 
 
+# ---- the colouring and the cull run one look-up ---------------------------------------------------------------------------------------------
+def _lookup_views(k, tiny, rng):
+    """k views with centres in [-0.5, 0.5]^3 and 8 x 16 maps of distances that split the vertices (view `tiny`: 1 x 1).  View 0 is not
+    rotated, so a vertex straight above it has d_z = 1 and one on its seam d_y = 0 exactly; the others have random rotations."""
+    poses, dmaps, cmaps = [], [], []
+    for i in range(k):
+        q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+        q = q * np.sign(np.diag(r))
+        if np.linalg.det(q) < 0:
+            q[:, 0] = -q[:, 0]
+        if i == 0:
+            q = np.eye(3)
+        pose = np.eye(4, dtype=np.float32)
+        pose[:3, :3], pose[:3, 3] = q, rng.uniform(-0.5, 0.5, size=3)
+        h, w = (1, 1) if i == tiny else (8, 16)
+        poses.append(pose)
+        dmaps.append(rng.uniform(0.2, 2.0, size=(h, w)).astype(np.float32))
+        cmaps.append(rng.uniform(0.0, 1.0, size=(h, w, 3)).astype(np.float32))
+    return poses, dmaps, cmaps
+
+
+def _lookup_vertices(n, poses, rng):
+    """For each of the first four views: straight above and below its centre (asinf(+-1)) and on its seam (atan2f at +-pi, and a hair to
+    either side of it); then random vertices in the box [-1.5, 1.5]^3 around the centres."""
+    special = []
+    for pose in poses[:4]:
+        rot, t = pose[:3, :3].astype(np.float64), pose[:3, 3].astype(np.float64)
+        for local in ((0, 0, 0.75), (0, 0, -0.75), (-0.6, 0.0, 0), (-0.6, 1e-6, 0), (-0.6, -1e-6, 0)):
+            special.append(t + rot @ np.array(local))
+    p = np.concatenate([np.array(special).reshape(-1, 3), rng.uniform(-1.5, 1.5, size=(n, 3))])[:n]
+    return np.ascontiguousarray(p, dtype=np.float32)
+
+
+@pytest.mark.parametrize('n_views,tiny', [(1, None), (1, 0), (64, 5)])
+@pytest.mark.parametrize('n', [257, 1])
+def test_used_bits_without_facing_are_the_culls_visible_bits(n, n_views, tiny):
+    """One full workgroup and a one-thread tail (257) or one vertex; one view or all 64 (bit 63, the whole LDS descriptor array); a 1 x 1
+    map (w - 1 = 0: both clamps coincide) among 8 x 16 ones.  No vertex lies at a centre: there dist == 0, which the colouring, unlike
+    the cull, refuses by rule.  Everywhere else the two kernels run the same look-up, so the words are equal."""
+    from perf_amd import ops
+    rng = np.random.default_rng(1000 * n + 10 * n_views + (tiny or 0))
+    poses, dmaps, cmaps = _lookup_views(n_views, tiny, rng)
+    p = _lookup_vertices(n, poses, rng)
+    centres = np.array([pose[:3, 3] for pose in poses])
+    assert (p[:, None, :] != centres[None]).any(axis=2).all()
+    vertices = torch.from_numpy(p).cuda()
+    views, _, sizes, held = ops.meshvis_views(poses, [torch.from_numpy(m).cuda() for m in dmaps])
+    pointers, held_colours = ops.meshcolor_maps([torch.from_numpy(m).cuda() for m in cmaps], sizes)
+    tol = 1 / 64
+    visible, _ = ops.meshvis_vertex_bits(vertices, views, sizes, tol, 0.0)
+    _, _, used, _ = ops.meshcolor_blend(vertices, None, views, sizes, pointers, tol, facing=False)
+    assert used.dtype == visible.dtype == torch.int64 and tuple(used.shape) == tuple(visible.shape) == (n,)
+    assert torch.equal(used, visible)
+    if n == 257:          # the comparison is not of empty words with empty words: bits are set and bits are clear
+        words = _words(visible)
+        low = np.uint64((1 << n_views) - 1) if n_views < 64 else ~np.uint64(0)
+        assert words.any() and (~words & low).any()
+        if n_views == 64:
+            assert (words >> np.uint64(63)).any()
+
+
 # ---- identities ---------------------------------------------------------------------------------------------------------------------------
 def _tunnel(color=None):
     from perf_amd.mesh import cull_unseen

@@ -117,8 +117,12 @@ def test_the_unit_is_built_with_its_own_header():
     users = [s for s in build.SOURCES if any(p.endswith(os.sep + 'perf_hip_meshcolor.h') for p in build._includes(os.path.join(build.CSRC, s)))]
     assert users == ['meshcolor.hip'], users          # the units that include the header, by their #include lines, are the ones rebuilt for it
     unit = open(os.path.join(ROOT, 'perf_amd', 'csrc', 'meshcolor.hip')).read()
-    assert '#include "../../include/perf_hip_meshcolor.h"' in unit and 'col_lookup' in unit
-    assert 'vis_lookup(float x' in open(os.path.join(ROOT, 'perf_amd', 'csrc', 'meshvis.hip')).read()          # restated, not moved
+    assert '#include "../../include/perf_hip_meshcolor.h"' in unit
+    # the panorama look-up is stated once: the three units that run it include the header, and no other file of csrc holds its asinf
+    for name in ('visibility.hip', 'meshvis.hip', 'meshcolor.hip'):
+        assert any(p.endswith(os.sep + 'pano_lookup_device.hpp') for p in build._includes(os.path.join(build.CSRC, name))), name
+    holders = sorted(f for f in os.listdir(build.CSRC) if 'asinf(' in open(os.path.join(build.CSRC, f)).read())
+    assert holders == ['pano_lookup_device.hpp'], holders
     assert unit.count('#pragma clang fp contract(off)') >= 3 and 'atomicAdd(acc' in unit
     assert not re.search(r'atomicAdd\s*\(\s*\(?\s*(float|double)', unit)          # no floating-point atomics
 

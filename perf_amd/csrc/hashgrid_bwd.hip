@@ -17,8 +17,8 @@ namespace perf {
 // keeps it in LDS (the multi-tile levels' 192 + 12 tiles plus the replicated coarse ones <= 256 CUs: the whole
 // table is resident in the chip's aggregate LDS).  Every owner walks all samples of its level and applies only the
 // corner updates that fall in its tile with LDS atomics -- multi-tile levels through a tile code per sample that a
-// pre-pass computes once for all owners (hashed levels of up to 16 tiles: a 16-bit tile mask, bwd_stream_masks; others:
-// 4 bytes, bwd_stream_codes), single-tile levels from positions (bwd_stream);
+// pre-pass computes once for all owners (hashed levels of up to 16 tiles: one bit row per tile, bwd_stream_bits; others:
+// 4 bytes per sample, bwd_stream_codes), single-tile levels from positions (bwd_stream);
 // at the end the tile is written back with plain coalesced stores.  No global atomics, no zero-fill pass, every
 // table entry written exactly once.
 constexpr int kTileEntries = 16384;
@@ -58,7 +58,7 @@ struct TileParams {
     uint32_t work[kMaxWork];
 };
 
-// per-wave match queue (entries).  An iteration of the code / mask loops starts with fewer than 128 entries (its burst loop ran
+// per-wave match queue (entries).  (The bit-row owners state their own count beside bwd_stream_bits.)  An iteration of the code loop starts with fewer than 128 entries (its burst loop ran
 // until then; the first starts empty), its four enqueue rounds add at most 4 x 64 (one per lane and sample slot: < 384), the apply's
 // re-queue at most 64 (< 448); the pop that follows takes 64 of them when there are that many, and every further burst round pops as
 // many as its apply re-queues at most.
@@ -67,7 +67,7 @@ constexpr int kQueueCap = 448;
 // multiplier, which is exact while an index of the level fits 24 bits.
 constexpr int kMaxCodedHashedTiles = 255, kMaxCodedDenseTiles = 64;
 static_assert((int64_t)(kMaxCodedHashedTiles + 1) * 16384 <= ((int64_t)1 << 24) && (int64_t)kMaxCodedDenseTiles * 16384 <= ((int64_t)1 << 24),
-              "coded levels: indices must fit 24 bits (bwd_stream_masks / bwd_stream_codes multiply with v_mul_u32_u24)");
+              "coded levels: indices must fit 24 bits (bwd_stream_bits / bwd_stream_codes multiply with v_mul_u32_u24)");
 constexpr int64_t kMaxCodedSamples = (int64_t)1 << 28;
 
 constexpr int kBitmapMinDenseTiles = 32;
@@ -135,9 +135,12 @@ static void plan_tiles(const GridParams& gp, bool fixed, TileParams* tp, int* n_
                 nb += nt * (want - r);
                 tp->replicas_of[l] = want;
             }
-        // ---- and then to the dense levels of 2..4 tiles.  With the hashed owners on 16-bit tile masks (bwd_stream_masks: 283-306 us per
-        // workgroup, were 297-335) the 4 tiles x 3 replicas of level 2 of L16 / T18 ended the launch at 342 us; a fourth replica brings
-        // them to 268 and the launch from 331 to 316 us on one box (profiles/bwd_tile_masks.json; 248 workgroups = kCus).  (Round 6
+        // ---- and then to the dense levels of 2..4 tiles.  With the hashed owners on 16-bit tile masks (283-306 us per workgroup, were
+        // 297-335) the 4 tiles x 3 replicas of level 2 of L16 / T18 ended the launch at 342 us; a fourth replica brings them to 268 and
+        // the launch from 331 to 316 us on one box (profiles/bwd_tile_masks.json; 248 workgroups = kCus).  With the hashed owners on bit
+        // rows (bwd_stream_bits) every kind of workgroup of the bench step takes 238-250 us (profiles/bwd_bit_rows.json: hashed 238-250,
+        // level 2's 4 x 4 250, the single-tile levels' 8 replicas 245, level 3's 8 x 3 238): the launch ends with all of them at once,
+        // there is no CU left (kCus), and no replica count is changed.  (Round 6
         // measured the same replica as a LOSS, 357.0 against 352.5 us: the hashed owners ended the launch then, and four more neighbours
         // cost them more than level 2 gained.)  Only while its slab fits the room the fp32 plan's slabs take anyway (16 / tiles replicas):
         // the workspace a grid asks for stays what it was.
@@ -375,14 +378,26 @@ constexpr int kCodeSamplesPerBlock = 256;
 //    sample order loses the 2-3 queued samples per 128-byte line that neighbouring lanes share, and the sort pass took
 //    0.65 ms;
 //  * one bit per (tile, sample) instead of the codes, expanded to queue entries with a wave scan: owners 0.325 ->
-//    0.277 ms per workgroup, but the kernel ends with its burstiest level (0.31 ms) and the pre-pass grew by 0.085 ms.
+//    0.277 ms per workgroup, but the kernel ends with its burstiest level (0.31 ms) and the pre-pass grew by 0.085 ms -- four LDS
+//    atomics per sample and level into a staged row.  Levels of at most 16 tiles have their bit rows now, from a transposition of
+//    the masks in registers that costs the pre-pass 7 us: below.
 //  What an owner costs is the drain: gather 20 B per queued sample, ~95 instructions and two 64-bit LDS atomics per
 //  combination; tests, gathers and LDS are within 2x of each other, so removing one of them moves little.)
 
-// Hashed levels of at most 16 tiles (log2_hashmap_size <= 18) keep a 16-bit mask per sample instead of the four bytes: bit t is set
-// when any of the sample's four (y,z) combinations names tile t.  The row lives in the first half of the level's code slot
-// (stride n_pad elements of two bytes); its owners are bwd_stream_masks.
+// Hashed levels of at most 16 tiles (log2_hashmap_size <= 18) keep one BIT ROW per tile instead of the four bytes per sample: row t
+// has the bit of sample i set when any of the sample's four (y,z) combinations names tile t, so that an owner reads n / 8 bytes and
+// pays per hit (bwd_stream_bits).  The pre-pass forms a 16-bit mask of the named tiles per sample in registers and transposes the
+// masks of a DPP row of 16 lanes (64 samples) into 64 bits per tile (store_bit_rows): a workgroup writes a piece of 32 bytes per row,
+// whole, so the rows need no zero fill.  The rows live in the level's code slot, row t at t * bit_row_words(n) words: 16 pieces of
+// 32 bytes per block of 256 samples are 2 bytes per sample, what the masks took, but the last block's pieces are written whole -- up
+// to 512 bytes of the slot's second half (a slot is 4 n_pad bytes and holds 512 * ceil(n / 256) for any n >= 256; below that a call's
+// bit-row levels take the position-streaming owners, perf_internal_hashgrid_bwd_riders).
+// Bit order, stated here once (bit_row_first_sample): a row is an array of 16-bit halfwords, halfword h holds the samples
+// 64 * (h / 4) + (h % 4) + 4 * b in bit b = 0..15 -- slot k = h % 4 of the 16 lanes of DPP row h / 4 % 4 of the block's wave.  A
+// halfword's hits stay inside a window of 64 samples, which keeps the gathers' line sharing.
 constexpr int kMaskTiles = 16;
+__device__ __forceinline__ uint32_t bit_row_first_sample(uint32_t h) { return ((h >> 2) << 6) | (h & 3u); }      // bit b: this + 4 b
+__host__ __device__ inline int64_t bit_row_words(int64_t n) { return (n + kCodeSamplesPerBlock - 1) / kCodeSamplesPerBlock * (kCodeSamplesPerBlock / 32); }
 constexpr uint32_t kCodeMasks = 0u, kCodeBytes = 1u, kCodeDense = 2u, kCodeDenseWide = 3u;
 constexpr uint32_t kPackedMaxRes = 500;     // kCodeDense: res <= 500, so that no corner index of cells below 16383 wraps (16383 * (1 + 500 + 500^2) + 500 + 500^2 < 2^32)
 
@@ -460,12 +475,13 @@ __device__ __forceinline__ uint32_t dense_code_packed(const CodeLevel& d, float 
     return (chunk & d.tmask4) | next;
 }
 
-// One coded level of a lane's four consecutive samples (cnt of them live): the codes, stored with one 8-byte (masks) or 16-byte store
-// (cnt < 4: element by element); returns the level's escape bit.  The kind is branched on once, around the four samples.
+// One coded level of a lane's four consecutive samples (cnt >= 1 of them live): the codes, stored with one 16-byte store (cnt < 4:
+// element by element) -- a bit-row level's four 16-bit masks are handed back in m01 / m23 instead (samples 0, 1 and 2, 3; zero for a
+// sample past cnt), for store_bit_rows --; returns the level's escape bit.  The kind is branched on once, around the four samples.
 // INSIDE: every grid position of the four samples is in [0, 16383) (or NaN) at this level.
 template <bool INSIDE>
 __device__ __forceinline__ uint32_t code_level(const CodeLevel& d, const float (&p)[12], int cnt, int64_t i0, uint32_t* __restrict__ codes,
-                                               const float2* __restrict__ dfeat, int64_t n) {
+                                               const float2* __restrict__ dfeat, int64_t n, uint32_t& m01, uint32_t& m23) {
     const uint32_t kind = d.kind_level & 0xffu;
     uint32_t code[4];
     if (kind == kCodeMasks) {           // 16-bit masks of the tiles the four combinations name
@@ -473,16 +489,10 @@ __device__ __forceinline__ uint32_t code_level(const CodeLevel& d, const float (
         for (int k = 0; k < 4; ++k) {
             uint32_t t[4];
             hashed_tiles<INSIDE>(d, p[3 * k + 1], p[3 * k + 2], t);
-            code[k] = (1u << t[0]) | (1u << t[1]) | (1u << t[2]) | (1u << t[3]);
+            code[k] = k < cnt ? (1u << t[0]) | (1u << t[1]) | (1u << t[2]) | (1u << t[3]) : 0u;
         }
-        uint16_t* row16 = reinterpret_cast<uint16_t*>(codes + d.row) + i0;
-        if (cnt == 4) {
-            *reinterpret_cast<uint2*>(row16) = make_uint2(code[0] | (code[1] << 16), code[2] | (code[3] << 16));
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < cnt) row16[k] = (uint16_t)code[k];
-        }
+        m01 = code[0] | (code[1] << 16);
+        m23 = code[2] | (code[3] << 16);
     } else {                            // one byte per combination
         if (kind == kCodeBytes) {
 #pragma unroll
@@ -527,8 +537,47 @@ __device__ __forceinline__ uint32_t code_level(const CodeLevel& d, const float (
     return esc;
 }
 
+// The bit rows of one level from the masks of a wave's 256 samples (m01 / m23 of code_level; zero on lanes without live samples).  Per
+// DPP row of 16 lanes and per sample slot the masks are a 16 x 16 bit matrix, lane by tile, two slots to a register; four butterfly
+// stages (partner = lane ^ 8, 4, 2, 1: the halves of a block of bits change places between the two lanes) transpose it, so that lane t
+// of the row ends with the bits of tile t: its 16 lanes' slot k in halfword k -- the bit order of bit_row_first_sample --, 8 bytes
+// of the row's piece.  A stage is a lane exchange, a rotate and a bit select on each register: the rotate stands for the
+// shift (left on the lower lane of a pair, right on the upper), as the bits it wraps around fall outside the half that is taken.
+// Must be called by the whole wave.
+template <int S>
+__device__ __forceinline__ uint32_t bit_row_partner(uint32_t v) {
+    if (S == 8) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, true);        // row_ror:8
+    if (S == 4) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x101f);                           // lane ^ 4 (no LDS is touched)
+    if (S == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4e, 0xf, 0xf, true);         // quad_perm:[2,3,0,1]
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xb1, 0xf, 0xf, true);                     // quad_perm:[1,0,3,2]
+}
+template <int S>
+__device__ __forceinline__ uint32_t bit_row_stage(uint32_t v, uint32_t lane) {
+    constexpr uint32_t kLow = S == 8 ? 0x00ff00ffu : (S == 4 ? 0x0f0f0f0fu : (S == 2 ? 0x33333333u : 0x55555555u));   // bits whose place has S clear
+    const bool upper = (lane & (uint32_t)S) != 0u;
+    const uint32_t keep = upper ? ~kLow : kLow;
+    const uint32_t other = bit_row_partner<S>(v);
+    const uint32_t moved = __builtin_amdgcn_alignbit(other, other, upper ? (uint32_t)S : 32u - (uint32_t)S);
+    return (v & keep) | (moved & ~keep);
+}
+__device__ __forceinline__ void store_bit_rows(const CodeLevel& d, uint32_t m01, uint32_t m23, unsigned bx, uint32_t lane,
+                                               uint32_t* __restrict__ codes, int64_t row_words) {
+    m01 = bit_row_stage<8>(m01, lane); m23 = bit_row_stage<8>(m23, lane);
+    m01 = bit_row_stage<4>(m01, lane); m23 = bit_row_stage<4>(m23, lane);
+    m01 = bit_row_stage<2>(m01, lane); m23 = bit_row_stage<2>(m23, lane);
+    m01 = bit_row_stage<1>(m01, lane); m23 = bit_row_stage<1>(m23, lane);
+    // lane 16 r + t holds piece r of row t; lane 4 t + r stores it, so that the four lanes next to each other write a row's 32 bytes
+    const uint32_t from = (((lane & 3u) << 4) | (lane >> 2)) << 2;
+    m01 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)from, (int)m01);
+    m23 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)from, (int)m23);
+    const uint32_t t = lane >> 2;       // (rows above the level's tile count stay unwritten: nobody reads them)
+    if (t <= d.tmask)
+        *reinterpret_cast<uint2*>(codes + d.row + (int64_t)t * row_words + (int64_t)bx * (kCodeSamplesPerBlock / 32) + 2u * (lane & 3u)) = make_uint2(m01, m23);
+}
+
 // The tile codes of every coded level.  One workgroup = the 256 samples of one escape word: each of its four waves holds all 256 (four
-// consecutive samples per lane: 48 bytes of positions in three 16-byte loads, one 16- or 8-byte store per level) and computes every
+// consecutive samples per lane: 48 bytes of positions in three 16-byte loads, one 16- or 8-byte store per level -- a bit-row level's
+// after the wave has transposed its masks, store_bit_rows, outside the branches that lanes take apart --) and computes every
 // fourth level, so that 1 M samples give a SIMD sixteen short waves, and the 16-35 k live rows of the reference-faithful training
 // step (1 M-row capacity; the count is on the device) still some hundred waves; workgroups past the live count only write their
 // (zero) escape word.  What bounds the kernel is its vector arithmetic (profiles/tile_codes_prepass.json), so the work per
@@ -557,10 +606,12 @@ __global__ __launch_bounds__(64 * kCodeWaves) void tile_codes4_kernel(CodePlan c
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t i0 = (int64_t)bx * kCodeSamplesPerBlock + 4 * lane;
     uint32_t esc = 0u;                  // bit l: level l must take the generic owners
-    if (i0 < n_live) {
-        const int cnt = (n_live - i0) < 4 ? (int)(n_live - i0) : 4;
-        float p[12];
-        if (cnt == 4 && (reinterpret_cast<uintptr_t>(x01) & 15) == 0) {
+    if ((int64_t)bx * kCodeSamplesPerBlock < n_live) {      // (the whole workgroup; lanes past the live count carry empty masks through the levels)
+        const int cnt = i0 >= n_live ? 0 : ((n_live - i0) < 4 ? (int)(n_live - i0) : 4);
+        const int64_t row_words = bit_row_words(n);
+        float p[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (cnt == 0) {
+        } else if (cnt == 4 && (reinterpret_cast<uintptr_t>(x01) & 15) == 0) {
             const float4 a = reinterpret_cast<const float4*>(x01 + 3 * i0)[0], b = reinterpret_cast<const float4*>(x01 + 3 * i0)[1],
                          c = reinterpret_cast<const float4*>(x01 + 3 * i0)[2];
             p[0] = a.x; p[1] = a.y; p[2] = a.z; p[3] = a.w; p[4] = b.x; p[5] = b.y; p[6] = b.z; p[7] = b.w;
@@ -579,10 +630,13 @@ __global__ __launch_bounds__(64 * kCodeWaves) void tile_codes4_kernel(CodePlan c
         for (int j = wave; j < cp.n_coded; j += kCodeWaves) {
             const CodeLevel d = next;
             next = cp.lv[j + kCodeWaves];
-            if (grid_pos(lo, d.scale) >= 0.f && grid_pos(hi, d.scale) < (float)(kTileEntries - 1))
-                esc |= code_level<true>(d, p, cnt, i0, codes, dfeat, n);
+            uint32_t m01 = 0u, m23 = 0u;
+            if (cnt == 0) {
+            } else if (grid_pos(lo, d.scale) >= 0.f && grid_pos(hi, d.scale) < (float)(kTileEntries - 1))
+                esc |= code_level<true>(d, p, cnt, i0, codes, dfeat, n, m01, m23);
             else
-                esc |= code_level<false>(d, p, cnt, i0, codes, dfeat, n);
+                esc |= code_level<false>(d, p, cnt, i0, codes, dfeat, n, m01, m23);
+            if ((d.kind_level & 0xffu) == kCodeMasks) store_bit_rows(d, m01, m23, bx, (uint32_t)lane, codes, row_words);
         }
     }
     if (esc) atomicOr(&esc_block, esc);
@@ -855,131 +909,6 @@ __device__ __forceinline__ void bwd_stream_codes(const BwdCtx& cx, float* lds_ti
 #undef PERF_WAIT_BATCH
 }
 
-// ---- hashed owners of a mask level (at most 16 tiles: kMaskTiles) ------------------------------------------------
-// The same loop over a 16-bit mask per sample: the test of a sample is ONE AND against this owner's bit and the compare that is
-// the ballot (the byte codes take five instructions for the zero-byte marks and a dot product on the lanes that hit), and a lane's four
-// samples arrive in one 8-byte load.  What the mask does not say is WHICH of the sample's four (y,z) combinations name the tile: a
-// fresh queue entry carries cm = 0 and the apply works the combinations out from the (y,z) it gathered anyway, with the pre-pass's own
-// four tile expressions (hashed_tiles); re-queued entries carry their remaining combinations as before.
-// In flight at the head of an iteration, oldest first: [masks: 1][gather batch: 2], so "vmcnt(2)" = the masks have landed; every pop
-// issues 2 loads and every iteration 1, whatever the queue holds.  The queue bound is bwd_stream_codes' (kQueueCap).
-// (A SECOND gather batch in flight per wave -- two register sets taking turns, the main loop unrolled by two, bursts drained in pairs,
-//  the batch popped in one iteration applied in the one after the next -- was built and measured beside this loop: per-workgroup times
-//  of the hashed owners equal within 1 us, the step 0.846 ms either way; DESIGN.md 5.1, profiles/bwd_tile_masks.json.  Not kept.)
-struct GatherBatch {
-    f32x3 ld_p; f32x2 ld_g;             // written by loads in flight: only ever read through PERF_WAIT_APPLY
-    uint32_t cm, i;                     // combinations (0: not known yet) and sample index of the lane's entry
-    bool live;                          // this lane holds an entry
-};
-
-template <bool FIXED>
-__device__ __forceinline__ void bwd_stream_masks(const BwdCtx& cx, float* lds_tile, uint32_t* queue,
-                                                 const uint32_t* __restrict__ masks_l, const float* __restrict__ x01,
-                                                 const float2* __restrict__ g_l, int64_t n, int rep, int R) {
-    __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0), see bwd_stream_codes
-    constexpr int kPer = 4;                             // samples of a lane per iteration (= per mask load)
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t qn = 0;                                    // wave-uniform queue fill
-    const int64_t n_full = n / kPer;
-    const int64_t g_lo = n_full * rep / R, g_hi = n_full * (rep + 1) / R;       // this replica's groups of kPer samples
-    u32x2 ld_m = {0u, 0u};                              // written by the load in flight
-    GatherBatch A = {{0.f, 0.f, 0.f}, {0.f, 0.f}, 0u, 0u, false};               // the batch in flight
-    const uint32_t bit2 = (1u << cx.t) * 0x00010001u;   // this owner's bit in both halves of a word of two masks
-    const uint32_t t_hi = cx.t * (uint32_t)kTileEntries, m_hi = cx.mask & ~(uint32_t)(kTileEntries - 1);
-    // (fresh entries: index << 4, the combinations not known yet; re-queued ones carry theirs)
-    auto requeue = [&](uint32_t cm, uint32_t i) __attribute__((always_inline)) { enqueue1(queue, qn, cm != 0u, (i << 4) | cm); };
-    auto load_masks = [&](uint32_t grp) __attribute__((always_inline)) {               // 1 load
-        const uint32_t off = (grp < (uint32_t)g_hi ? grp : (uint32_t)g_hi - 1u) * 8u;
-        asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(ld_m) : "v"(off), "s"(masks_l) : "memory");
-    };
-    auto pop_and_gather = [&]() __attribute__((always_inline)) {                       // up to 64 queued samples: 2 loads
-        // (readfirstlane: scalar min and subtract -- left to itself the compiler forms qn - take as a saturating VECTOR subtract)
-        const uint32_t take = (uint32_t)__builtin_amdgcn_readfirstlane((int)(qn < 64u ? qn : 64u));
-        __builtin_amdgcn_wave_barrier();
-        uint32_t e = 0;
-        if (lane < take) e = (queue + (qn - take))[lane];
-        __builtin_amdgcn_wave_barrier();
-        qn -= take;
-        A.live = lane < take;
-        A.cm = e & 15u;
-        A.i = e >> 4;
-        uint32_t ox, og;
-        sample_offsets(A.i, ox, og);
-        asm volatile("global_load_dwordx3 %0, %2, %3\n\tglobal_load_dwordx2 %1, %4, %5"
-                     : "=&v"(A.ld_p), "=&v"(A.ld_g) : "v"(ox), "s"(x01), "v"(og), "s"(g_l) : "memory");
-    };
-    // Every lane applies ONE combination; the samples that name this tile with two or more go back into the queue with the rest.
-    auto apply_batch = [&](float bx, f32x2 byz, f32x2 bg) __attribute__((always_inline)) {
-        const float px = grid_pos(bx, cx.scale), py = grid_pos_alone(byz.x, cx.scale), pz = grid_pos_alone(byz.y, cx.scale);
-        const float flx = floorf(px), fly = floorf(py), flz = floorf(pz);
-        const uint32_t gx = (uint32_t)(int32_t)flx;
-        // (a mask level has at most 2^18 entries: only the low 24 bits of the (y,z) terms count, and those are the low 24 bits of the
-        //  full-rate 24-bit product of the factors' low 24 bits, for any cell -- the pre-pass's own expressions, hashed_tiles)
-        const uint32_t ay0 = __umul24((uint32_t)(int32_t)fly, kPrimeY & 0xffffffu), az0 = __umul24((uint32_t)(int32_t)flz, kPrimeZ & 0xffffffu);
-        const uint32_t ay1 = ay0 + kPrimeY, az1 = az0 + kPrimeZ;
-        // (tile == t, with the tile's bits of the index compared in place)
-        const uint32_t derived = ((((ay0 ^ az0) & m_hi) == t_hi) ? 1u : 0u) | ((((ay1 ^ az0) & m_hi) == t_hi) ? 2u : 0u) |
-                                 ((((ay0 ^ az1) & m_hi) == t_hi) ? 4u : 0u) | ((((ay1 ^ az1) & m_hi) == t_hi) ? 8u : 0u);
-        uint32_t cm = A.cm ? A.cm : derived;
-        if (!A.live || gx >= (uint32_t)(kTileEntries - 1)) cm = 0u;     // (idle lane; or zero gradient, see tile_codes4_kernel)
-        const uint32_t rest = cm & (cm - 1u);
-        cm &= 0u - cm;
-        if (cm) apply_pair_one<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, sub_alone(py, fly), sub_alone(pz, flz), ay0, az0, cm);
-        requeue(rest, A.i);
-    };
-    // wait until at most `younger` loads are in flight, then apply the batch from the registers it landed in (they are in-out operands
-    // of the wait: the compiler must not move a read of them above it, and no copy is spent -- the batch is dead before the next pop
-    // issues loads into them).
-    // (The batch must keep its registers from pop to apply on every path: a compiler-made copy of a register that a load in flight
-    //  is still to write reads it too early.  After a change to this loop, compare the registers of the loads with those of the copies
-    //  in the assembly.)
-#define PERF_WAIT_APPLY(younger)                                                                                        \
-    {                                                                                                                   \
-        asm volatile("s_waitcnt vmcnt(" #younger ")" : "+v"(A.ld_p), "+v"(A.ld_g) : : "memory");                        \
-        apply_batch(A.ld_p.x, f32x2{A.ld_p.y, A.ld_p.z}, A.ld_g);                                                       \
-    }
-    if (g_hi > g_lo) {
-        // (groups and sample indices fit 32 bits: kMaxCodedSamples; the trip count is wave-uniform and kept on the scalar unit)
-        const uint32_t g_end = (uint32_t)g_hi;
-        uint32_t grp = (uint32_t)g_lo + threadIdx.x;
-        load_masks(grp);
-        pop_and_gather();               // empty queue: dummy gather, keeps the in-flight count of the loop static
-        for (uint32_t base = (uint32_t)g_lo + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u)); base < g_end; base += kBwdThreads) {
-            u32x2 m;
-            asm volatile("s_waitcnt vmcnt(2)\n\tv_mov_b64 %0, %1" : "=&v"(m) : "v"(ld_m) : "memory");
-            const uint32_t g0 = grp;
-            const uint32_t vb = g0 < g_end ? bit2 : 0u;     // a lane without a group of its own in the last iteration hits nothing
-            grp += kBwdThreads;
-            load_masks(grp);
-            const uint32_t b_lo = vb & 0xffffu, b_hi = vb & 0xffff0000u, e0 = g0 << 6;
-            enqueue1(queue, qn, (m.x & b_lo) != 0u, e0);
-            enqueue1(queue, qn, (m.x & b_hi) != 0u, e0 + 16u);
-            enqueue1(queue, qn, (m.y & b_lo) != 0u, e0 + 32u);
-            enqueue1(queue, qn, (m.y & b_hi) != 0u, e0 + 48u);
-            PERF_WAIT_APPLY(1)              // all but the mask load
-            pop_and_gather();
-            while (qn >= 128u) {            // bursts (ray-coherent samples at coarse hashed levels)
-                PERF_WAIT_APPLY(0)
-                pop_and_gather();
-            }
-        }
-    }
-    if (threadIdx.x < 64 && rep == 0) {                 // ragged tail (n % kPer samples)
-        const int64_t i = n_full * kPer + lane;
-        bool hit = false;
-        if (i < n) hit = ((reinterpret_cast<const uint16_t*>(masks_l)[i] >> cx.t) & 1u) != 0u;
-        enqueue1(queue, qn, hit, (uint32_t)i << 4);
-    }
-    for (;;) {
-        PERF_WAIT_APPLY(0)
-        A.live = false;
-        if (qn == 0u) break;
-        pop_and_gather();
-    }
-    asm volatile("" : : "v"(ld_m));                     // (the last mask load landed with a vmcnt(0) above)
-#undef PERF_WAIT_APPLY
-}
-
 // inclusive prefix sum over the 64 lanes of a wave (DPP: shifts inside rows of 16, then row broadcasts)
 __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);      // row_shr:1
@@ -989,6 +918,155 @@ __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);     // row_bcast:15 -> rows 1, 3
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);     // row_bcast:31 -> rows 2, 3
     return v;
+}
+
+// ---- hashed owners of a bit-row level (at most 16 tiles: kMaskTiles) ----------------------------------------------
+// An owner reads ITS row only -- one bit per sample, n / 8 bytes -- and pays per hit instead of per sample: a lane takes one halfword
+// of the row per round (16 samples; the wave 1,024: kBitRoundSamples), the wave places its hits with one popcount and one scan, and
+// every lane appends its set bits to the wave's queue (about 225 of 1,024 at 16 tiles: 8-9 trips of the longest lane).  A fresh queue
+// entry carries cm = 0, as the row does not say WHICH of the sample's four (y,z) combinations name the tile: the apply works them out
+// from the (y,z) it gathered anyway, with the pre-pass's own four tile expressions (hashed_tiles); re-queued entries carry their
+// remaining combinations.  The queue is drained 64 entries at a time while it holds that many, so the applies run at full lanes.
+// TWO gather batches take turns (PERF_BITS_HALF): the queue is drained in bursts of three or four pops between two rounds, and with
+// one batch every pop but the first of a burst was waited for right where it was issued.  The wait counts are static: a half waits
+// until its own pop's 2 loads are the only ones in flight, a round is taken behind "vmcnt(0)", and the row's next halfword is
+// requested at the end of the half that took a round.
+// Queue bound (kQueueCap): the queue is fed when it holds fewer than 64 entries, with one batch waiting to be applied, which re-queues
+// at most 64.  A round of at most kQueueCap - 64 - (entries held) hits is appended whole; a fuller one (a run of samples in one cell
+// of a coarse level; any round of a level of 2 tiles) goes in by nibbles -- at most 4 x 64 hits each -- with drains between.
+constexpr int kBitRoundSamples = 16 * 64;
+static_assert(64 + kBitRoundSamples / 4 + 64 <= kQueueCap, "bwd_stream_bits: a nibble of a round and the apply's re-queue must fit the queue");
+struct GatherBatch {
+    f32x3 ld_p; f32x2 ld_g;             // written by loads in flight: only ever read behind the wait of PERF_BITS_HALF
+    uint32_t cm, i;                     // combinations (0: not known yet) and sample index of the lane's entry
+    bool live;                          // this lane holds an entry
+};
+
+template <bool FIXED>
+__device__ __forceinline__ void bwd_stream_bits(const BwdCtx& cx, float* lds_tile, uint32_t* queue,
+                                                const uint32_t* __restrict__ row, const float* __restrict__ x01,
+                                                const float2* __restrict__ g_l, int64_t n, int rep, int R) {
+    __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0), see bwd_stream_codes
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t qn = 0;                                    // wave-uniform queue fill
+    // halfwords of the row that hold live samples (the pre-pass writes a block's pieces whole), and this replica's share of them
+    const int64_t h_all = (n + kCodeSamplesPerBlock - 1) / kCodeSamplesPerBlock * (kCodeSamplesPerBlock / 16);
+    const int64_t h_lo = h_all * rep / R, h_hi = h_all * (rep + 1) / R;
+    uint32_t ld_w = 0u;                                 // written by the load in flight
+    GatherBatch A = {{0.f, 0.f, 0.f}, {0.f, 0.f}, 0u, 0u, false}, B = A;          // the two batches that take turns in flight
+    const uint32_t t_hi = cx.t * (uint32_t)kTileEntries, m_hi = cx.mask & ~(uint32_t)(kTileEntries - 1);
+    // (fresh entries: index << 4, the combinations not known yet; re-queued ones carry theirs)
+    auto requeue = [&](uint32_t cm, uint32_t i) __attribute__((always_inline)) { enqueue1(queue, qn, cm != 0u, (i << 4) | cm); };
+    auto load_row = [&](uint32_t h) __attribute__((always_inline)) {                   // 1 load
+        const uint32_t off = (h < (uint32_t)h_hi ? h : (uint32_t)h_hi - 1u) * 2u;
+        asm volatile("global_load_ushort %0, %1, %2" : "+v"(ld_w) : "v"(off), "s"(row) : "memory");      // (in-out: the one register on every path)
+    };
+    // the set bits of a lane's halfword as entries behind the wave's: bit b is sample s0 + 4 b (bit_row_first_sample), e0 = s0 << 4.
+    // incl: the inclusive wave prefix of the popcounts; the caller made room.
+    auto append = [&](uint32_t bits, uint32_t e0, uint32_t incl) __attribute__((always_inline)) {
+        uint32_t* q = queue + qn + (incl - (uint32_t)__popc(bits));
+        while (bits) {
+            const uint32_t b = (uint32_t)__ffs((int)bits) - 1u;
+            bits &= bits - 1u;
+            *q++ = e0 + (b << 6);
+        }
+        qn += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    };
+    // up to 64 queued samples into batch X: 2 loads; returns how many
+    auto pop_and_gather = [&](GatherBatch& X) __attribute__((always_inline)) {
+        // (readfirstlane: scalar min and subtract -- left to itself the compiler forms qn - take as a saturating VECTOR subtract)
+        const uint32_t take = (uint32_t)__builtin_amdgcn_readfirstlane((int)(qn < 64u ? qn : 64u));
+        __builtin_amdgcn_wave_barrier();
+        uint32_t e = 0;
+        if (lane < take) e = (queue + (qn - take))[lane];
+        __builtin_amdgcn_wave_barrier();
+        qn -= take;
+        X.live = lane < take;
+        X.cm = e & 15u;
+        X.i = e >> 4;
+        uint32_t ox, og;
+        sample_offsets(X.i, ox, og);
+        asm volatile("global_load_dwordx3 %0, %2, %3\n\tglobal_load_dwordx2 %1, %4, %5"
+                     : "+v"(X.ld_p), "+v"(X.ld_g) : "v"(ox), "s"(x01), "v"(og), "s"(g_l) : "memory");     // (in-out: the batch's one register set)
+        return take;
+    };
+    // Every lane applies ONE combination; the samples that name this tile with two or more go back into the queue with the rest.
+    auto apply_batch = [&](const GatherBatch& X, float bx, f32x2 byz, f32x2 bg) __attribute__((always_inline)) {
+        const float px = grid_pos(bx, cx.scale), py = grid_pos_alone(byz.x, cx.scale), pz = grid_pos_alone(byz.y, cx.scale);
+        const float flx = floorf(px), fly = floorf(py), flz = floorf(pz);
+        const uint32_t gx = (uint32_t)(int32_t)flx;
+        // (a bit-row level has at most 2^18 entries: only the low 24 bits of the (y,z) terms count, and those are the low 24 bits of
+        //  the full-rate 24-bit product of the factors' low 24 bits, for any cell -- the pre-pass's own expressions, hashed_tiles)
+        const uint32_t ay0 = __umul24((uint32_t)(int32_t)fly, kPrimeY & 0xffffffu), az0 = __umul24((uint32_t)(int32_t)flz, kPrimeZ & 0xffffffu);
+        const uint32_t ay1 = ay0 + kPrimeY, az1 = az0 + kPrimeZ;
+        // (tile == t, with the tile's bits of the index compared in place)
+        const uint32_t derived = ((((ay0 ^ az0) & m_hi) == t_hi) ? 1u : 0u) | ((((ay1 ^ az0) & m_hi) == t_hi) ? 2u : 0u) |
+                                 ((((ay0 ^ az1) & m_hi) == t_hi) ? 4u : 0u) | ((((ay1 ^ az1) & m_hi) == t_hi) ? 8u : 0u);
+        uint32_t cm = X.cm ? X.cm : derived;
+        if (!X.live || gx >= (uint32_t)(kTileEntries - 1)) cm = 0u;     // (idle lane; or zero gradient, see tile_codes4_kernel)
+        const uint32_t rest = cm & (cm - 1u);
+        cm &= 0u - cm;
+        if (cm) apply_pair_one<FIXED>(cx, lds_tile, make_float2(bg.x, bg.y), gx, px - flx, sub_alone(py, fly), sub_alone(pz, flz), ay0, az0, cm);
+        requeue(rest, X.i);
+    };
+    // One half of the loop's body: feed the queue when it runs low, pop batch Y, then wait for batch X -- popped one half earlier --
+    // and apply it from the registers it landed in.  Each batch has ONE pop and ONE apply in the text of the loop, and its registers
+    // are in-out operands of both: wherever a pop or an apply stood twice, the compiler gave the batch a register set per place and
+    // copied between them while its loads were in flight (a wait count chosen by a branch between two such statements did the same).
+    // In flight at the wait, oldest first: [X: 2][the row][Y: 2], or the batches alone, so the wait leaves 2 loads out.
+    // (After a change to this loop, compare the registers of the loads with those of the waits and the applies in the assembly.)
+#define PERF_BITS_HALF(X, Y)                                                                                            \
+    {                                                                                                                   \
+        const bool fed = feed();                                                                                        \
+        const uint32_t popped = pop_and_gather(Y);                                                                      \
+        asm volatile("s_waitcnt vmcnt(2)" : "+v"(X.ld_p), "+v"(X.ld_g) : : "memory");                                   \
+        apply_batch(X, X.ld_p.x, f32x2{X.ld_p.y, X.ld_p.z}, X.ld_g);                                                    \
+        if (fed && base < h_end) load_row(h);                                                                           \
+        if (popped == 0u && qn == 0u && nibble == 4 && base >= h_end) break;                                            \
+    }
+    const uint32_t h_end = (uint32_t)h_hi;              // (halfwords and sample indices fit 32 bits: kMaxCodedSamples)
+    uint32_t h = (uint32_t)h_lo + threadIdx.x;
+    // the round to take next, wave-uniform and kept on the scalar unit
+    uint32_t base = (uint32_t)h_lo + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
+    uint32_t rest = 0u, e0 = 0u;        // what is left of a round that did not fit, and its lanes' first entries
+    int nibble = 4;                     // the next nibble of `rest` (4: none left)
+    // the next round, or the next nibble of one that did not fit, once the queue holds fewer than 64 entries; true: a round was taken
+    auto feed = [&]() __attribute__((always_inline)) {
+        bool fed = false;
+        if (qn < 64u && (nibble < 4 || base < h_end)) {
+            if (nibble == 4) {
+                uint32_t w;         // (the row may be the youngest load in flight)
+                asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %1" : "=&v"(w) : "v"(ld_w) : "memory");
+                const uint32_t bits = h < h_end ? w : 0u;       // a lane without a halfword of its own in the last round hits nothing
+                e0 = bit_row_first_sample(h) << 4;
+                h += kBwdThreads;
+                base += kBwdThreads;
+                fed = true;
+                const uint32_t incl = wave_inclusive_sum((uint32_t)__popc(bits));
+                const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+                if (qn + total <= (uint32_t)(kQueueCap - 64)) append(bits, e0, incl);
+                else { rest = bits; nibble = 0; }
+            }
+            if (nibble < 4) {
+                const uint32_t nib = rest & (0xfu << (4 * nibble));
+                append(nib, e0, wave_inclusive_sum((uint32_t)__popc(nib)));
+                ++nibble;
+            }
+        }
+        return fed;
+    };
+    if (base < h_end) {
+        load_row(h);
+        (void)pop_and_gather(A);        // empty queue: dummy gather, keeps the in-flight count of the loop static
+        for (;;) {
+            PERF_BITS_HALF(A, B)
+            PERF_BITS_HALF(B, A)
+        }
+        // (the last pop took nothing: its dummy loads land before the registers are anybody else's)
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(A.ld_p), "+v"(A.ld_g), "+v"(B.ld_p), "+v"(B.ld_g) : : "memory");
+    }
+#undef PERF_BITS_HALF
+    asm volatile("" : : "v"(ld_w));                     // (the last row load landed with a vmcnt(0) above)
 }
 
 // Owner of one tile of a bitmap level.  A wave reads 64 words of the row per step (2048 samples), turns the set bits into
@@ -1297,7 +1375,7 @@ __global__ __launch_bounds__(kBwdThreads) void hashgrid_bwd_kernel(GridParams gp
     uint32_t* queue = reinterpret_cast<uint32_t*>(lds_tile + 2 * kTileEntries) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kQueueCap;
     if (by_bitmap && hashed) bwd_stream_bitmap<FIXED, false>(cx, lds_tile, queue, bitmaps + (int64_t)(tp.bm_row[l] + (int)t) * tp.bm_row_words, x01, g_l, n_live);
     else if (by_bitmap) bwd_stream_bitmap<FIXED, true>(cx, lds_tile, queue, bitmaps + (int64_t)(tp.bm_row[l] + (int)t) * tp.bm_row_words, x01, g_l, n_live);
-    else if (coded && hashed && n_tiles <= (uint32_t)kMaskTiles) bwd_stream_masks<FIXED>(cx, lds_tile, queue, codes + (int64_t)tp.code_slot[l] * tp.n_pad, x01, g_l, n_live, rep, R);
+    else if (coded && hashed && n_tiles <= (uint32_t)kMaskTiles) bwd_stream_bits<FIXED>(cx, lds_tile, queue, codes + (int64_t)tp.code_slot[l] * tp.n_pad + (int64_t)t * bit_row_words(n), x01, g_l, n_live, rep, R);
     else if (coded && hashed) bwd_stream_codes<FIXED, false>(cx, lds_tile, queue, codes + (int64_t)tp.code_slot[l] * tp.n_pad, x01, g_l, n_live, rep, R);
     else if (coded) bwd_stream_codes<FIXED, true>(cx, lds_tile, queue, codes + (int64_t)tp.code_slot[l] * tp.n_pad, x01, g_l, n_live, rep, R);
     else if (hashed) bwd_stream<FIXED, true>(cx, lds_tile, x01, g_l, n_live, rep, R);
@@ -1772,6 +1850,10 @@ int perf_internal_hashgrid_bwd_riders(const perf_grid_desc* grid, const float* x
     int32_t* shifts_ws = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + shifts_at);
     // tile codes of the multi-tile levels (workspace permitting)
     const int slots = plan_codes(gp, n, &tp);
+    // (a slot holds a block's sixteen 32-byte pieces whole only from 256 rows on, see bit_row_words: below that the bit-row levels'
+    //  slots stay unused)
+    for (int l = 0; l < gp.n_levels; ++l)
+        if (n < kCodeSamplesPerBlock && gp.hashed[l] && tp.tiles_of[l] <= kMaskTiles) tp.code_slot[l] = -1;
     uint32_t* codes = nullptr;
     uint32_t* escape = nullptr;
     uint32_t* bitmaps = nullptr;

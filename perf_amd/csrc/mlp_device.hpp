@@ -100,10 +100,46 @@ __device__ __forceinline__ int frag_src(int f, int c, int h, int j) {
     return (in < L::n_in_pad) ? L::w1_off + slot_neuron(s, h, j) * L::n_in_pad + in : -1;
 }
 
-// Stage permuted weight fragments into LDS: frag f occupies lds[f*64 + lane] (16 B per lane).  The elements of ALL of a wave's
-// fragments are requested before any is packed: one memory round trip per block instead of one per fragment.
+// Position of weight element src in the block's LDS copy of the weight vector: every matrix row starts two elements -- one bank --
+// further than in memory, so that the 32 rows a fragment element is gathered from lie in 32 different banks (rows of 16 KS or 64
+// elements are a whole number of half-turns round the banks: the same bank, or two, for all of a wave's lanes).
+template <int NH, int KS>
+__device__ __forceinline__ int raw_slot(int src) {
+    using L = Layout<NH, KS>;
+    return src + 2 * (src < L::w2_off ? src / L::n_in_pad : 64 + (src - L::w2_off) / 64);
+}
+template <int NH, int KS>
+constexpr int raw_bytes() {      // (a multiple of 16)
+    using L = Layout<NH, KS>;
+    return (2 * (L::n_params + 2 * (64 + (L::n_params - L::w2_off) / 64)) + 15) / 16 * 16;
+}
+
+// Stage permuted weight fragments into LDS: frag f occupies lds[f*64 + lane] (16 B per lane).  The block first copies the weight
+// vector to LDS (`raw`, raw_bytes(): room the caller provides beside the fragments) with COALESCED loads -- one 128-byte line per
+// wave instruction -- and gathers the fragments' elements from there.  Gathered from memory, a fragment element cost a wave
+// instruction over 16 or 32 lines, 16 to 32 such instructions per wave and up to 16 waves per CU at once: the texture addresser
+// walked them for microseconds before the first tile, in every launch.
+// (The elements of ALL of a wave's fragments are requested before any is packed: one round trip instead of one per fragment.)
+// Without `raw` (the two-argument form: the surface-normal kernels, which have no room set aside) the elements are gathered from memory.
+template <int NH, int KS, bool BWD, bool PADDED>
+__device__ __forceinline__ void gather_fragments(const uint16_t* w, u32x4* lds);
 template <int NH, int KS, bool BWD>
-__device__ __forceinline__ void stage_fragments(const uint16_t* __restrict__ w, u32x4* lds) {
+__device__ __forceinline__ void stage_fragments(const uint16_t* __restrict__ w, u32x4* lds) { gather_fragments<NH, KS, BWD, false>(w, lds); }
+template <int NH, int KS, bool BWD>
+__device__ __forceinline__ void stage_fragments(const uint16_t* __restrict__ w, u32x4* lds, uint16_t* raw) {
+    using L = Layout<NH, KS>;
+    static_assert(L::n_params % 256 == 0, "the copy below takes whole turns of the block");
+    constexpr int per_thread = L::n_params / 256;
+    uint16_t e[per_thread];
+#pragma unroll
+    for (int i = 0; i < per_thread; ++i) e[i] = w[256 * i + (int)threadIdx.x];
+#pragma unroll
+    for (int i = 0; i < per_thread; ++i) raw[raw_slot<NH, KS>(256 * i + (int)threadIdx.x)] = e[i];
+    __syncthreads();
+    gather_fragments<NH, KS, BWD, true>(raw, lds);
+}
+template <int NH, int KS, bool BWD, bool PADDED>
+__device__ __forceinline__ void gather_fragments(const uint16_t* w, u32x4* lds) {
     using L = Layout<NH, KS>;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;     // (blocks of four waves)
     const int c = lane & 31, h = lane >> 5;
@@ -116,7 +152,8 @@ __device__ __forceinline__ void stage_fragments(const uint16_t* __restrict__ w, 
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int src = frag_src<NH, KS>(f, c, h, j);
-            v[k][j] = w[src < 0 ? 0 : src];
+            const int at = src < 0 ? 0 : src;
+            v[k][j] = w[PADDED ? raw_slot<NH, KS>(at) : at];
         }
     }
 #pragma unroll
@@ -207,17 +244,18 @@ struct RowsIn {
 };
 
 template <typename T16, int NH, int KS, bool FUSED, bool ROWS = false>
-__global__ __launch_bounds__(256) void mlp_fwd_kernel(MlpParams mp, const uint16_t* __restrict__ w,
+__global__ __launch_bounds__(256, (NH == 1 && KS == 1 && !FUSED && !ROWS) ? 5 : 1) void mlp_fwd_kernel(MlpParams mp, const uint16_t* __restrict__ w,
                                                       const uint32_t* __restrict__ feat,
                                                       const uint8_t* __restrict__ sel, float* __restrict__ out,
                                                       int64_t n, const int64_t* __restrict__ n_dev,
                                                       std::conditional_t<FUSED, FusedIn, std::conditional_t<ROWS, RowsIn, NoFusedIn>> fz) {
     static_assert(!(FUSED && ROWS), "the fused kernel forms its features itself");
     using L = Layout<NH, KS>;
+    constexpr bool kSmallestPlain = NH == 1 && KS == 1 && !FUSED && !ROWS;       // (five waves per SIMD: the launch bounds above)
     const int64_t n_live = live_count(n, n_dev);        // n stays the stride of the level-major features
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32x4* frag = reinterpret_cast<u32x4*>(smem);
-    stage_fragments<NH, KS, false>(w, frag);
+    stage_fragments<NH, KS, false>(w, frag, reinterpret_cast<uint16_t*>(smem + L::n_fwd * 1024));
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
@@ -225,6 +263,9 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(MlpParams mp, const uint16
     struct TileIn { u32x4 b1[KS]; uint8_t sv; };
     // the layers and the store of one tile, given the packed first-layer operand
     auto layers = [&](int64_t si, bool valid, const u32x4 (&b1)[KS], float sv) __attribute__((always_inline)) {
+        // (the smallest net's six fragments are read per tile, as everywhere else: held in registers across the loop they cost
+        // the kernel 20 registers and its fifth wave per SIMD)
+        if constexpr (kSmallestPlain) asm volatile("" ::: "memory");
         f32x16 acc[2];
         u32x4 hb[4];
 #pragma unroll
@@ -469,7 +510,8 @@ __global__ __launch_bounds__(256, (KS < 3 && !(NH == 2 && KS == 2 && !FAST)) ? 2
     uint16_t* tA = reinterpret_cast<uint16_t*>(smem + L::n_all * 1024) + wave * (2 * kTile * kPitchT);
     uint16_t* tB = tA + kTile * kPitchT;
     const int off32 = tr_offset32(lane), off16 = tr_offset16(lane);
-    stage_fragments<NH, KS, true>(w, frag);
+    static_assert(raw_bytes<NH, KS>() <= 4 * 2 * kTile * kPitchT * 2, "the weight copy borrows the tiles' room");
+    stage_fragments<NH, KS, true>(w, frag, reinterpret_cast<uint16_t*>(smem + L::n_all * 1024));      // (the tiles are first written behind the barrier below)
     __syncthreads();
     const int c = lane & 31, h = lane >> 5;
     const int64_t n_tiles = (n_live + kTile - 1) / kTile;
@@ -831,21 +873,21 @@ namespace perf {
 template <typename T16, int NH, int KS>
 static void launch_fwd(int blocks, hipStream_t st, MlpParams mp, const uint16_t* w, const uint32_t* feat, const uint8_t* sel,
                        float* out, int64_t n, const int64_t* n_dev) {
-    constexpr int lds_bytes = Layout<NH, KS>::n_fwd * 1024;
+    constexpr int lds_bytes = Layout<NH, KS>::n_fwd * 1024 + raw_bytes<NH, KS>();
     mlp_fwd_kernel<T16, NH, KS, false><<<dim3(blocks), dim3(256), lds_bytes, st>>>(mp, w, feat, sel, out, n, n_dev, NoFusedIn{});
 }
 
 template <typename T16, int NH, int KS>
 static void launch_fwd_rows(int blocks, hipStream_t st, MlpParams mp, const uint16_t* w, const uint32_t* feat, const int32_t* feat_index,
                             int64_t feat_stride, const uint8_t* sel, float* out, int64_t n, const int64_t* n_dev) {
-    constexpr int lds_bytes = Layout<NH, KS>::n_fwd * 1024;
+    constexpr int lds_bytes = Layout<NH, KS>::n_fwd * 1024 + raw_bytes<NH, KS>();
     mlp_fwd_kernel<T16, NH, KS, false, true><<<dim3(blocks), dim3(256), lds_bytes, st>>>(mp, w, feat, sel, out, n, n_dev, RowsIn{feat_index, feat_stride});
 }
 
 template <typename T16, int NH, int KS>
 static void launch_fused(int blocks, hipStream_t st, MlpParams mp, const uint16_t* w, const uint8_t* sel, float* out, int64_t n,
                          const int64_t* n_dev, FusedIn fz) {
-    constexpr int lds_bytes = Layout<NH, KS>::n_fwd * 1024;
+    constexpr int lds_bytes = Layout<NH, KS>::n_fwd * 1024 + raw_bytes<NH, KS>();
     mlp_fwd_kernel<T16, NH, KS, true><<<dim3(blocks), dim3(256), lds_bytes, st>>>(mp, w, nullptr, sel, out, n, n_dev, fz);
 }
 

@@ -11,7 +11,7 @@ LIB = os.path.join(HERE, 'libperf_hip.so')
 # (the MLP kernels are instantiated in six units of their own: one unit took 65 s, the longest of them now takes ~15 s)
 SOURCES = ['mlp_bwd_bf16_nh2.hip', 'mlp_bwd_fp16_nh2.hip', 'mlp_bwd_bf16_nh1.hip', 'mlp_bwd_fp16_nh1.hip', 'mlp_fwd_bf16.hip', 'mlp_fwd_fp16.hip', 'mlp_fwd_rows.hip',
            'hashgrid_bwd.hip', 'hashgrid_bwd_lines.hip', 'hashgrid_fwd.hip', 'hashgrid_aux.hip', 'march.hip', 'misc.hip', 'composite.hip', 'mlp.hip', 'visibility.hip', 'field_normal.hip', 'field_normal_bwd.hip', 'sphere_field.hip', 'hashgrid_pair.hip', 'joint_align.hip', 'mesh.hip', 'brickmesh.hip', 'meshcc.hip', 'meshvis.hip', 'meshsimp.hip', 'meshcolor.hip', 'meshray.hip']
-HEADERS = ['common.hpp', 'grid_device.hpp', 'grid_fixed_point.hpp', 'mlp_reduce_device.hpp', 'step_book_device.hpp', 'mlp_device.hpp', 'field_normal_device.hpp', 'mesh_device.hpp', 'mesh_scan_device.hpp', 'mesh_filter_device.hpp', 'mesh_check_host.hpp', 'pano_lookup_device.hpp', 'march_device.hpp', 'step_riders_device.hpp']
+HEADERS = ['common.hpp', 'grid_device.hpp', 'grid_fixed_point.hpp', 'mlp_reduce_device.hpp', 'step_book_device.hpp', 'mlp_device.hpp', 'field_normal_device.hpp', 'mesh_device.hpp', 'mesh_scan_device.hpp', 'mesh_filter_device.hpp', 'mesh_check_host.hpp', 'pano_lookup_device.hpp', 'march_device.hpp', 'step_riders_device.hpp', 'composite_device.hpp']
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs (no v_accvgpr_read per accumulator register before the epilogues)
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
          '-mllvm', '-amdgpu-mfma-vgpr-form=1']

@@ -9,74 +9,16 @@
 // unfused adds so that thresholds on it (early termination) are bit-exact against
 // oracle/perf_oracle.py:packed_exclusive_sum_canonical.
 #include "common.hpp"
+#include "composite_device.hpp"
 
 namespace perf {
-
-__device__ __forceinline__ float wave_incl_scan_f(float x, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        float y = __shfl_up(x, off);
-        if (lane >= off) x = add_rn(x, y);
-    }
-    return x;
-}
-
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
-// exclusive prefix within the ray: returns ex for this lane's sample, updates carry
-__device__ __forceinline__ float chunk_excl(float v, int lane, float& carry) {
-    const float inc = wave_incl_scan_f(v, lane);
-    float prev = __shfl_up(inc, 1);
-    if (lane == 0) prev = 0.f;
-    const float ex = add_rn(carry, prev);
-    carry = add_rn(carry, __shfl(inc, 63));
-    return ex;
-}
 
 // ---- ray teams ------------------------------------------------------------------------------------------------------
 // A wave serves FOUR rays.  When all four hold at most 16 samples each gets a quarter wave (16 lanes): a trained scene
 // keeps a sample or two per ray, a whole wavefront per ray then idles 60 of its 64 lanes (eval frames: 5 x 10^5 rays).
 // Otherwise the wave walks its four rays one after the other with all 64 lanes.  Both ways produce the same bits: the
 // canonical scan is Kogge-Stone inside 64-sample chunks, and for <= 16 samples its offsets 16 and 32 -- like the butterfly
-// steps 32 and 16 of the reductions -- only ever add exact zeros.
-template <int W> struct Team { static constexpr int width = W; };
-
-template <int W>
-__device__ __forceinline__ float team_incl_scan_f(float x, int l) {
-#pragma unroll
-    for (int off = 1; off < W; off <<= 1) {
-        const float y = __shfl_up(x, off, W);
-        if (l >= off) x = add_rn(x, y);
-    }
-    return x;
-}
-template <int W>
-__device__ __forceinline__ float team_sum(float x) {
-#pragma unroll
-    for (int off = W / 2; off >= 1; off >>= 1) x += __shfl_xor(x, off, W);
-    return x;
-}
-template <int W>
-__device__ __forceinline__ float team_chunk_excl(float v, int l, float& carry) {
-    const float inc = team_incl_scan_f<W>(v, l);
-    float prev = __shfl_up(inc, 1, W);
-    if (l == 0) prev = 0.f;
-    const float ex = add_rn(carry, prev);
-    carry = add_rn(carry, __shfl(inc, W - 1, W));
-    return ex;
-}
-// ballot restricted to the caller's team (bit k = lane k of the team)
-template <int W>
-__device__ __forceinline__ unsigned long long team_ballot(bool p) {
-    const unsigned long long b = __ballot(p);
-    if (W == 64) return b;
-    return (b >> (((threadIdx.x & 63) / W) * W)) & ((1ull << W) - 1ull);
-}
-
+// steps 32 and 16 of the reductions -- only ever add exact zeros.  (Team<W> and the team_* helpers: composite_device.hpp)
 // Two launch shapes, told apart by the grid size (team_grid); a third one -- sixteen rays per wave, BY16 -- has its own instantiations:
 //  * packed (n_rays / 4 waves; chosen when that still fills the GPU, i.e. eval batches): wave w serves rays 4w..4w+3 --
 //    a quarter wave each when all four hold <= 16 samples, one after the other with all 64 lanes otherwise;
@@ -146,6 +88,14 @@ __device__ __forceinline__ void for_rays_of_wave(int64_t n_rays, CountFn count_o
         body(Team<64>{}, w, lane);
     }
 }
+// the kernels launched on ray_grid: a wavefront per ray and nothing else
+template <typename Body>
+__device__ __forceinline__ void for_ray_of_wave(int64_t n_rays, Body body) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n_rays) return;
+    body(r, (int)(threadIdx.x & 63));
+}
+static inline dim3 ray_grid(int64_t n_rays) { return dim3((unsigned)div_up(n_rays, 4)); }
 static inline dim3 team_grid(int64_t n_rays) {
     return dim3((unsigned)(n_rays / 4 >= kPackedMinWaves ? div_up(n_rays, 16) : div_up(n_rays, 4)));
 }
@@ -155,6 +105,12 @@ static inline dim3 team_grid(int64_t n_rays) {
 constexpr int64_t kBy16MinRays = 16 * 4 * kPackedMinWaves;          // 524,288
 static inline bool team_by16(int64_t n_rays) { return n_rays >= kBy16MinRays; }
 static inline dim3 team_grid16(int64_t n_rays) { return dim3((unsigned)div_up(n_rays, 64)); }
+// one argument list for both instantiations of a team kernel
+#define PERF_LAUNCH_TEAMS(KERNEL, n_rays, stream, ...)                                                                                \
+    do {                                                                                                                               \
+        if (perf::team_by16(n_rays)) hipLaunchKernelGGL(KERNEL<true>, perf::team_grid16(n_rays), dim3(256), 0, perf::as_stream(stream), __VA_ARGS__); \
+        else hipLaunchKernelGGL(KERNEL<false>, perf::team_grid(n_rays), dim3(256), 0, perf::as_stream(stream), __VA_ARGS__);           \
+    } while (0)
 
 template <bool BY16>
 __global__ __launch_bounds__(256) void visibility_count_kernel(const float* __restrict__ sig, const float* __restrict__ ts,
@@ -168,7 +124,7 @@ __global__ __launch_bounds__(256) void visibility_count_kernel(const float* __re
         const int cnt = packed[2 * r + 1];
         float carry = 0.f;
         int kept = 0;
-        for (int c0 = 0; c0 < cnt; c0 += 64) {
+        for (int c0 = 0; c0 < cnt; c0 += W) {
             const int i = c0 + l;
             const bool valid = i < cnt;
             float sd = 0.f;
@@ -207,27 +163,26 @@ __global__ __launch_bounds__(256) void compact_prefix_kernel(const int32_t* __re
                                                              const float* __restrict__ x01_in, const uint8_t* __restrict__ sel_in,
                                                              float* __restrict__ x01_out, uint8_t* __restrict__ sel_out,
                                                              FeatCopy fc) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n_rays) return;
-    const int64_t src = packed[2 * r];
-    const int cnt = new_counts[r];
-    const int64_t dst = new_offsets[r];
-    if (lane == 0) { packed_out[2 * r] = (int32_t)dst; packed_out[2 * r + 1] = cnt; }
-    for (int i = lane; i < cnt; i += 64) {
-        ts_out[dst + i] = ts_in[src + i];
-        te_out[dst + i] = te_in[src + i];
-        ri_out[dst + i] = r;
-        if (sig_out) sig_out[dst + i] = sig_in[src + i];
-        if (sel_out) sel_out[dst + i] = sel_in[src + i];
-    }
-    if (x01_out)            // positions of the kept samples: 3*cnt contiguous floats
-        for (int i = lane; i < 3 * cnt; i += 64) x01_out[3 * dst + i] = x01_in[3 * src + i];
-    if (fc.out)             // level-major encoded features of the kept samples (one packed 2x16-bit dword per level)
-        for (int l = 0; l < fc.n_levels; ++l)
-            for (int i = lane; i < cnt; i += 64) fc.out[(int64_t)l * fc.stride_out + dst + i] = fc.in_h[(int64_t)l * fc.stride_h + src + i];
-    if (fc.src_index_out)   // ... or where they are (perf_mlp_bwd reads them in place)
-        for (int i = lane; i < cnt; i += 64) fc.src_index_out[dst + i] = (int32_t)(src + i);
+    for_ray_of_wave(n_rays, [&](int64_t r, int lane) {
+        const int64_t src = packed[2 * r];
+        const int cnt = new_counts[r];
+        const int64_t dst = new_offsets[r];
+        if (lane == 0) { packed_out[2 * r] = (int32_t)dst; packed_out[2 * r + 1] = cnt; }
+        for (int i = lane; i < cnt; i += 64) {
+            ts_out[dst + i] = ts_in[src + i];
+            te_out[dst + i] = te_in[src + i];
+            ri_out[dst + i] = r;
+            if (sig_out) sig_out[dst + i] = sig_in[src + i];
+            if (sel_out) sel_out[dst + i] = sel_in[src + i];
+        }
+        if (x01_out)            // positions of the kept samples: 3*cnt contiguous floats
+            for (int i = lane; i < 3 * cnt; i += 64) x01_out[3 * dst + i] = x01_in[3 * src + i];
+        if (fc.out)             // level-major encoded features of the kept samples (one packed 2x16-bit dword per level)
+            for (int l = 0; l < fc.n_levels; ++l)
+                for (int i = lane; i < cnt; i += 64) fc.out[(int64_t)l * fc.stride_out + dst + i] = fc.in_h[(int64_t)l * fc.stride_h + src + i];
+        if (fc.src_index_out)   // ... or where they are (perf_mlp_bwd reads them in place)
+            for (int i = lane; i < cnt; i += 64) fc.src_index_out[dst + i] = (int32_t)(src + i);
+    });
 }
 
 template <bool BY16>
@@ -244,8 +199,8 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const float* __restr
         const int cnt = packed[2 * r + 1];
         float carry = 0.f;
         float a_op = 0.f, a_d = 0.f, a_r = 0.f, a_g = 0.f, a_b = 0.f;
-        float cW = 0.f, cWM = 0.f, a_dl = 0.f;          // distortion loss of the ray (same arithmetic as distloss_fwd_kernel)
-        for (int c0 = 0; c0 < cnt; c0 += 64) {
+        float cW = 0.f, cWM = 0.f, a_dl = 0.f;          // distortion loss of the ray
+        for (int c0 = 0; c0 < cnt; c0 += TW) {
             const int i = c0 + l;
             const bool valid = i < cnt;
             float sd = 0.f, t0 = 0.f, t1 = 0.f;
@@ -253,9 +208,8 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const float* __restr
             const float ex = team_chunk_excl<TW>(sd, l, carry);
             float w_dl = 0.f;
             if (valid) {
-                const float T = expf(-ex);
-                const float al = 1.0f - expf(-sd);
-                const float w = T * al;
+                float T, al, w;
+                ray_weight(ex, sd, T, al, w);
                 w_dl = w;
                 if (weights) weights[start + i] = w;
                 if (trans) trans[start + i] = T;
@@ -270,9 +224,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const float* __restr
             }
             if (distloss) {
                 const float m = (t0 + t1) * 0.5f, d = t1 - t0;
-                const float Wp = team_chunk_excl<TW>(w_dl, l, cW);
-                const float WMp = team_chunk_excl<TW>(w_dl * m, l, cWM);
-                if (valid) a_dl += d * w_dl * w_dl * (1.0f / 3.0f) + 2.0f * w_dl * (m * Wp - WMp);
+                distloss_chunk<TW>(w_dl, m, d, valid, l, cW, cWM, a_dl);
             }
         }
         if (distloss) { a_dl = team_sum<TW>(a_dl); if (l == 0) distloss[r] = a_dl; }
@@ -328,25 +280,14 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
         }
         if (with_dl) {
             const float m = (t0 + t1) * 0.5f, wm = w * m;
-            float sw = w, swm = wm;                     // inclusive suffix sums within the chunk
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const float y0 = __shfl_down(sw, off), y1 = __shfl_down(swm, off);
-                if (lane + off < 64) { sw += y0; swm += y1; }
-            }
+            const float sw = team_suffix_incl<64>(w, lane), swm = team_suffix_incl<64>(wm, lane);
             const float Wsuf = sufW + (sw - w), WMsuf = sufWM + (swm - wm);
             const float W = totW - Wsuf - w, WM = totWM - WMsuf - wm;
             if (valid) G += dl_scale * ((2.0f / 3.0f) * (t1 - t0) * w + 2.0f * (m * (W - Wsuf) - (WM - WMsuf)));
             sufW += __shfl(sw, 0); sufWM += __shfl(swm, 0);
         }
         const float qv = G * w + gT * T;
-        // inclusive suffix sum within the chunk
-        float suf = qv;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            float y = __shfl_down(suf, off);
-            if (lane + off < 64) suf += y;
-        }
+        const float suf = team_suffix_incl<64>(qv, lane);
         const float later = carry + (suf - qv);
         if (valid) {
             const float delta = t1 - t0;
@@ -357,27 +298,24 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
     }
 }
 
-// distortion loss, per ray:  sum_i ( d_i w_i^2 / 3 + 2 w_i (m_i W_i - WM_i) ),  W, WM exclusive prefixes
+// distortion loss per ray from given weights (distloss_chunk)
 __global__ __launch_bounds__(256) void distloss_fwd_kernel(const float* __restrict__ w, const float* __restrict__ ts,
                                                            const float* __restrict__ te, const int32_t* __restrict__ packed,
                                                            int64_t n_rays, float* __restrict__ loss) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n_rays) return;
-    const int64_t start = packed[2 * r];
-    const int cnt = packed[2 * r + 1];
-    float cW = 0.f, cWM = 0.f, acc = 0.f;
-    for (int c0 = 0; c0 < cnt; c0 += 64) {
-        const int i = c0 + lane;
-        const bool valid = i < cnt;
-        float wi = 0.f, m = 0.f, d = 0.f;
-        if (valid) { wi = w[start + i]; const float a = ts[start + i], b = te[start + i]; m = (a + b) * 0.5f; d = b - a; }
-        const float W = chunk_excl(wi, lane, cW);
-        const float WM = chunk_excl(wi * m, lane, cWM);
-        if (valid) acc += d * wi * wi * (1.0f / 3.0f) + 2.0f * wi * (m * W - WM);
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) loss[r] = acc;
+    for_ray_of_wave(n_rays, [&](int64_t r, int lane) {
+        const int64_t start = packed[2 * r];
+        const int cnt = packed[2 * r + 1];
+        float cW = 0.f, cWM = 0.f, acc = 0.f;
+        for (int c0 = 0; c0 < cnt; c0 += 64) {
+            const int i = c0 + lane;
+            const bool valid = i < cnt;
+            float wi = 0.f, m = 0.f, d = 0.f;
+            if (valid) { wi = w[start + i]; const float a = ts[start + i], b = te[start + i]; m = (a + b) * 0.5f; d = b - a; }
+            distloss_chunk<64>(wi, m, d, valid, lane, cW, cWM, acc);
+        }
+        acc = team_sum<64>(acc);
+        if (lane == 0) loss[r] = acc;
+    });
 }
 
 // d loss / d w_i = scale * ( 2/3 d_i w_i + 2 ( m_i (W_i - Wsuf_i) - (WM_i - WMsuf_i) ) )
@@ -385,48 +323,46 @@ __global__ __launch_bounds__(256) void distloss_bwd_kernel(const float* __restri
                                                            const float* __restrict__ te, const int32_t* __restrict__ packed,
                                                            int64_t n_rays, float scale, const float* __restrict__ scale_dev,
                                                            float* __restrict__ g_w) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n_rays) return;
-    if (scale_dev) scale *= scale_dev[0];
-    const int64_t start = packed[2 * r];
-    const int cnt = packed[2 * r + 1];
-    float totW = 0.f, totWM = 0.f;
-    for (int i = lane; i < cnt; i += 64) {
-        const float wi = w[start + i];
-        totW += wi; totWM += wi * ((ts[start + i] + te[start + i]) * 0.5f);
-    }
-    totW = wave_sum(totW); totWM = wave_sum(totWM);
-    float cW = 0.f, cWM = 0.f;
-    for (int c0 = 0; c0 < cnt; c0 += 64) {
-        const int i = c0 + lane;
-        const bool valid = i < cnt;
-        float wi = 0.f, m = 0.f, d = 0.f;
-        if (valid) { wi = w[start + i]; const float a = ts[start + i], b = te[start + i]; m = (a + b) * 0.5f; d = b - a; }
-        const float W = chunk_excl(wi, lane, cW);
-        const float WM = chunk_excl(wi * m, lane, cWM);
-        if (valid) {
-            const float Wsuf = totW - W - wi, WMsuf = totWM - WM - wi * m;
-            g_w[start + i] = scale * ((2.0f / 3.0f) * d * wi + 2.0f * (m * (W - Wsuf) - (WM - WMsuf)));
+    for_ray_of_wave(n_rays, [&](int64_t r, int lane) {
+        if (scale_dev) scale *= scale_dev[0];
+        const int64_t start = packed[2 * r];
+        const int cnt = packed[2 * r + 1];
+        float totW = 0.f, totWM = 0.f;                  // lane-strided totals and prefix scans: NOT composite_bwd_kernel's form of this gradient
+        for (int i = lane; i < cnt; i += 64) {
+            const float wi = w[start + i];
+            totW += wi; totWM += wi * ((ts[start + i] + te[start + i]) * 0.5f);
         }
-    }
+        totW = team_sum<64>(totW); totWM = team_sum<64>(totWM);
+        float cW = 0.f, cWM = 0.f;
+        for (int c0 = 0; c0 < cnt; c0 += 64) {
+            const int i = c0 + lane;
+            const bool valid = i < cnt;
+            float wi = 0.f, m = 0.f, d = 0.f;
+            if (valid) { wi = w[start + i]; const float a = ts[start + i], b = te[start + i]; m = (a + b) * 0.5f; d = b - a; }
+            const float W = team_chunk_excl<64>(wi, lane, cW);
+            const float WM = team_chunk_excl<64>(wi * m, lane, cWM);
+            if (valid) {
+                const float Wsuf = totW - W - wi, WMsuf = totWM - WM - wi * m;
+                g_w[start + i] = scale * ((2.0f / 3.0f) * d * wi + 2.0f * (m * (W - Wsuf) - (WM - WMsuf)));
+            }
+        }
+    });
 }
 
 // accumulate_along_rays: out[r, c] = sum_i w_i * v[i, c]  (v == NULL: C = 1, out[r] = sum_i w_i)
 __global__ __launch_bounds__(256) void accumulate_kernel(const float* __restrict__ w, const float* __restrict__ v,
                                                          const int32_t* __restrict__ packed, int64_t n_rays, int C,
                                                          float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n_rays) return;
-    const int64_t start = packed[2 * r];
-    const int cnt = packed[2 * r + 1];
-    for (int c = 0; c < C; ++c) {
-        float acc = 0.f;
-        for (int i = lane; i < cnt; i += 64) acc += w[start + i] * (v ? v[(start + i) * C + c] : 1.0f);
-        acc = wave_sum(acc);
-        if (lane == 0) out[r * C + c] = acc;
-    }
+    for_ray_of_wave(n_rays, [&](int64_t r, int lane) {
+        const int64_t start = packed[2 * r];
+        const int cnt = packed[2 * r + 1];
+        for (int c = 0; c < C; ++c) {
+            float acc = 0.f;                            // lane-strided: NOT the chunked per-ray sums of composite_fwd_kernel
+            for (int i = lane; i < cnt; i += 64) acc += w[start + i] * (v ? v[(start + i) * C + c] : 1.0f);
+            acc = team_sum<64>(acc);
+            if (lane == 0) out[r * C + c] = acc;
+        }
+    });
 }
 
 // packed_info from sorted ray_indices: start[r] = lower_bound(ray_indices, r)
@@ -442,8 +378,6 @@ __global__ __launch_bounds__(256) void pack_info_kernel(const int64_t* __restric
     packed[2 * r] = (int32_t)first; packed[2 * r + 1] = (int32_t)(lo - first);
 }
 
-static inline dim3 ray_grid(int64_t n_rays) { return dim3((unsigned)div_up(n_rays, 4)); }
-
 }  // namespace perf
 
 using namespace perf;
@@ -456,10 +390,8 @@ extern "C" int perf_visibility_count(const float* sigmas, const float* t_starts,
     if (n_rays == 0) return PERF_OK;
     PERF_REQUIRE(packed_info && new_counts, "NULL pointer");
     PERF_REQUIRE(!tail_counts || (march_counts && head_samples >= 1), "perf_visibility_count: tail counts need the march counts and the head size");
-    if (team_by16(n_rays)) hipLaunchKernelGGL(visibility_count_kernel<true>, team_grid16(n_rays), dim3(256), 0, as_stream(stream), sigmas, t_starts, t_ends,
-                       packed_info, n_rays, thr, new_counts, exsum, march_counts, head_samples, tail_counts);
-    else hipLaunchKernelGGL(visibility_count_kernel<false>, team_grid(n_rays), dim3(256), 0, as_stream(stream), sigmas, t_starts, t_ends,
-                       packed_info, n_rays, thr, new_counts, exsum, march_counts, head_samples, tail_counts);
+    PERF_LAUNCH_TEAMS(visibility_count_kernel, n_rays, stream, sigmas, t_starts, t_ends, packed_info, n_rays, thr, new_counts, exsum,
+                      march_counts, head_samples, tail_counts);
     PERF_LAUNCH_CHECK("perf_visibility_count");
     return PERF_OK;
 }
@@ -491,10 +423,8 @@ extern "C" int perf_composite_fwd(const float* sigmas, const float* rgbs, const 
     PERF_REQUIRE(n_rays >= 0, "n_rays < 0");
     if (n_rays == 0) return PERF_OK;
     PERF_REQUIRE(packed_info, "NULL pointer");
-    if (team_by16(n_rays)) hipLaunchKernelGGL(composite_fwd_kernel<true>, team_grid16(n_rays), dim3(256), 0, as_stream(stream), sigmas, rgbs, t_starts,
-                       t_ends, packed_info, n_rays, weights, trans, alphas, opacity, distance, color, (float*)nullptr);
-    else hipLaunchKernelGGL(composite_fwd_kernel<false>, team_grid(n_rays), dim3(256), 0, as_stream(stream), sigmas, rgbs, t_starts,
-                       t_ends, packed_info, n_rays, weights, trans, alphas, opacity, distance, color, (float*)nullptr);
+    PERF_LAUNCH_TEAMS(composite_fwd_kernel, n_rays, stream, sigmas, rgbs, t_starts, t_ends, packed_info, n_rays, weights, trans, alphas,
+                      opacity, distance, color, (float*)nullptr);
     PERF_LAUNCH_CHECK("perf_composite_fwd");
     return PERF_OK;
 }
@@ -505,10 +435,8 @@ extern "C" int perf_composite_distloss_fwd(const float* sigmas, const float* rgb
     PERF_REQUIRE(n_rays >= 0, "n_rays < 0");
     if (n_rays == 0) return PERF_OK;
     PERF_REQUIRE(packed_info && distloss_per_ray, "NULL pointer");
-    if (team_by16(n_rays)) hipLaunchKernelGGL(composite_fwd_kernel<true>, team_grid16(n_rays), dim3(256), 0, as_stream(stream), sigmas, rgbs, t_starts,
-                       t_ends, packed_info, n_rays, weights, trans, (float*)nullptr, opacity, distance, color, distloss_per_ray);
-    else hipLaunchKernelGGL(composite_fwd_kernel<false>, team_grid(n_rays), dim3(256), 0, as_stream(stream), sigmas, rgbs, t_starts,
-                       t_ends, packed_info, n_rays, weights, trans, (float*)nullptr, opacity, distance, color, distloss_per_ray);
+    PERF_LAUNCH_TEAMS(composite_fwd_kernel, n_rays, stream, sigmas, rgbs, t_starts, t_ends, packed_info, n_rays, weights, trans, (float*)nullptr,
+                      opacity, distance, color, distloss_per_ray);
     PERF_LAUNCH_CHECK("perf_composite_distloss_fwd");
     return PERF_OK;
 }
@@ -622,7 +550,7 @@ __global__ __launch_bounds__(256) void visibility_count2_kernel(TwoSource src, i
         const int cnt = ch + ct;
         float carry = 0.f;
         int kept = 0;
-        for (int c0 = 0; c0 < cnt; c0 += 64) {
+        for (int c0 = 0; c0 < cnt; c0 += TW) {
             const int i = c0 + l;
             const bool valid = i < cnt;
             float sd = 0.f;
@@ -698,8 +626,7 @@ extern "C" int perf_visibility_count2(const float* sig_h, const float* ts_h, con
     if (n_rays == 0) return PERF_OK;
     PERF_REQUIRE(packed_h && packed_t && new_counts, "NULL pointer");
     perf::TwoSource src{sig_h, ts_h, te_h, packed_h, sig_t, ts_t, te_t, packed_t};
-    if (perf::team_by16(n_rays)) hipLaunchKernelGGL(perf::visibility_count2_kernel<true>, perf::team_grid16(n_rays), dim3(256), 0, perf::as_stream(stream), src, n_rays, thr, new_counts);
-    else hipLaunchKernelGGL(perf::visibility_count2_kernel<false>, perf::team_grid(n_rays), dim3(256), 0, perf::as_stream(stream), src, n_rays, thr, new_counts);
+    PERF_LAUNCH_TEAMS(perf::visibility_count2_kernel, n_rays, stream, src, n_rays, thr, new_counts);
     PERF_LAUNCH_CHECK("perf_visibility_count2");
     return PERF_OK;
 }
@@ -718,16 +645,10 @@ extern "C" int perf_compact_prefix2(const float* sig_h, const float* ts_h, const
     PERF_REQUIRE(packed_h && packed_t && new_counts && new_offsets && packed_out, "NULL pointer");
     PERF_REQUIRE(capacity == 0 || (ray_indices_out && ts_out && te_out), "NULL sample arrays");
     perf::TwoSource src{sig_h, ts_h, te_h, packed_h, sig_t, ts_t, te_t, packed_t};
-    if (perf::team_by16(n_rays)) hipLaunchKernelGGL(perf::compact_prefix2_kernel<true>, perf::team_grid16(n_rays), dim3(256), 0, perf::as_stream(stream), src, x01_h, sel_h,
-                       x01_t, sel_t, new_counts, new_offsets, n_rays, capacity, ray_indices_out, ts_out, te_out, sig_out, x01_out,
-                       sel_out, packed_out,
-                       perf::FeatCopy{(const uint32_t*)feat_h, feat_stride_h, (const uint32_t*)feat_t, feat_stride_t, (uint32_t*)feat_out,
-                                      feat_stride_out, n_levels});
-    else hipLaunchKernelGGL(perf::compact_prefix2_kernel<false>, perf::team_grid(n_rays), dim3(256), 0, perf::as_stream(stream), src, x01_h, sel_h,
-                       x01_t, sel_t, new_counts, new_offsets, n_rays, capacity, ray_indices_out, ts_out, te_out, sig_out, x01_out,
-                       sel_out, packed_out,
-                       perf::FeatCopy{(const uint32_t*)feat_h, feat_stride_h, (const uint32_t*)feat_t, feat_stride_t, (uint32_t*)feat_out,
-                                      feat_stride_out, n_levels});
+    PERF_LAUNCH_TEAMS(perf::compact_prefix2_kernel, n_rays, stream, src, x01_h, sel_h, x01_t, sel_t, new_counts, new_offsets, n_rays, capacity,
+                      ray_indices_out, ts_out, te_out, sig_out, x01_out, sel_out, packed_out,
+                      perf::FeatCopy{(const uint32_t*)feat_h, feat_stride_h, (const uint32_t*)feat_t, feat_stride_t, (uint32_t*)feat_out,
+                                     feat_stride_out, n_levels});
     PERF_LAUNCH_CHECK("perf_compact_prefix2");
     return PERF_OK;
 }
@@ -808,16 +729,12 @@ extern "C" int perf_pdf_resample(const float* s_in, const float* cdf, const floa
 namespace perf {
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
+    v = team_sum<64>(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     return red[0] + red[1] + red[2] + red[3];
 }
-
-// smooth_l1(x, beta): 0.5 x^2 / beta for |x| < beta else |x| - 0.5 beta;  derivative x/beta or sign(x)
-__device__ __forceinline__ float sl1(float x, float beta) { const float a = fabsf(x); return a < beta ? 0.5f * x * x / beta : a - 0.5f * beta; }
-__device__ __forceinline__ float sl1_grad(float x, float beta) { return fabsf(x) < beta ? x / beta : (x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f)); }
 
 // Loss heads: per-ray work is spread over kLossBlocks workgroups that leave their partial sums behind the results in
 // `scalars` (PERF_LOSS_SCALARS floats), a one-workgroup kernel then folds them in a fixed order (deterministic).
@@ -900,10 +817,9 @@ __global__ __launch_bounds__(256) void app_loss_kernel(const float* __restrict__
     float sum = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_rays * 3; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / 3;
-        const float c = color[i] + (bg ? bg[i] : 0.0f) * (1.0f - opacity[r]);
-        const float diff = c - gt[i];
-        sum += sl1(diff, 5e-2f);
-        g_col[i] = sl1_grad(diff, 5e-2f) * inv_n * color_w * loss_scale;
+        const AppHead h = app_head(color[i], bg ? bg[i] : 0.0f, 1.0f - opacity[r], gt[i], inv_n, color_w, loss_scale);
+        sum += h.term;
+        g_col[i] = h.g;
     }
     const float tot = block_sum_256(sum, red);
     if (threadIdx.x == 0) scalars[4 + blockIdx.x] = tot;
@@ -923,7 +839,9 @@ __global__ __launch_bounds__(64) void app_loss_final_kernel(int n_blocks, float 
 // distortion loss, flatten_eff_distloss's "last ray that holds a sample" -- which every wave finds for itself with one load
 // from the end of packed_info (a ballot over the last 64 rays; it walks further back only over rays without samples).  The
 // loss VALUES are reports: their per-ray terms are left in memory for the caller to sum when somebody asks.  Same arithmetic,
-// expression by expression, as composite_fwd_kernel (Team<64>) -> geo_loss_kernel / app_loss_kernel -> composite_bwd_kernel;
+// expression by expression, as composite_fwd_kernel (Team<64>) -> geo_loss_kernel / app_loss_kernel -> composite_bwd_kernel: the weights,
+// the distortion-loss term, the suffix scans and the colour head are the same functions of composite_device.hpp, the per-ray sums, the
+// geometry head and the backward chunk are written out here as there (shared, they compiled to other code: profiles/composite_stated_once.json);
 // the last chunk of the forward loop is the first of the backward loop and stays in registers.
 struct HeadLoss {
     const float* gt;            // geometry: distances [R]; colour: colours [R, 3]
@@ -998,9 +916,8 @@ __global__ __launch_bounds__(256) void train_head_kernel(const float* __restrict
             const float ex = team_chunk_excl<W>(sd, l, carry);
             float w_dl = 0.f, T = 0.f;
             if (valid) {
-                T = expf(-ex);
-                const float al = 1.0f - expf(-sd);
-                const float w = T * al;
+                float al, w;
+                ray_weight(ex, sd, T, al, w);
                 w_dl = w;
                 weights[start + i] = w;
                 trans[start + i] = T;
@@ -1014,9 +931,7 @@ __global__ __launch_bounds__(256) void train_head_kernel(const float* __restrict
             }
             if (!APP) {
                 const float m = (t0 + t1) * 0.5f, d = t1 - t0;
-                const float Wp = team_chunk_excl<W>(w_dl, l, cW);
-                const float WMp = team_chunk_excl<W>(w_dl * m, l, cWM);
-                if (valid) a_dl += d * w_dl * w_dl * (1.0f / 3.0f) + 2.0f * w_dl * (m * Wp - WMp);
+                distloss_chunk<W>(w_dl, m, d, valid, l, cW, cWM, a_dl);
             }
             w_l = w_dl; T_l = T; t0_l = t0; t1_l = t1; s_l = s;
         }
@@ -1049,10 +964,9 @@ __global__ __launch_bounds__(256) void train_head_kernel(const float* __restrict
             float g[3], term = 0.f;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                const float c = acc[k] + (hl.bg ? in_bg[k] : 0.0f) * om;
-                const float diff = c - in_gt[k];
-                term += sl1(diff, 5e-2f);
-                g[k] = sl1_grad(diff, 5e-2f) * hl.inv_bs * hl.w0 * hl.loss_scale;
+                const AppHead h = app_head(acc[k], hl.bg ? in_bg[k] : 0.0f, om, in_gt[k], hl.inv_bs, hl.w0, hl.loss_scale);
+                term += h.term;
+                g[k] = h.g;
             }
             gc0 = g[0]; gc1 = g[1]; gc2 = g[2];
             if (l == 0) terms[r] = term;
@@ -1076,23 +990,14 @@ __global__ __launch_bounds__(256) void train_head_kernel(const float* __restrict
             {
                 const float m = (t0 + t1) * 0.5f, wm = w * m;
                 float sw = w, swm = wm;
-#pragma unroll
-                for (int off = 1; off < W; off <<= 1) {
-                    const float y0 = __shfl_down(sw, off, W), y1 = __shfl_down(swm, off, W);
-                    if (l + off < W) { sw += y0; swm += y1; }
-                }
+                sw = team_suffix_incl<W>(sw, l); swm = team_suffix_incl<W>(swm, l);
                 const float Wsuf = sufW + (sw - w), WMsuf = sufWM + (swm - wm);
                 const float Wt = totW - Wsuf - w, WM = totWM - WMsuf - wm;
                 if (valid) G += dl_scale * ((2.0f / 3.0f) * (t1 - t0) * w + 2.0f * (m * (Wt - Wsuf) - (WM - WMsuf)));
                 sufW += __shfl(sw, 0, W); sufWM += __shfl(swm, 0, W);
             }
             const float qv = G * w;
-            float suf = qv;
-#pragma unroll
-            for (int off = 1; off < W; off <<= 1) {
-                const float y = __shfl_down(suf, off, W);
-                if (l + off < W) suf += y;
-            }
+            const float suf = team_suffix_incl<W>(qv, l);
             const float later = bcarry + (suf - qv);
             if (valid) {
                 const float delta = t1 - t0;
@@ -1104,13 +1009,17 @@ __global__ __launch_bounds__(256) void train_head_kernel(const float* __restrict
     // TEAMS = false (chosen by the host for batches whose sample arrays hold >= 32 rows per ray: the fixed-count benchmark step, the
     // first steps of an episode): a wavefront per ray and nothing else -- 50 registers and a third of the code; with the team shapes in the
     // same kernel (77 registers) rays of 128 samples took 7 % (geometry) / 35 % (colour) longer
-    if constexpr (TEAMS) {
-        for_rays_of_wave(n_rays, [&](int64_t q) { return packed[2 * q + 1]; }, head_of_ray);
-    } else {
-        const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-        if (r < n_rays) head_of_ray(Team<64>{}, r, (int)(threadIdx.x & 63));
-    }
+    if constexpr (TEAMS) for_rays_of_wave(n_rays, [&](int64_t q) { return packed[2 * q + 1]; }, head_of_ray);
+    else for_ray_of_wave(n_rays, [&](int64_t r, int lane) { head_of_ray(Team<64>{}, r, lane); });
 }
+
+// one argument list for the TEAMS and the wave-per-ray instantiation of a head
+#define PERF_LAUNCH_HEAD(APP, n_rays, sample_rows, stream, ...)                                                                       \
+    do {                                                                                                                               \
+        if (perf::head_by_teams(n_rays, sample_rows))                                                                                  \
+            hipLaunchKernelGGL((perf::train_head_kernel<APP, true>), perf::team_grid(n_rays), dim3(256), 0, perf::as_stream(stream), __VA_ARGS__);  \
+        else hipLaunchKernelGGL((perf::train_head_kernel<APP, false>), perf::ray_grid(n_rays), dim3(256), 0, perf::as_stream(stream), __VA_ARGS__); \
+    } while (0)
 
 }  // namespace perf
 
@@ -1154,14 +1063,8 @@ extern "C" int perf_train_head_geo(const float* sigmas, const float* rgbs, const
     PERF_REQUIRE(!rgbs || color, "perf_train_head_geo: rgbs without a colour output");
     perf::HeadLoss hl{gt_distance, noise, nullptr, ratio_dev, 1.0f / (float)global_batch, depth_weight, distortion_weight, loss_scale,
                       (int)(n_rays != global_batch)};
-    if (perf::head_by_teams(n_rays, sample_rows))
-        hipLaunchKernelGGL((perf::train_head_kernel<false, true>), perf::team_grid(n_rays), dim3(256), 0, perf::as_stream(stream), sigmas, rgbs, t_starts,
-                           t_ends, packed_info, n_rays, hl, weights, trans, opacity, distance, color, depth_terms, distloss_per_ray, inv_n_out,
-                           d_sigmas, (float*)nullptr);
-    else
-        hipLaunchKernelGGL((perf::train_head_kernel<false, false>), ray_grid(n_rays), dim3(256), 0, perf::as_stream(stream), sigmas, rgbs, t_starts,
-                           t_ends, packed_info, n_rays, hl, weights, trans, opacity, distance, color, depth_terms, distloss_per_ray, inv_n_out,
-                           d_sigmas, (float*)nullptr);
+    PERF_LAUNCH_HEAD(false, n_rays, sample_rows, stream, sigmas, rgbs, t_starts, t_ends, packed_info, n_rays, hl, weights, trans, opacity, distance,
+                     color, depth_terms, distloss_per_ray, inv_n_out, d_sigmas, (float*)nullptr);
     PERF_LAUNCH_CHECK("perf_train_head_geo");
     return PERF_OK;
 }
@@ -1174,14 +1077,8 @@ extern "C" int perf_train_head_app(const float* sigmas, const float* rgbs, const
     PERF_REQUIRE(sigmas && rgbs && t_starts && t_ends && packed_info && gt_color && weights && trans && opacity && distance && color &&
                  color_terms && d_rgbs, "NULL pointer");
     perf::HeadLoss hl{gt_color, nullptr, bg_color, nullptr, 1.0f / (float)(global_batch * 3), color_weight, 0.0f, loss_scale, 0};
-    if (perf::head_by_teams(n_rays, sample_rows))
-        hipLaunchKernelGGL((perf::train_head_kernel<true, true>), perf::team_grid(n_rays), dim3(256), 0, perf::as_stream(stream), sigmas, rgbs, t_starts,
-                           t_ends, packed_info, n_rays, hl, weights, trans, opacity, distance, color, color_terms, (float*)nullptr, (float*)nullptr,
-                           (float*)nullptr, d_rgbs);
-    else
-        hipLaunchKernelGGL((perf::train_head_kernel<true, false>), ray_grid(n_rays), dim3(256), 0, perf::as_stream(stream), sigmas, rgbs, t_starts,
-                           t_ends, packed_info, n_rays, hl, weights, trans, opacity, distance, color, color_terms, (float*)nullptr, (float*)nullptr,
-                           (float*)nullptr, d_rgbs);
+    PERF_LAUNCH_HEAD(true, n_rays, sample_rows, stream, sigmas, rgbs, t_starts, t_ends, packed_info, n_rays, hl, weights, trans, opacity, distance,
+                     color, color_terms, (float*)nullptr, (float*)nullptr, (float*)nullptr, d_rgbs);
     PERF_LAUNCH_CHECK("perf_train_head_app");
     return PERF_OK;
 }

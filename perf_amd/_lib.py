@@ -22,6 +22,7 @@ MESHVIS_ABI_VERSION = 1      # PERF_MESHVIS_ABI_VERSION of include/perf_hip_mesh
 MESHSIMP_ABI_VERSION = 1     # PERF_MESHSIMP_ABI_VERSION of include/perf_hip_meshsimp.h (simplify a mesh by vertex clustering)
 MESHCOLOR_ABI_VERSION = 1    # PERF_MESHCOLOR_ABI_VERSION of include/perf_hip_meshcolor.h (colour a mesh from the registered panoramas; normals from faces)
 MESHRAY_ABI_VERSION = 1      # PERF_MESHRAY_ABI_VERSION of include/perf_hip_meshray.h (rays against a mesh on a uniform grid: closest hit, any hit, occlusion)
+MESHTEX_ABI_VERSION = 1      # PERF_MESHTEX_ABI_VERSION of include/perf_hip_meshtex.h (a texture atlas for a mesh, baked from the registered panoramas)
 RIDERS_ABI_VERSION = 1       # PERF_RIDERS_ABI_VERSION of include/perf_hip_riders.h (the next batch's front end riding in the backward's launches)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
@@ -303,6 +304,22 @@ _SIGS_MESHRAY = {
     'perf_meshray_occluded': (c_int, _RAY_MESH + _RAY_BOX + [P, P, c_int64, P, c_int32, P, P, P]),
 }
 
+# include/perf_hip_meshtex.h: a texture atlas for a mesh: corner UVs, the texel -> point map, the fused bake (perf_meshtex_version)
+MESHTEX_MIN_SIZE = 64                # PERF_MESHTEX_MIN_SIZE
+MESHTEX_MAX_SIZE = 16384             # PERF_MESHTEX_MAX_SIZE
+MESHTEX_MIN_TILE = 4                 # PERF_MESHTEX_MIN_TILE
+MESHTEX_MAX_VIEWS = 64               # PERF_MESHTEX_MAX_VIEWS
+MESHTEX_MAX_VERTICES = 1 << 30       # PERF_MESHTEX_MAX_VERTICES
+MESHTEX_MAX_POWER = 8                # PERF_MESHTEX_MAX_POWER
+MESHTEX_COVER = {'none': 0, 'inside': 1, 'gutter': 2}               # PERF_MESHTEX_COVER_*
+_TEX_MESH = [P, c_int64, P, P, c_int64, c_int32, c_int32]             # vertices, n_vertices, normals, faces, n_faces, size, tile
+_SIGS_MESHTEX = {
+    'perf_meshtex_version': (c_int, []),
+    'perf_meshtex_uv': (c_int, [c_int64, c_int32, c_int32, P, P]),
+    'perf_meshtex_points': (c_int, _TEX_MESH + [P, P, P, P, P, P]),
+    'perf_meshtex_bake': (c_int, _TEX_MESH + [P, P, POINTER(c_int32), c_int32, c_float, c_int32, c_int32, c_int32, P, POINTER(c_float), P, P, P, P, P, P]),
+}
+
 # include/perf_hip_riders.h: the step riders, exported from the same library, versioned on their own (perf_riders_version)
 RIDER_THREADS = 256          # PERF_RIDER_THREADS
 RIDER_DRAW_RAYS = 256        # PERF_RIDER_DRAW_RAYS
@@ -340,6 +357,7 @@ _UNITS = (
     (_SIGS_MESHSIMP, 'perf_meshsimp_version', MESHSIMP_ABI_VERSION, _expects('mesh-simplification ABI'), ()),
     (_SIGS_MESHCOLOR, 'perf_meshcolor_version', MESHCOLOR_ABI_VERSION, _expects('mesh-colouring ABI'), ()),
     (_SIGS_MESHRAY, 'perf_meshray_version', MESHRAY_ABI_VERSION, _expects('mesh ray-casting ABI'), ()),
+    (_SIGS_MESHTEX, 'perf_meshtex_version', MESHTEX_ABI_VERSION, _expects('texture-atlas ABI'), ()),
     (_SIGS_RIDERS, 'perf_riders_version', RIDERS_ABI_VERSION, 'step-rider ABI version {has} or other argument blocks than this binding ({want})',
      (('perf_sizeof_rider_draw', ctypes.sizeof(RiderDraw)), ('perf_sizeof_rider_count', ctypes.sizeof(RiderCount)),
       ('perf_sizeof_rider_write', ctypes.sizeof(RiderWrite)))),

@@ -546,7 +546,7 @@ def panorama_colors(vertices, views, normals=None, tol=1 / 256, facing=True, pow
     vertex_visibility: dist < stored + tol) and, with facing, the normal points at the view's centre.  It is weighted by
     cos^power / dist^2 (facing) or 1 / dist^2: a panorama pixel's footprint on the surface grows as dist^2 / cos.  select='blend': the
     weighted mean; 'best': the colour of the view with the largest weight.  Where no view passes: the fallback row [V, 3] if given, else
-    fill.  No occlusion test against the mesh itself, no texture atlas (colours are per vertex), no exposure matching between views, no
+    fill.  No occlusion test against the mesh itself, no texture atlas here (colours are per vertex: bake_panorama_texture bakes one), no exposure matching between views, no
     wrap at the seam; more than 64 views are refused.  No host read."""
     if not torch.is_tensor(vertices) or not vertices.is_cuda:
         raise _lib.PerfError('panorama_colors: vertices must be a CUDA tensor (there is no CPU path)')
@@ -579,6 +579,180 @@ def color_from_panoramas(mesh, views, normals='faces', **kw) -> Mesh:
             weigh_by = face_normals(mesh, box)
     kw.setdefault('fallback', mesh.colors)
     return Mesh(mesh.vertices, mesh.faces, panorama_colors(mesh.vertices, views, weigh_by, **kw).colors, mesh.normals)
+
+
+# ---- a texture atlas: as many colour samples as the panoramas hold on a mesh of any size (include/perf_hip_meshtex.h) -------------------
+class Atlas(NamedTuple):
+    size: int                                    # S: the atlas is S x S texels
+    tile: int                                    # T: a tile of T x T texels holds two faces
+    uv: torch.Tensor                             # [F, 3, 2] fp32: (u, v) of each face's corners a, b, c; v grows with the row index
+    image: torch.Tensor                          # [S, S, 3] fp32: texel (column i, row j) at image[j, i]
+    coverage: torch.Tensor                       # [S, S] uint8: 0 no face, 1 inside its face's triangle, 2 gutter
+    weight: torch.Tensor                         # [S, S] fp32: the blend's weight, 0 where no view passed
+    used: torch.Tensor                           # [S, S] int64: bit k set iff view k's colour went into the texel
+
+
+def _atlas_capacity(size, tile):
+    return 2 * (size // tile) ** 2
+
+
+def atlas_layout(n_faces, size=None, tile=None):
+    """(size, tile) of an atlas that holds n_faces faces, two per tile (capacity 2 (size // tile)^2).  Given size: the largest tile that
+    fits; given tile (neither: 8): the smallest power-of-two size in 64 .. 16384; given both: checked.  What does not fit is refused."""
+    f = int(n_faces)
+    if f < 0:
+        raise _lib.PerfError(f'atlas_layout: a negative number of faces ({f})')
+    lo, hi, least = _lib.MESHTEX_MIN_SIZE, _lib.MESHTEX_MAX_SIZE, _lib.MESHTEX_MIN_TILE
+    if size is not None:
+        size = int(size)
+        if not lo <= size <= hi:
+            raise _lib.PerfError(f'atlas_layout: an atlas size of {size} is outside {lo} .. {hi}')
+    if tile is not None:
+        tile = int(tile)
+        if tile < least or tile > (hi if size is None else size):
+            raise _lib.PerfError(f'atlas_layout: a tile of {tile} texels is outside {least} .. {hi if size is None else size}')
+    if size is not None and tile is None:
+        per_row = max(1, math.isqrt((f + 1) // 2))          # the smallest n with 2 n^2 >= f
+        per_row += 2 * per_row * per_row < f
+        tile = size // per_row
+        if tile < least:
+            raise _lib.PerfError(f'atlas_layout: {f} faces do not fit an atlas of {size}: it holds {_atlas_capacity(size, least)} at tiles of {least} texels')
+    elif size is None:
+        tile = 8 if tile is None else tile
+        size = lo
+        while size < hi and (size < tile or _atlas_capacity(size, tile) < f):
+            size *= 2
+    if size < tile or _atlas_capacity(size, tile) < f:
+        raise _lib.PerfError(f'atlas_layout: {f} faces are more than the {_atlas_capacity(size, tile) if size >= tile else 0} an atlas of {size} with tiles of {tile} holds')
+    return size, tile
+
+
+def atlas_uv(n_faces, size, tile, device='cuda') -> torch.Tensor:
+    """The corner UVs fp32 [F, 3, 2] of the layout: each face's corners sit on texel centres, (i + 0.5) / size."""
+    return ops.meshtex_uv(n_faces, size, tile, device)
+
+
+def _atlas_normals(who, mesh, normals, box=None):
+    if normals not in ('flat', 'faces', 'mesh'):
+        raise _lib.PerfError(f"{who}: normals is 'flat', 'faces' or 'mesh', got {normals!r}")
+    if normals == 'mesh':
+        if mesh.normals is None:
+            raise _lib.PerfError(f"{who}: normals='mesh' needs mesh.normals: extract them, or use normals='flat' or 'faces'")
+        return mesh.normals.contiguous()
+    return face_normals(mesh, box) if normals == 'faces' else None
+
+
+def atlas_points(mesh, size, tile, normals='flat'):
+    """The texel -> point map of the atlas, materialised -> (points fp32 [S * S, 3], point_normals fp32 [S * S, 3], face_of int32 [S * S],
+    coverage uint8 [S * S]); texel (column i, row j) at element j S + i.  A texel's point is (a + beta (b - a)) + gamma (c - a) of its
+    face, extrapolated (not clamped) in the gutter.  normals='flat': the face's own unit normal; 'faces': face_normals' vertex normals
+    interpolated (not normalised); 'mesh': mesh.normals interpolated.  One host read: the flag of a face index outside [0, V), refused."""
+    _check_mesh('atlas_points', mesh)
+    vertices, faces = mesh.vertices.contiguous(), mesh.faces.contiguous()
+    points, point_normals, face_of, coverage, flag = ops.meshtex_points(vertices, faces, size, tile, _atlas_normals('atlas_points', mesh, normals))
+    bad = int(flag.item())          # the one host synchronisation
+    if bad >= 0:
+        _raise_bad_face('atlas_points', faces, bad, vertices.shape[0])
+    return points, point_normals, face_of, coverage
+
+
+def bake_panorama_texture(mesh, views, size=None, tile=None, normals='flat', **kw) -> Atlas:
+    """A texture atlas of the mesh baked from the registered panoramas in ONE launch: every texel's point goes through the blend of
+    panorama_colors (its keywords: tol, facing, power, select, fill; box for normals='faces'), so a mesh of any size carries as many colour
+    samples as the atlas has texels.  The layout is atlas_layout's.  mesh.colors, when present, is the fallback of the texels no view
+    passed for, interpolated over the face.  Every face gets the same texel budget (no area-proportional charts, no chart merging), no
+    mip-safe padding between tiles, no exposure matching, at most 64 views.  One host read: the flag of a face index outside [0, V)."""
+    _check_mesh('bake_panorama_texture', mesh)
+    vertices, faces = mesh.vertices.contiguous(), mesh.faces.contiguous()
+    size, tile = atlas_layout(faces.shape[0], size, tile)
+    box = kw.pop('box', None)
+    tol, facing, power, select = kw.pop('tol', 1 / 256), kw.pop('facing', True), kw.pop('power', 2), kw.pop('select', 'blend')
+    fallback, fill = kw.pop('fallback', mesh.colors), kw.pop('fill', (0.5, 0.5, 0.5))
+    if kw:
+        raise _lib.PerfError(f'bake_panorama_texture: unknown keywords {sorted(kw)}')
+    if select not in _lib.MESHCOLOR_SELECT:
+        raise _lib.PerfError(f"bake_panorama_texture: select is 'blend' or 'best', got {select!r}")
+    if facing and not 1 <= int(power) <= _lib.MESHTEX_MAX_POWER:
+        raise _lib.PerfError(f'bake_panorama_texture: power {power} is outside 1 .. {_lib.MESHTEX_MAX_POWER}')
+    if normals not in ('flat', 'faces', 'mesh'):
+        raise _lib.PerfError(f"bake_panorama_texture: normals is 'flat', 'faces' or 'mesh', got {normals!r}")
+    weigh_by = _atlas_normals('bake_panorama_texture', mesh, normals, box) if facing else None          # (the normals are read only with facing)
+    cv = _color_views('bake_panorama_texture', views)
+    image, weight, used, coverage, flag = ops.meshtex_bake(vertices, faces, size, tile, cv.views.table, cv.views.sizes, cv.pointers, float(tol), weigh_by, facing, power,
+                                                           select, fallback.contiguous() if fallback is not None else None, fill)
+    uv = ops.meshtex_uv(faces.shape[0], size, tile, faces.device)
+    bad = int(flag.item())          # the one host synchronisation
+    if bad >= 0:
+        _raise_bad_face('bake_panorama_texture', faces, bad, vertices.shape[0])
+    return Atlas(size, tile, uv, image, coverage, weight, used)
+
+
+def bake_field_texture(scene, mesh, size=None, tile=None, fill=(0.5, 0.5, 0.5)) -> Atlas:
+    """A texture atlas of the mesh from the field's own colours: vertex_colors at the covered texels' points (atlas_points); texels of no
+    face take fill.  weight is 1 at the covered texels, used is 0."""
+    _check_mesh('bake_field_texture', mesh)
+    size, tile = atlas_layout(mesh.faces.shape[0], size, tile)
+    points, _, _, coverage = atlas_points(mesh, size, tile)
+    covered = coverage != 0
+    image = torch.tensor([float(v) for v in fill], dtype=torch.float32, device=points.device).repeat(size * size, 1)
+    image[covered] = vertex_colors(scene, points[covered].contiguous())
+    uv = ops.meshtex_uv(mesh.faces.shape[0], size, tile, points.device)
+    return Atlas(size, tile, uv, image.view(size, size, 3), coverage.view(size, size), covered.float().view(size, size),
+                 torch.zeros(size, size, dtype=torch.int64, device=points.device))
+
+
+def sample_atlas(atlas, face_ids, bary) -> torch.Tensor:
+    """The atlas' colour at points of the mesh's faces, bilinear, in torch (float64) -> [N, 3] float64.  face_ids [N] integers; bary
+    [N, 3]: the weights (alpha, beta, gamma) of the face's corners a, b, c.  The texture coordinate is the corners' uv weighted by bary;
+    the texel centre (i, j) sits at (u, v) S - 0.5; taps are clamped to the image."""
+    s = int(atlas.size)
+    corner = atlas.uv.double()[face_ids.long()] * s - 0.5                                   # [N, 3, 2]: the corners in texel units
+    xy = (bary.double().to(corner.device)[:, :, None] * corner).sum(dim=1)
+    x, y = xy[:, 0], xy[:, 1]
+    x0, y0 = torch.floor(x), torch.floor(y)
+    fx, fy = x - x0, y - y0
+    image = atlas.image.double()
+    at = lambda yy, xx: image[yy.long().clamp(0, s - 1), xx.long().clamp(0, s - 1)]
+    top = at(y0, x0) * (1 - fx)[:, None] + at(y0, x0 + 1) * fx[:, None]
+    bottom = at(y0 + 1, x0) * (1 - fx)[:, None] + at(y0 + 1, x0 + 1) * fx[:, None]
+    return top * (1 - fy)[:, None] + bottom * fy[:, None]
+
+
+def atlas_image_u8(atlas) -> np.ndarray:
+    """The atlas' image as a file holds it: uint8 [S, S, 3], clipped to [0, 1], ROW S - 1 FIRST (OBJ's v points up)."""
+    image = np.nan_to_num(atlas.image.detach().cpu().numpy().astype(np.float64), nan=0.0)
+    return np.ascontiguousarray(np.rint(np.clip(image, 0.0, 1.0) * 255.0).astype(np.uint8)[::-1])
+
+
+def write_obj(path, mesh, atlas):
+    """Wavefront OBJ + MTL + the atlas' image beside it -> the image's path.  Three `vt` per face and `f a/ta b/tb c/tc`; the image is
+    8-bit, clipped, row S - 1 first; PNG through PIL when it imports, binary PPM otherwise."""
+    import os
+    v = mesh.vertices.detach().cpu().numpy().astype(np.float64)
+    f = mesh.faces.detach().cpu().numpy().astype(np.int64)
+    uv = atlas.uv.detach().cpu().numpy().astype(np.float64).reshape(-1, 2)
+    if len(uv) != 3 * len(f):
+        raise _lib.PerfError(f'write_obj: the atlas holds the corners of {len(uv) // 3} faces, the mesh has {len(f)}')
+    stem = os.path.splitext(path)[0]
+    pixels = atlas_image_u8(atlas)
+    try:
+        from PIL import Image
+        image_path = stem + '.png'
+        Image.fromarray(pixels, 'RGB').save(image_path)
+    except ImportError:
+        image_path = stem + '.ppm'
+        with open(image_path, 'wb') as out:
+            out.write(f'P6\n{pixels.shape[1]} {pixels.shape[0]}\n255\n'.encode('ascii'))
+            out.write(pixels.tobytes())
+    with open(stem + '.mtl', 'w') as out:
+        out.write(f'newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 0\nmap_Kd {os.path.basename(image_path)}\n')
+    lines = [f'mtllib {os.path.basename(stem)}.mtl', 'usemtl atlas']
+    lines += ['v %.9g %.9g %.9g' % tuple(row) for row in v]
+    lines += ['vt %.9g %.9g' % tuple(row) for row in uv]
+    lines += ['f %d/%d %d/%d %d/%d' % (a + 1, 3 * i + 1, b + 1, 3 * i + 2, c + 1, 3 * i + 3) for i, (a, b, c) in enumerate(f)]
+    with open(path, 'w') as out:
+        out.write('\n'.join(lines) + '\n')
+    return image_path
 
 
 # ---- rays against the mesh itself: closest hit, any hit, occlusion-aware cull (include/perf_hip_meshray.h) ------------------------------

@@ -1282,6 +1282,85 @@ def meshcolor_blend(vertices, normals, views, sizes, map_pointers, tol, facing=T
     return colors, weight, used, best
 
 
+# ---- a texture atlas for a mesh: corner UVs, the texel -> point map, the fused bake (include/perf_hip_meshtex.h) ------------------------
+def _tex_layout(who, n_faces, size, tile):
+    s, t, f = int(size), int(tile), int(n_faces)
+    if not _lib.MESHTEX_MIN_SIZE <= s <= _lib.MESHTEX_MAX_SIZE:
+        raise _lib.PerfError(f'{who}: an atlas size of {s} is outside 64 .. 16384')
+    if not _lib.MESHTEX_MIN_TILE <= t <= s:
+        raise _lib.PerfError(f'{who}: a tile of {t} texels is outside 4 .. {s}')
+    if f < 0 or f > 2 * (s // t) ** 2:
+        raise _lib.PerfError(f'{who}: {f} faces are more than the {2 * (s // t) ** 2} an atlas of {s} with tiles of {t} holds')
+    return s, t
+
+
+def _tex_mesh(who, vertices, normals, faces, size, tile):
+    vertices, nv = _simp_vertices(who, vertices)
+    _, f = _cc_faces(who, faces, nv)
+    if faces.device != vertices.device:
+        raise _lib.PerfError(f'{who}: faces must be on the vertices\' device')
+    s, t = _tex_layout(who, f, size, tile)
+    normals = _cc_vertices(who, normals, nv, vertices.device)
+    return vertices, nv, f, s, t, (_p(vertices) if nv else None, nv, _p(normals) if normals is not None and nv else None, _p(faces) if f else None, f, s, t)
+
+
+def meshtex_uv(n_faces, size, tile, device='cuda'):
+    """The corner UVs fp32 [F, 3, 2] of the atlas layout of include/perf_hip_meshtex.h (perf_meshtex_uv)."""
+    f = int(n_faces)
+    s, t = _tex_layout('meshtex_uv', f, size, tile)
+    if torch.device(device).type != 'cuda':
+        raise _lib.PerfError('meshtex_uv: device must be a CUDA device (there is no CPU path)')
+    uv = torch.empty(f, 3, 2, dtype=torch.float32, device=device)
+    _call('perf_meshtex_uv', f, s, t, _p(uv) if f else None, _stream())
+    return uv
+
+
+def meshtex_points(vertices, faces, size, tile, normals=None, flag=None):
+    """The texels' points of the atlas (perf_meshtex_points) -> (points fp32 [S * S, 3], point_normals fp32 [S * S, 3], face_of int32
+    [S * S], coverage uint8 [S * S], flag): normals fp32 [V, 3] are interpolated, None takes the faces' own; flag = int64 [1] ON THE DEVICE,
+    the smallest index of a face with an index outside [0, V) or -1 (an int64 [1] view to write it into may be passed)."""
+    vertices, nv, f, s, t, head = _tex_mesh('meshtex_points', vertices, normals, faces, size, tile)
+    dev = vertices.device
+    points = torch.empty(s * s, 3, dtype=torch.float32, device=dev)
+    point_normals = torch.empty(s * s, 3, dtype=torch.float32, device=dev)
+    face_of = torch.empty(s * s, dtype=torch.int32, device=dev)
+    coverage = torch.empty(s * s, dtype=torch.uint8, device=dev)
+    if flag is None:
+        flag = torch.empty(1, dtype=torch.int64, device=dev)
+    _call('perf_meshtex_points', *head, _p(points), _p(point_normals), _p(face_of), _p(coverage), _p(flag), _stream())
+    return points, point_normals, face_of, coverage, flag
+
+
+def meshtex_bake(vertices, faces, size, tile, views, sizes, map_pointers, tol, normals=None, facing=True, power=2, select='blend', fallback=None,
+                 fill=(0.5, 0.5, 0.5), flag=None):
+    """The fused bake (perf_meshtex_bake): the texels' points through the blend of include/perf_hip_meshcolor.h in ONE launch -> (image fp32
+    [S, S, 3], weight fp32 [S, S], used_bits int64 [S, S], coverage uint8 [S, S], flag).  views, sizes, map_pointers: of meshvis_views and
+    meshcolor_maps; normals, fallback: fp32 [V, 3] or None."""
+    vertices, nv, f, s, t, head = _tex_mesh('meshtex_bake', vertices, normals, faces, size, tile)
+    dev, k = vertices.device, len(sizes)
+    if tuple(views.shape) != (k, 16) or views.dtype != torch.int32 or (k and views.device != dev) or not views.is_contiguous():
+        raise _lib.PerfError(f'meshtex_bake: views must be the contiguous int32 [{k}, 16] tensor of meshvis_views on the vertices\' device')
+    if tuple(map_pointers.shape) != (k,) or map_pointers.dtype != torch.int64 or (k and map_pointers.device != dev):
+        raise _lib.PerfError(f'meshtex_bake: map_pointers must be the int64 [{k}] tensor of meshcolor_maps on the vertices\' device')
+    if select not in _lib.MESHCOLOR_SELECT:
+        raise _lib.PerfError(f"meshtex_bake: select is 'blend' or 'best', got {select!r}")
+    fallback = _cc_vertices('meshtex_bake', fallback, nv, dev)
+    fill3 = [float(v) for v in fill]
+    if len(fill3) != 3:
+        raise _lib.PerfError('meshtex_bake: fill holds three values')
+    image = torch.empty(s, s, 3, dtype=torch.float32, device=dev)
+    weight = torch.empty(s, s, dtype=torch.float32, device=dev)
+    used = torch.empty(s, s, dtype=torch.int64, device=dev)
+    coverage = torch.empty(s, s, dtype=torch.uint8, device=dev)
+    if flag is None:
+        flag = torch.empty(1, dtype=torch.int64, device=dev)
+    flat = (ctypes.c_int32 * (2 * k))(*[v for hw in sizes for v in hw]) if k else None
+    _call('perf_meshtex_bake', *head, _p(views) if k else None, _p(map_pointers) if k else None, flat, k, float(tol), int(bool(facing)), int(power),
+          _lib.MESHCOLOR_SELECT[select], _p(fallback) if fallback is not None and nv else None, (ctypes.c_float * 3)(*fill3), _p(image), _p(weight), _p(used),
+          _p(coverage), _p(flag), _stream())
+    return image, weight, used, coverage, flag
+
+
 # ---- rays against a mesh on a uniform grid: closest hit, any hit, segment occlusion (include/perf_hip_meshray.h) -------------------------
 def _ray_mesh(who, vertices, faces):
     vertices, nv = _simp_vertices(who, vertices)

@@ -1700,6 +1700,16 @@ class NeRFScene:
         kw.setdefault('box', (aabb[:3], aabb[3:]))
         return color_from_panoramas(mesh, sup_pool, **kw)
 
+    def bake_mesh_texture(self, mesh, sup_pool=None, **kw):
+        """A texture atlas of the mesh: from sup_pool's registered panoramas when a pool is given (perf_amd/mesh.py:
+        bake_panorama_texture's keywords), from the field's own colours otherwise (bake_field_texture's) -> mesh.Atlas."""
+        from .mesh import bake_field_texture, bake_panorama_texture
+        if sup_pool is None:
+            return bake_field_texture(self, mesh, **kw)
+        aabb = [float(v) for v in self.nerf._aabb_host]
+        kw.setdefault('box', (aabb[:3], aabb[3:]))
+        return bake_panorama_texture(mesh, sup_pool, **kw)
+
     def cull_occluded_mesh(self, mesh, sup_pool, **kw):
         """mesh without the faces none of sup_pool's registered panoramas saw, the mesh's own occlusion included (perf_amd/mesh.py:
         cull_occluded's keywords) -> mesh.Mesh."""

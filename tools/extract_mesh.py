@@ -1,10 +1,11 @@
-"""Write the trained density as a triangle mesh (binary PLY): trains the synthetic room, or loads a checkpoint of NeRFScene.state_dict().
+"""Write the trained density as a triangle mesh (binary PLY; with --texture, OBJ + MTL + the atlas image): trains the synthetic room, or loads a checkpoint of NeRFScene.state_dict().
 
   python tools/extract_mesh.py --out room.ply [--resolution 256] [--threshold T] [--no-occupancy] [--no-colors] [--no-normals] [--sparse]
                                [--seen-by-panoramas [--occlusion] [--visibility-tol T] [--carve] [--sup-pool pool.pt]]
                                [--min-component-faces N] [--keep-largest K] [--orientation inward|outward]
                                [--simplify-cell H [--simplify-placement mean|member] [--simplify-dedupe oriented|unoriented|none]]
                                [--colors-from-panoramas [--color-select blend|best] [--color-power N] [--sup-pool pool.pt]]
+                               [--texture SIZE [--texture-source panoramas|field] [--texture-tile T]]
                                [--checkpoint scene.pt | --geo 3000 --app 1500] [--dtype fp16]
 
 Prints one JSON line: the counts, the threshold and the seconds of training and extraction."""
@@ -13,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from perf_amd import synthetic
-from perf_amd.mesh import write_ply
+from perf_amd.mesh import write_obj, write_ply
 from perf_amd.scene import NeRFScene, SupInfoPool, gen_pano_rays
 
 ap = argparse.ArgumentParser()
@@ -46,6 +47,11 @@ ap.add_argument('--colors-from-panoramas', action='store_true',
                      'cos^N / dist^2 over the views that saw a vertex (the field\'s colours stay where none did)')
 ap.add_argument('--color-select', choices=['blend', 'best'], default='blend', help='with --colors-from-panoramas: the weighted mean of the views, or the best view alone')
 ap.add_argument('--color-power', type=int, default=2, help='with --colors-from-panoramas: the power N of the incidence cosine, 1 .. 8')
+ap.add_argument('--texture', type=int, default=None, metavar='SIZE',
+                help='after the simplification: bake a SIZE x SIZE texture atlas (two faces per tile) and write --out as OBJ + MTL + image, not PLY')
+ap.add_argument('--texture-source', choices=['panoramas', 'field'], default='panoramas',
+                help='with --texture: the registered panoramas blended as --colors-from-panoramas blends them at every texel, or the field\'s own colours')
+ap.add_argument('--texture-tile', type=int, default=None, help='with --texture: the tile edge in texels (default: the largest that holds the faces)')
 ap.add_argument('--checkpoint', default=None, help='a torch.save of NeRFScene.state_dict()')
 ap.add_argument('--geo', type=int, default=3000)
 ap.add_argument('--app', type=int, default=1500)
@@ -57,7 +63,7 @@ torch.manual_seed(0); np.random.seed(0)
 scene = NeRFScene(dtype=args.dtype)
 t0 = time.perf_counter()
 views = None          # --seen-by-panoramas: the registered panoramas the mesh is tested against
-with_views = args.seen_by_panoramas or args.colors_from_panoramas
+with_views = args.seen_by_panoramas or args.colors_from_panoramas or (args.texture is not None and args.texture_source == 'panoramas')
 if with_views and args.checkpoint and not args.sup_pool:
     ap.error('--seen-by-panoramas and --colors-from-panoramas with --checkpoint need the panoramas: --sup-pool FILE, a torch.save of SupInfoPool.state_dict()')
 if args.checkpoint:
@@ -96,7 +102,18 @@ if args.colors_from_panoramas:          # on the fine vertices, which lie on the
 cleaned = {'cleaned_vertices': len(mesh.vertices), 'cleaned_faces': len(mesh.faces)} if args.simplify_cell is not None else {}
 if args.simplify_cell is not None:          # last: the cull and the cleaning have seen the mesh as it was extracted
     mesh = scene.simplify_mesh(mesh, args.simplify_cell, placement=args.simplify_placement, dedupe=None if args.simplify_dedupe == 'none' else args.simplify_dedupe)
+textured = {}
+if args.texture is not None:          # after the simplification: the small mesh carries as many colour samples as the atlas has texels
+    if args.texture_source == 'panoramas':
+        atlas = scene.bake_mesh_texture(mesh, views, size=args.texture, tile=args.texture_tile, tol=args.visibility_tol, select=args.color_select, power=args.color_power)
+    else:
+        atlas = scene.bake_mesh_texture(mesh, None, size=args.texture, tile=args.texture_tile)
+    textured = {'texture': atlas.size, 'texture_tile': atlas.tile, 'texture_source': args.texture_source}
 torch.cuda.synchronize(); t3 = time.perf_counter()
-write_ply(args.out, mesh)
+if args.texture is not None:
+    args.out = os.path.splitext(args.out)[0] + '.obj'
+    textured['texture_image'] = write_obj(args.out, mesh, atlas)
+else:
+    write_ply(args.out, mesh)
 print(json.dumps({'out': args.out, 'vertices': len(mesh.vertices), 'faces': len(mesh.faces), 'resolution': args.resolution, 'sparse': args.sparse,
-                  'threshold': args.threshold, 'extracted_vertices': extracted[0], 'extracted_faces': extracted[1], **seen, **cleaned, 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'clean_s': t3 - t2, 'bytes': os.path.getsize(args.out)}))
+                  'threshold': args.threshold, 'extracted_vertices': extracted[0], 'extracted_faces': extracted[1], **seen, **cleaned, **textured, 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'clean_s': t3 - t2, 'bytes': os.path.getsize(args.out)}))

@@ -1,6 +1,11 @@
 """CPU tests (no GPU) of the integer oracle of the fixed-point table gradient (oracle/perf_oracle.py:grid_fixed_fields): against a
-float64 sum of the same contributions, for rounding bias, for order and partition independence, and the overlap fold.  The GPU tests
-(tests/test_gpu_exact_gradients.py) demand equality with it to the bit, so it has to be right on its own."""
+float64 sum of the same contributions, for rounding bias, for order and partition independence, and the overlap fold; its corner
+indices and its association rule against a slow restatement in Python integers on levels with res + 2 >= 16384 and on positions
+outside the unit cube.  The GPU tests (tests/test_gpu_exact_gradients.py, tests/test_gpu_exact_gradients_large.py) demand equality
+with it to the bit, so it has to be right on its own."""
+import math
+from fractions import Fraction
+
 import numpy as np
 import torch
 
@@ -126,6 +131,147 @@ def test_the_two_associations_differ_and_each_is_what_it_says():
     _, w = O.grid_fixed_weights(xo, lv, 12)
     _, f = O.grid_corner_indices(xo, lv, 12)
     assert np.array_equal(w[:, 2], ((F32(1) - f[:, 0]) * f[:, 1]) * (F32(1) - f[:, 2]))
+
+
+# ---- the input classes of tests/test_gpu_exact_gradients_large.py: res + 2 >= 16384, positions outside the unit cube -----------------
+def _outside_batch(n, seed):
+    """uniform points, a share of them outside the unit cube on every side (the 'outside' batch of the GPU tests)"""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.rand(n, 3, generator=g)
+    x[::7, 0] = -0.25
+    x[5::11, 0] = 9.5
+    x[3::13, 1] = -3.0
+    x[4::17, 2] = 1.75
+    return x.numpy()
+
+
+def _fl32(v: Fraction) -> Fraction:
+    """a rational rounded to the nearest fp32 number, ties to even (normal and subnormal range), in integer arithmetic"""
+    if v == 0:
+        return v
+    s, a = (-1 if v < 0 else 1), abs(v)
+    e = a.numerator.bit_length() - a.denominator.bit_length()
+    if Fraction(2) ** e > a:
+        e -= 1
+    assert Fraction(2) ** e <= a < Fraction(2) ** (e + 1)
+    quantum = Fraction(2) ** (max(e, -126) - 23)
+    q = a / quantum
+    k = q.numerator // q.denominator
+    rest = q - k
+    if rest > Fraction(1, 2) or (rest == Fraction(1, 2) and k % 2 == 1):
+        k += 1
+    return s * k * quantum
+
+
+def _slow_corners(x, lv, level):
+    """grid_corner_indices and the pair flag of grid_fixed_weights once more, one sample at a time: Python integers for the cell, the
+    hash and the wrap, % for the dense modulo, math.floor, and the fma of the grid position as a rational rounded once"""
+    M = 0xFFFFFFFF
+    scale = Fraction(float(lv.scale[level]))
+    res, size, hashed = int(lv.res[level]), int(lv.size[level]), bool(lv.hashed[level])
+    idx, frac, pair, cells = [], [], [], []
+    for p in x:
+        pos = [_fl32(Fraction(float(F32(c))) * scale + Fraction(1, 2)) for c in p]
+        cell = [math.floor(v) for v in pos]
+        frac.append([float(v - c) for v, c in zip(pos, cell)])          # (exact: both are fp32 numbers of one binade or less)
+        u = [c & M for c in cell]                                          # (uint32)(int32) of the kernels: two's complement
+        row = []
+        for c in range(8):
+            cx, cy, cz = (u[0] + (c & 1)) & M, (u[1] + ((c >> 1) & 1)) & M, (u[2] + (c >> 2)) & M
+            if hashed:
+                h = cx ^ ((cy * 2654435761) & M) ^ ((cz * 805459861) & M)
+            else:
+                h = (cx + cy * res + cz * res * res) & M
+            row.append(h % size)
+        idx.append(row)
+        pair.append(hashed and u[0] < 16383)
+        cells.append(cell)
+    return np.array(idx, np.int64), np.array(frac, np.float64), np.array(pair), cells
+
+
+def _both_associations(f):
+    one = (F32(1.0) - f).astype(F32)
+    generic, paired = np.zeros((f.shape[0], 8), F32), np.zeros((f.shape[0], 8), F32)
+    for c in range(8):
+        wx, wy, wz = (f[:, 0] if c & 1 else one[:, 0]), (f[:, 1] if c & 2 else one[:, 1]), (f[:, 2] if c & 4 else one[:, 2])
+        generic[:, c] = ((wx * wy).astype(F32) * wz).astype(F32)
+        paired[:, c] = (wx * (wy * wz).astype(F32)).astype(F32)
+    return generic, paired
+
+
+# the three finest levels of the GPU tests' fine grids (res 8192, 16384, 32768; all hashed), and a coarse grid with two dense levels
+FINE = dict(n_levels=3, log2_hashmap_size=14, base_resolution=8192, per_level_scale=2.0)
+COARSE = dict(n_levels=3, log2_hashmap_size=14)
+
+
+def test_corner_indices_and_the_association_rule_against_a_slow_integer_restatement():
+    for kw, hashed in ((FINE, [True, True, True]), (COARSE, [False, False, True])):
+        lv = O.grid_levels(**kw)
+        assert lv.hashed.tolist() == hashed
+        x = _outside_batch(300, seed=21)
+        x[-1] = 1.0
+        x[-2] = 0.0
+        x[-3] = [16383.0 / 32767.0, 0.5, 0.5]                            # around the cell where the association switches
+        x[-4] = [16382.4 / 32767.0, 0.5, 0.5]
+        classes = set()
+        for l in range(lv.n_levels):
+            want_idx, want_frac, want_pair, cells = _slow_corners(x, lv, l)
+            idx, f = O.grid_corner_indices(x, lv, l)
+            assert np.array_equal(idx.astype(np.int64), want_idx), (kw, l)
+            assert np.array_equal(f.astype(np.float64), want_frac), (kw, l)
+            idx2, w = O.grid_fixed_weights(x, lv, l)
+            assert np.array_equal(idx2, idx)
+            generic, paired = _both_associations(f)
+            assert np.array_equal(w, np.where(want_pair[:, None], paired, generic)), (kw, l)
+            outside = ((x < 0) | (x > 1)).any(1)
+            classes |= {(bool(lv.hashed[l]), bool(p), bool(o)) for p, o in zip(want_pair, outside)}
+            if not lv.hashed[l]:                                           # the modulo of a dense level is taken, and not by every sample
+                assert any(min(c) < 0 for c in cells) and any(max(c) > int(lv.res[l]) for c in cells) and not want_pair.any()
+        if kw is FINE:      # hashed: both associations inside the cube (res 32768) and outside it (a pair: outside along y or z only)
+            assert {(True, True, False), (True, False, False), (True, True, True), (True, False, True)} <= classes
+
+
+def test_integer_fields_outside_the_cube_and_on_fine_levels_against_a_float64_sum():
+    for kw in (FINE, COARSE):
+        for interp in ('Linear', 'Smoothstep'):
+            lv = O.grid_levels(**kw)
+            x = _outside_batch(5003, seed=22)
+            g = torch.Generator().manual_seed(23)
+            dfeat = (torch.randn(lv.n_levels, 5003, 2, generator=g) * 1e-3).numpy()      # (gradients kept outside the cube)
+            shifts = [16 - int(np.ceil(np.log2(np.abs(dfeat[l]).max()))) for l in range(lv.n_levels)]
+            got = O.grid_fixed_fields(x, dfeat, lv, shifts, interp)
+            ref, cnt = _float64_sum(x, dfeat, lv, shifts, interp)
+            assert (np.abs(got - ref) <= 0.5 * cnt[:, None] + 1).all(), (kw, interp)
+            assert not got[cnt == 0].any() and cnt.sum() == 8 * 5003 * lv.n_levels
+
+
+def test_the_association_matters_on_either_side_of_cell_16383():
+    """a kernel with the wrong association on one side of the switch must not pass the GPU tests' equality: on the res 32768 level
+    enough samples of a 5,003-sample batch have a weight whose last bit depends on the association, on both sides"""
+    lv = O.grid_levels(**FINE)
+    assert int(lv.res[2]) == 32768
+    x = torch.rand(5003, 3, generator=torch.Generator().manual_seed(1)).numpy()
+    _, f = O.grid_corner_indices(x, lv, 2)
+    _, w = O.grid_fixed_weights(x, lv, 2)
+    generic, paired = _both_associations(f)
+    differ = (generic != paired).any(1)
+    pair = np.floor(O.grid_pos(x[:, 0], lv.scale[2])) < 16383
+    # (few of 5,003: a grid position near 2^14 keeps 9 or 10 fraction bits, so most three-factor products are exact either way -- and
+    #  fewer right of the switch, where positions are larger.  One differing sample on a side fails an equality; 16 is a margin.)
+    assert differ.sum() >= 50 and (differ & pair).sum() >= 16 and (differ & ~pair).sum() >= 16, (int((differ & pair).sum()), int((differ & ~pair).sum()))
+    assert np.array_equal(w, np.where(pair[:, None], paired, generic))
+    # ... and the integers see it at fine units (the largest field near 2^26, as the GPU tests' fine set: a contribution of 2^k units
+    # has an fp32 ulp of 2^(k - 23) units, so only the large ones carry the last bit of w into the integer): one association for
+    # the whole level, either one, gives other fields
+    idx = [O.grid_corner_indices(x, lv, l)[0] for l in range(3)]
+    dfeat = torch.randn(3, 5003, 2, generator=torch.Generator().manual_seed(2)).numpy()
+    for shift in (24,):
+        right = O.grid_fixed_fields(x, dfeat, lv, [shift] * 3)
+        for wrong in (generic, paired):
+            ws = [O.grid_fixed_weights(x, lv, l) for l in range(2)] + [(idx[2], wrong)]
+            other = O.grid_fixed_fields(x, dfeat, lv, [shift] * 3, weights=ws)
+            lo = int(lv.offset[2])
+            assert np.array_equal(other[:lo], right[:lo]) and (other[lo:] != right[lo:]).sum() >= 8, shift
 
 
 def test_the_overlap_fold_gives_both_copies_the_vertex_sum():

@@ -37,7 +37,8 @@ def _grid(interp='Linear', **kw):
     lv = O.grid_levels(cfg.n_levels, 2, cfg.log2_hashmap_size, cfg.base_resolution, cfg.per_level_scale)
     assert lv.total == cfg.total and np.array_equal(lv.size, cfg.size)
     # hashed levels switch the association of the weight product at cell x = 16383 (grid_fixed_weights restates the rule per sample);
-    # the grids of this file stay below it, so each level is of ONE class
+    # the grids of this file stay below it, so each level is of ONE class (finer grids, levels of more than 16 tiles and gradients
+    # outside the unit cube: tests/test_gpu_exact_gradients_large.py)
     assert all(int(r) + 2 < 16384 for r in cfg.res)
     return cfg, lv
 
@@ -75,7 +76,8 @@ def _face_points(cfg, n, g):
 SIGNS = ('neg_pos', 'pos_neg', 'mixed', 'zero_level')
 
 
-def _dfeat(cfg, x, g, signs):
+def _dfeat(cfg, x, g, signs, outside=False):
+    """outside=True keeps the gradient of the samples outside the unit cube (tests/test_gpu_exact_gradients_large.py)"""
     d = torch.randn(cfg.n_levels, x.shape[0], 2, generator=g) * torch.logspace(-3, 1, cfg.n_levels)[:, None, None]
     if signs == 'neg_pos':                              # the packed pair: a negative low field borrows from the high one
         d[..., 0] = -d[..., 0].abs(); d[..., 1] = d[..., 1].abs()
@@ -83,7 +85,8 @@ def _dfeat(cfg, x, g, signs):
         d[..., 0] = d[..., 0].abs(); d[..., 1] = -d[..., 1].abs()
     elif signs == 'zero_level':
         d[cfg.n_levels // 2] = 0.0
-    d[:, ((x < 0) | (x > 1)).any(1)] = 0.0              # (wrap-around outside the cube stays with the kernel-against-kernel tests)
+    if not outside:                                     # (wrap-around outside the cube: tests/test_gpu_exact_gradients_large.py)
+        d[:, ((x < 0) | (x > 1)).any(1)] = 0.0
     return d
 
 
@@ -114,9 +117,12 @@ def _assert_same_fields(got, want, lv, what):
                              f'largest difference {np.abs(got - want).max()} units')
 
 
-def _check_raw(ops, cfg, lv, x, dfeat, interp, n_live, what, coarse=True):
+def _check_raw(ops, cfg, lv, x, dfeat, interp, n_live, what, coarse=True, codes=(True, False), weights=None):
+    """codes: the values of use_codes to run (a grid with levels on the global-atomics scatter without its bitmaps has no raw fields
+    there); weights: grid_fixed_weights of x[:n_live] per level, for a caller that shares them between tests"""
     n = x.shape[0]
-    weights = [O.grid_fixed_weights(x[:n_live].numpy(), lv, l, interp) for l in range(lv.n_levels)]
+    if weights is None:
+        weights = [O.grid_fixed_weights(x[:n_live].numpy(), lv, l, interp) for l in range(lv.n_levels)]
     fine = _shifts_for(x, dfeat, lv, interp, n_live, weights)
     xc, dc = x.cuda(), dfeat.cuda()
     n_dev = None if n_live == n else torch.tensor([n_live], dtype=torch.int64, device='cuda')
@@ -127,7 +133,7 @@ def _check_raw(ops, cfg, lv, x, dfeat, interp, n_live, what, coarse=True):
         want = O.grid_fixed_fields(x, dfeat, lv, shifts, interp, n_live, weights=weights)
         m = O.fixed_field_max(want, lv)
         assert int(m.max()) < FLAG_LEVEL and (shifts is not fine or int(m.max()) >= 1 << 26)
-        for use_codes in (True, False):                 # coded owners / position-streaming (and run-merging) owners
+        for use_codes in codes:                         # coded owners / position-streaming (and run-merging) owners
             flag.zero_()
             raw = ops.hashgrid_bwd(cfg, xc, dc, shifts=_dev_shifts(shifts), raw_fields=True, n_dev=n_dev, use_codes=use_codes)
             got = raw.view(torch.int32).view(-1, 2).cpu().numpy()

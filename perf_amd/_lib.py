@@ -23,6 +23,7 @@ MESHSIMP_ABI_VERSION = 1     # PERF_MESHSIMP_ABI_VERSION of include/perf_hip_mes
 MESHCOLOR_ABI_VERSION = 1    # PERF_MESHCOLOR_ABI_VERSION of include/perf_hip_meshcolor.h (colour a mesh from the registered panoramas; normals from faces)
 MESHRAY_ABI_VERSION = 1      # PERF_MESHRAY_ABI_VERSION of include/perf_hip_meshray.h (rays against a mesh on a uniform grid: closest hit, any hit, occlusion)
 MESHTEX_ABI_VERSION = 1      # PERF_MESHTEX_ABI_VERSION of include/perf_hip_meshtex.h (a texture atlas for a mesh, baked from the registered panoramas)
+MESHQUADRIC_ABI_VERSION = 1  # PERF_MESHQUADRIC_ABI_VERSION of include/perf_hip_meshquadric.h (quadric error placement of a simplified mesh's vertices, sums in fixed point)
 RIDERS_ABI_VERSION = 1       # PERF_RIDERS_ABI_VERSION of include/perf_hip_riders.h (the next batch's front end riding in the backward's launches)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
@@ -320,6 +321,21 @@ _SIGS_MESHTEX = {
     'perf_meshtex_bake': (c_int, _TEX_MESH + [P, P, POINTER(c_int32), c_int32, c_float, c_int32, c_int32, c_int32, P, POINTER(c_float), P, P, P, P, P, P]),
 }
 
+# include/perf_hip_meshquadric.h: quadric error placement of the clusters' vertices: int64 fixed-point sums, a 3 x 3 solve (perf_meshquadric_version)
+MESHQUADRIC_MAX_VERTICES = 1 << 30       # PERF_MESHQUADRIC_MAX_VERTICES
+MESHQUADRIC_MAX_FACES = (1 << 31) - 1    # PERF_MESHQUADRIC_MAX_FACES
+MESHQUADRIC_MAX_CELLS = 1 << 21          # PERF_MESHQUADRIC_MAX_CELLS, per axis
+MESHQUADRIC_TERMS = 9                    # PERF_MESHQUADRIC_TERMS: qA xx, xy, xz, yy, yz, zz, then qb x, y, z
+MESHQUADRIC_FRACTION_BITS = 40           # PERF_MESHQUADRIC_FRACTION_BITS
+MESHQUADRIC_SKIP_BITS = 60               # PERF_MESHQUADRIC_SKIP_BITS
+MESHQUADRIC_REGULARISER_BITS = 10        # PERF_MESHQUADRIC_REGULARISER_BITS
+_QUADRIC_GRID = [POINTER(c_float), c_float, c_int32, c_int32, c_int32]          # lo, h, nx, ny, nz
+_SIGS_MESHQUADRIC = {
+    'perf_meshquadric_version': (c_int, []),
+    'perf_meshquadric_sums': (c_int, [P, c_int64, P, c_int64] + _QUADRIC_GRID + [P, c_int64, P, P, P, P]),
+    'perf_meshquadric_place': (c_int, [P, c_int64] + _QUADRIC_GRID + [P, P, P, c_int64, P, P]),
+}
+
 # include/perf_hip_riders.h: the step riders, exported from the same library, versioned on their own (perf_riders_version)
 RIDER_THREADS = 256          # PERF_RIDER_THREADS
 RIDER_DRAW_RAYS = 256        # PERF_RIDER_DRAW_RAYS
@@ -358,6 +374,7 @@ _UNITS = (
     (_SIGS_MESHCOLOR, 'perf_meshcolor_version', MESHCOLOR_ABI_VERSION, _expects('mesh-colouring ABI'), ()),
     (_SIGS_MESHRAY, 'perf_meshray_version', MESHRAY_ABI_VERSION, _expects('mesh ray-casting ABI'), ()),
     (_SIGS_MESHTEX, 'perf_meshtex_version', MESHTEX_ABI_VERSION, _expects('texture-atlas ABI'), ()),
+    (_SIGS_MESHQUADRIC, 'perf_meshquadric_version', MESHQUADRIC_ABI_VERSION, _expects('quadric-placement ABI'), ()),
     (_SIGS_RIDERS, 'perf_riders_version', RIDERS_ABI_VERSION, 'step-rider ABI version {has} or other argument blocks than this binding ({want})',
      (('perf_sizeof_rider_draw', ctypes.sizeof(RiderDraw)), ('perf_sizeof_rider_count', ctypes.sizeof(RiderCount)),
       ('perf_sizeof_rider_write', ctypes.sizeof(RiderWrite)))),

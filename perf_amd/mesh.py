@@ -408,8 +408,8 @@ def _cluster_grid(who, vertices, cell, box):
 
 
 def _check_placement(who, placement, dedupe='oriented'):
-    if placement not in _lib.MESHSIMP_PLACEMENT:
-        raise _lib.PerfError(f"{who}: placement is 'mean' or 'member', got {placement!r}")
+    if placement != 'quadric' and placement not in _lib.MESHSIMP_PLACEMENT:          # ('quadric' is a second pass over the faces, not a placement of the clustering unit)
+        raise _lib.PerfError(f"{who}: placement is 'mean', 'member' or 'quadric', got {placement!r}")
     if dedupe not in _lib.MESHSIMP_DEDUPE:
         raise _lib.PerfError(f"{who}: dedupe is 'oriented', 'unoriented' or None, got {dedupe!r}")
 
@@ -422,7 +422,10 @@ def cluster_vertices(vertices, cell, box=None, placement='mean') -> Clusters:
     """The vertices fp32 [V, 3] that share a cell of edge `cell` of the grid over box = (lo, hi) (None: the vertices' own bounds, one more
     host read) become one cluster: its vertex is the mean of its members (exact integer sums of 2^-32 fixed-point fractions) or, under
     placement='member', the member nearest that mean, bit for bit.  One host read: the cluster count with the flag of a vertex that is
-    not finite, which is refused."""
+    not finite, which is refused.  placement='quadric' reads the faces, which this call does not have: quadric_placement takes the
+    clusters and the mesh."""
+    if placement == 'quadric':
+        raise _lib.PerfError("cluster_vertices: placement 'quadric' needs the faces: cluster with 'mean', then call quadric_placement(mesh, clusters, cell, box)")
     if not torch.is_tensor(vertices) or not vertices.is_cuda:
         raise _lib.PerfError('cluster_vertices: vertices must be a CUDA tensor (there is no CPU path)')
     _check_placement('cluster_vertices', placement)
@@ -456,7 +459,12 @@ def simplify_mesh(mesh, cell, box=None, placement='mean', dedupe='oriented'):
     """mesh with one vertex per occupied cell of edge `cell` -> (Mesh, kept_vertex_index int32 [V']): cluster_vertices -> cluster_faces ->
     the compaction of filter_faces, with ONE host read of (clusters, the two flags, kept vertices, kept faces) beside the compaction's own.
     Clusters no kept face names are dropped; kept_vertex_index holds the surviving clusters' representatives, through which colors and
-    normals are gathered.  Clustering can pinch a surface: there is no manifold repair."""
+    normals are gathered.  Clustering can pinch a surface: there is no manifold repair.
+    placement: 'mean' (the members' mean), 'member' (the member nearest the mean) or 'quadric' (include/perf_hip_meshquadric.h: the
+    point of the cell that minimises the summed squared distances to the planes of the members' faces, regularised towards the mean, so
+    edges and corners of the surface stay where they are; int64 fixed-point sums, bit-identical from run to run).  'quadric' runs the
+    'mean' simplification, then two more launches on the same stream: faces, kept_vertex_index, colors and normals are those of 'mean',
+    and there is no further host read (the flag of the faces the 2^60 rule skipped stays on the device: quadric_placement returns it)."""
     _check_mesh('simplify_mesh', mesh)
     _check_placement('simplify_mesh', placement, dedupe)
     vertices, faces = mesh.vertices.contiguous(), mesh.faces.contiguous()
@@ -471,7 +479,10 @@ def simplify_mesh(mesh, cell, box=None, placement='mean', dedupe='oriented'):
         _raise_bad_vertex('simplify_mesh', vertices, bad_vertex)
     if bad_face >= 0:
         _raise_bad_face('simplify_mesh', faces, bad_face, n_vertices)
-    placed, representative = ops.meshsimp_place(vertices, lo, h, n, vertex_cluster, n_clusters, placement)
+    placed, representative = ops.meshsimp_place(vertices, lo, h, n, vertex_cluster, n_clusters, 'mean' if placement == 'quadric' else placement)
+    if placement == 'quadric':
+        acc, _ = ops.meshquadric_sums(vertices, faces, lo, h, n, vertex_cluster, n_clusters)
+        placed = ops.meshquadric_place(vertices, lo, h, n, placed, representative, acc)
     _, new_faces, kept_cluster = ops.meshvis_filter_write(remapped, n_vertices, keep, filter_ws, kept_vertices, kept_faces)
     kept_cluster = kept_cluster.long()
     index = representative[kept_cluster]
@@ -479,6 +490,26 @@ def simplify_mesh(mesh, cell, box=None, placement='mean', dedupe='oriented'):
     colors = mesh.colors[gather] if mesh.colors is not None else None
     normals = mesh.normals[gather] if mesh.normals is not None else None
     return Mesh(placed[kept_cluster], new_faces, colors, normals), index
+
+
+class QuadricPlacement(NamedTuple):
+    vertices: torch.Tensor                       # [C, 3] fp32: the clusters' vertices by quadric error
+    skipped: torch.Tensor                        # [1] int64 ON THE DEVICE: the smallest index of a face the 2^60 rule skipped, or -1
+
+
+def quadric_placement(mesh, clusters, cell, box=None) -> QuadricPlacement:
+    """The vertices of `clusters` (cluster_vertices of mesh.vertices with the SAME cell and box, under either placement) by quadric
+    error (include/perf_hip_meshquadric.h), for callers that cluster apart: the 'mean' placement as the anchor, the fixed-point sums
+    over mesh.faces, the solve.  No host read: `skipped` stays on the device, and a face with an index outside [0, V) is not followed
+    (cluster_faces is what refuses it)."""
+    _check_mesh('quadric_placement', mesh)
+    vertices, faces = mesh.vertices.contiguous(), mesh.faces.contiguous()
+    if not isinstance(clusters, Clusters) or clusters.vertex_cluster.numel() != vertices.shape[0]:
+        raise _lib.PerfError('quadric_placement: clusters must be the Clusters cluster_vertices made of mesh.vertices')
+    lo, h, n = _cluster_grid('quadric_placement', vertices, cell, box)
+    anchor, representative = ops.meshsimp_place(vertices, lo, h, n, clusters.vertex_cluster, clusters.n_clusters, 'mean')
+    acc, flags = ops.meshquadric_sums(vertices, faces, lo, h, n, clusters.vertex_cluster, clusters.n_clusters)
+    return QuadricPlacement(ops.meshquadric_place(vertices, lo, h, n, anchor, representative, acc), flags[1:])
 
 
 # ---- the panoramas' colours on the mesh; vertex normals from the faces (include/perf_hip_meshcolor.h) ------------------------------------

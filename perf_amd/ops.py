@@ -1204,6 +1204,59 @@ def meshsimp_faces(faces, vertex_cluster, dedupe='oriented', ws=None, flag=None)
     return remapped, keep, flag
 
 
+# ---- quadric error placement of the clusters' vertices (include/perf_hip_meshquadric.h) ------------------------------------------------
+def _quadric_rows(who, t, name, dtype, shape, device):
+    if not torch.is_tensor(t) or not t.is_cuda or t.device != device:
+        raise _lib.PerfError(f'{who}: {name} must be a CUDA tensor on the vertices\' device (there is no CPU path)')
+    if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+        raise _lib.PerfError(f'{who}: {name} must be a contiguous {dtype} {list(shape)} tensor, got {t.dtype} {tuple(t.shape)}')
+    return t
+
+
+def meshquadric_sums(vertices, faces, lo, h, n, vertex_cluster, n_clusters, flags=None):
+    """Stage A of include/perf_hip_meshquadric.h (perf_meshquadric_sums) -> (acc int64 [C, 9], flags): per cluster the int64 fixed-point
+    sums (2^-40) of its members' quadrics, qA xx, xy, xz, yy, yz, zz then qb x, y, z, by integer atomics: exact in any order.  flags =
+    int64 [2] ON THE DEVICE: the smallest index of a face with an index outside [0, V) or -1, then the smallest index of a face the
+    2^60 rule skipped or -1 (an int64 [2] view to write them into may be passed)."""
+    vertices, nv = _simp_vertices('meshquadric_sums', vertices)
+    _, f = _cc_faces('meshquadric_sums', faces, nv)
+    if faces.device != vertices.device:
+        raise _lib.PerfError('meshquadric_sums: faces must be on the vertices\' device')
+    if f > _lib.MESHQUADRIC_MAX_FACES:
+        raise _lib.PerfError(f'meshquadric_sums: {f} faces are more than 2^31 - 1')
+    lo3, h, n3 = _simp_grid('meshquadric_sums', lo, h, n)
+    _cc_labels('meshquadric_sums', vertex_cluster, nv, vertices.device)
+    c = int(n_clusters)
+    if c < 0 or c > nv:
+        raise _lib.PerfError(f'meshquadric_sums: {c} clusters, the mesh has {nv} vertices')
+    acc = torch.empty(c, _lib.MESHQUADRIC_TERMS, dtype=torch.int64, device=vertices.device)
+    if flags is None:
+        flags = torch.empty(2, dtype=torch.int64, device=vertices.device)
+    _quadric_rows('meshquadric_sums', flags, 'flags', torch.int64, (2,), vertices.device)
+    _call('perf_meshquadric_sums', _p(vertices) if nv else None, nv, _p(faces) if f else None, f, lo3, h, *n3, _p(vertex_cluster) if nv else None, c,
+          _p(acc) if c else None, ctypes.c_void_p(flags.data_ptr()), ctypes.c_void_p(flags.data_ptr() + 8), _stream())
+    return acc, flags
+
+
+def meshquadric_place(vertices, lo, h, n, anchor, representative, acc):
+    """Stage B of include/perf_hip_meshquadric.h (perf_meshquadric_place) -> cluster vertices fp32 [C, 3]: the minimiser of the cluster's
+    summed quadric, regularised towards anchor fp32 [C, 3] (the 'mean' placement) and clamped to the cell of vertices[representative];
+    anchor's row, bit for bit, where the cluster has no face or no solve."""
+    vertices, nv = _simp_vertices('meshquadric_place', vertices)
+    lo3, h, n3 = _simp_grid('meshquadric_place', lo, h, n)
+    c = int(acc.shape[0]) if torch.is_tensor(acc) and acc.dim() == 2 else -1
+    if c < 0 or c > nv:
+        raise _lib.PerfError(f'meshquadric_place: acc must be an int64 [C, {_lib.MESHQUADRIC_TERMS}] tensor with C <= {nv} vertices')
+    dev = vertices.device
+    _quadric_rows('meshquadric_place', acc, 'acc', torch.int64, (c, _lib.MESHQUADRIC_TERMS), dev)
+    _quadric_rows('meshquadric_place', anchor, 'anchor', torch.float32, (c, 3), dev)
+    _quadric_rows('meshquadric_place', representative, 'representative', torch.int32, (c,), dev)
+    out = torch.empty(c, 3, dtype=torch.float32, device=dev)
+    _call('perf_meshquadric_place', _p(vertices) if nv else None, nv, lo3, h, *n3, _p(anchor) if c else None, _p(representative) if c else None,
+          _p(acc) if c else None, c, _p(out) if c else None, _stream())
+    return out
+
+
 # ---- colour a mesh from the registered panoramas; vertex normals from faces (include/perf_hip_meshcolor.h) -----------------------------
 def meshcolor_normal_sums(vertices, faces, scale_log2, flag=None):
     """The faces' area-weighted normals (double, times 2^scale_log2, rounded to int64) summed at their vertices by integer atomics

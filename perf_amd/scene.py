@@ -1686,7 +1686,7 @@ class NeRFScene:
 
     def simplify_mesh(self, mesh, cell, **kw):
         """mesh with one vertex per occupied cell of edge `cell` of the grid over the scene's aabb (perf_amd/mesh.py: simplify_mesh's
-        keywords) -> mesh.Mesh."""
+        keywords; placement='quadric' keeps the edges and corners the mean rounds off) -> mesh.Mesh."""
         from .mesh import simplify_mesh
         aabb = [float(v) for v in self.nerf._aabb_host]
         kw.setdefault('box', (aabb[:3], aabb[3:]))

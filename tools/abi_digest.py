@@ -11,7 +11,8 @@ include/perf_hip_meshvis.h, PERF_MESHVIS_ABI_VERSION, include/perf_hip_meshvis.a
 include/perf_hip_meshsimp.h, PERF_MESHSIMP_ABI_VERSION, include/perf_hip_meshsimp.abi.json; `--meshcolor`: of the colouring from the panoramas,
 include/perf_hip_meshcolor.h, PERF_MESHCOLOR_ABI_VERSION, include/perf_hip_meshcolor.abi.json; `--meshray`: of the rays against a mesh on a uniform grid,
 include/perf_hip_meshray.h, PERF_MESHRAY_ABI_VERSION, include/perf_hip_meshray.abi.json; `--meshtex`: of the texture atlas baked from the panoramas,
-include/perf_hip_meshtex.h, PERF_MESHTEX_ABI_VERSION, include/perf_hip_meshtex.abi.json; `--riders`: of the step riders,
+include/perf_hip_meshtex.h, PERF_MESHTEX_ABI_VERSION, include/perf_hip_meshtex.abi.json; `--meshquadric`: of the quadric error placement,
+include/perf_hip_meshquadric.h, PERF_MESHQUADRIC_ABI_VERSION, include/perf_hip_meshquadric.abi.json; `--riders`: of the step riders,
 include/perf_hip_riders.h, PERF_RIDERS_ABI_VERSION, include/perf_hip_riders.abi.json): sha256 over the comment-free, whitespace-normalised text of every
 `perf_*` prototype, struct and #define, in file order.  `python tools/abi_digest.py` prints {version, digest};
 `--write` records it in include/perf_hip.abi.json.  tests/test_cpu_oracle.py fails when the digest of the header differs
@@ -50,6 +51,8 @@ MESHRAY_HEADER = os.path.join(ROOT, 'include', 'perf_hip_meshray.h')
 MESHRAY_RECORD = os.path.join(ROOT, 'include', 'perf_hip_meshray.abi.json')
 MESHTEX_HEADER = os.path.join(ROOT, 'include', 'perf_hip_meshtex.h')
 MESHTEX_RECORD = os.path.join(ROOT, 'include', 'perf_hip_meshtex.abi.json')
+MESHQUADRIC_HEADER = os.path.join(ROOT, 'include', 'perf_hip_meshquadric.h')
+MESHQUADRIC_RECORD = os.path.join(ROOT, 'include', 'perf_hip_meshquadric.abi.json')
 RIDERS_HEADER = os.path.join(ROOT, 'include', 'perf_hip_riders.h')
 RIDERS_RECORD = os.path.join(ROOT, 'include', 'perf_hip_riders.abi.json')
 
@@ -72,10 +75,11 @@ if __name__ == '__main__':
     meshcolor = '--meshcolor' in sys.argv
     meshray = '--meshray' in sys.argv
     meshtex = '--meshtex' in sys.argv
+    meshquadric = '--meshquadric' in sys.argv
     riders = '--riders' in sys.argv
     ext, sphere, pair, joint, mesh = '--ext' in sys.argv, '--sphere' in sys.argv, '--pair' in sys.argv, '--joint' in sys.argv, '--mesh' in sys.argv
-    d = digest(RIDERS_HEADER, 'PERF_RIDERS_ABI_VERSION') if riders else digest(MESHTEX_HEADER, 'PERF_MESHTEX_ABI_VERSION') if meshtex else digest(MESHRAY_HEADER, 'PERF_MESHRAY_ABI_VERSION') if meshray else digest(MESHCOLOR_HEADER, 'PERF_MESHCOLOR_ABI_VERSION') if meshcolor else digest(MESHSIMP_HEADER, 'PERF_MESHSIMP_ABI_VERSION') if meshsimp else digest(MESHVIS_HEADER, 'PERF_MESHVIS_ABI_VERSION') if meshvis else digest(MESHCC_HEADER, 'PERF_MESHCC_ABI_VERSION') if meshcc else digest(BRICKMESH_HEADER, 'PERF_BRICKMESH_ABI_VERSION') if brickmesh else digest(MESH_HEADER, 'PERF_MESH_ABI_VERSION') if mesh else digest(JOINT_HEADER, 'PERF_JOINT_ABI_VERSION') if joint else digest(PAIR_HEADER, 'PERF_PAIR_ABI_VERSION') if pair else digest(SPHERE_HEADER, 'PERF_SPHERE_ABI_VERSION') if sphere else digest(EXT_HEADER, 'PERF_EXT_ABI_VERSION') if ext else digest()
-    record = RIDERS_RECORD if riders else MESHTEX_RECORD if meshtex else MESHRAY_RECORD if meshray else MESHCOLOR_RECORD if meshcolor else MESHSIMP_RECORD if meshsimp else MESHVIS_RECORD if meshvis else MESHCC_RECORD if meshcc else BRICKMESH_RECORD if brickmesh else MESH_RECORD if mesh else JOINT_RECORD if joint else PAIR_RECORD if pair else SPHERE_RECORD if sphere else EXT_RECORD if ext else RECORD
+    d = digest(RIDERS_HEADER, 'PERF_RIDERS_ABI_VERSION') if riders else digest(MESHQUADRIC_HEADER, 'PERF_MESHQUADRIC_ABI_VERSION') if meshquadric else digest(MESHTEX_HEADER, 'PERF_MESHTEX_ABI_VERSION') if meshtex else digest(MESHRAY_HEADER, 'PERF_MESHRAY_ABI_VERSION') if meshray else digest(MESHCOLOR_HEADER, 'PERF_MESHCOLOR_ABI_VERSION') if meshcolor else digest(MESHSIMP_HEADER, 'PERF_MESHSIMP_ABI_VERSION') if meshsimp else digest(MESHVIS_HEADER, 'PERF_MESHVIS_ABI_VERSION') if meshvis else digest(MESHCC_HEADER, 'PERF_MESHCC_ABI_VERSION') if meshcc else digest(BRICKMESH_HEADER, 'PERF_BRICKMESH_ABI_VERSION') if brickmesh else digest(MESH_HEADER, 'PERF_MESH_ABI_VERSION') if mesh else digest(JOINT_HEADER, 'PERF_JOINT_ABI_VERSION') if joint else digest(PAIR_HEADER, 'PERF_PAIR_ABI_VERSION') if pair else digest(SPHERE_HEADER, 'PERF_SPHERE_ABI_VERSION') if sphere else digest(EXT_HEADER, 'PERF_EXT_ABI_VERSION') if ext else digest()
+    record = RIDERS_RECORD if riders else MESHQUADRIC_RECORD if meshquadric else MESHTEX_RECORD if meshtex else MESHRAY_RECORD if meshray else MESHCOLOR_RECORD if meshcolor else MESHSIMP_RECORD if meshsimp else MESHVIS_RECORD if meshvis else MESHCC_RECORD if meshcc else BRICKMESH_RECORD if brickmesh else MESH_RECORD if mesh else JOINT_RECORD if joint else PAIR_RECORD if pair else SPHERE_RECORD if sphere else EXT_RECORD if ext else RECORD
     if '--write' in sys.argv:
         json.dump(d, open(record, 'w'), indent=1)
         open(record, 'a').write('\n')

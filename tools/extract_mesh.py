@@ -3,7 +3,7 @@
   python tools/extract_mesh.py --out room.ply [--resolution 256] [--threshold T] [--no-occupancy] [--no-colors] [--no-normals] [--sparse]
                                [--seen-by-panoramas [--occlusion] [--visibility-tol T] [--carve] [--sup-pool pool.pt]]
                                [--min-component-faces N] [--keep-largest K] [--orientation inward|outward]
-                               [--simplify-cell H [--simplify-placement mean|member] [--simplify-dedupe oriented|unoriented|none]]
+                               [--simplify-cell H [--simplify-placement mean|member|quadric] [--simplify-dedupe oriented|unoriented|none]]
                                [--colors-from-panoramas [--color-select blend|best] [--color-power N] [--sup-pool pool.pt]]
                                [--texture SIZE [--texture-source panoramas|field] [--texture-tile T]]
                                [--checkpoint scene.pt | --geo 3000 --app 1500] [--dtype fp16]
@@ -38,8 +38,9 @@ ap.add_argument('--occlusion', action='store_true', help='with --seen-by-panoram
 ap.add_argument('--sup-pool', default=None, help='with --checkpoint and --seen-by-panoramas: a torch.save of SupInfoPool.state_dict()')
 ap.add_argument('--simplify-cell', type=float, default=None,
                 help='after the cleaning: one vertex per occupied cell of this edge (scene units) of the grid over the scene box (vertex clustering)')
-ap.add_argument('--simplify-placement', choices=['mean', 'member'], default='mean',
-                help='the vertex of a cell: the mean of its vertices, or the one of them nearest the mean (no shrinkage)')
+ap.add_argument('--simplify-placement', choices=['mean', 'member', 'quadric'], default='mean',
+                help='the vertex of a cell: the mean of its vertices, the one of them nearest the mean (no shrinkage), or the point of the cell nearest the planes of '
+                     'their faces (quadric error: edges and corners stay sharp)')
 ap.add_argument('--simplify-dedupe', choices=['oriented', 'unoriented', 'none'], default='oriented',
                 help='of the faces that become equal up to rotation (oriented) or as sets (unoriented: a double skin thinner than a cell) one stays')
 ap.add_argument('--colors-from-panoramas', action='store_true',

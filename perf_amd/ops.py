@@ -758,20 +758,68 @@ def joint_tv(m, weight=1.0, grad=None, value=None, ws=None):
 
 
 # ---- what the mesh units' bindings share ------------------------------------------------------------------------------------------------
+_ANYWHERE = 'anywhere'          # _dev_tensor's device for a tensor the library is not handed (K = 0 views): it may be on the host
+
+
+def _dev_tensor(who, name, t, dtype, shape, device=None, any_dtype_if_empty=False):
+    """The one check of a tensor the library reads or writes: t is a contiguous CUDA tensor of dtype (one, or a tuple of them) and shape,
+    on `device` (the device of the tensor it must live with) when one is given.  A shape entry is a size, or a letter for a dimension
+    left free, reported as in [V, 3]; a shape of None leaves all of them free.  None passes through: an optional argument.
+    any_dtype_if_empty: an empty t stands for NULL in the call and may have any dtype."""
+    if t is None:
+        return None
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    ok = torch.is_tensor(t) and (t.dtype in dtypes or (any_dtype_if_empty and t.numel() == 0)) and t.is_contiguous()
+    ok = ok and (device is _ANYWHERE or (t.is_cuda and device in (None, t.device)))
+    if ok and shape is not None:
+        ok = t.dim() == len(shape) and all(isinstance(s, str) or s == d for s, d in zip(shape, t.shape))
+    if not ok:
+        want = ' or '.join(str(d) for d in dtypes) + ('' if shape is None else f' [{", ".join(str(s) for s in shape)}]')
+        where = 'tensor' if device is _ANYWHERE else 'CUDA tensor (there is no CPU path)' if device is None else f'CUDA tensor on {device} (there is no CPU path)'
+        got = f'{t.dtype} {tuple(t.shape)} on {t.device}{"" if t.is_contiguous() else ", not contiguous"}' if torch.is_tensor(t) else type(t).__name__
+        raise _lib.PerfError(f'{who}: {name} must be a contiguous {want} {where}, got {got}')
+    return t
+
+
+def _pn(t):
+    """The pointer of t, NULL for None and for an empty tensor."""
+    return _p(t) if t is not None and t.numel() else None
+
+
+def _flag(who, name, flag, n, device):
+    """The words the library reports into: new int64 [n] ones, or what the caller passed, which is the caller's to size: only that it
+    is a tensor is checked here."""
+    if flag is None:
+        return torch.empty(n, dtype=torch.int64, device=device)
+    if not torch.is_tensor(flag):
+        raise _lib.PerfError(f'{who}: {name} must be an int64 [{n}] CUDA tensor, got {type(flag).__name__}')
+    return flag
+
+
 def _mesh_ws(query, sizes, ws, device):
     """The int64 workspace of at least perf_*_workspace_bytes(*sizes) bytes on device: ws itself when it serves, else a new one."""
     nbytes = getattr(_lib.load(), query)(*sizes)
     if nbytes < 0:
         _lib.check(-1, query)
+    if ws is not None and not torch.is_tensor(ws):
+        raise _lib.PerfError(f'{query}: ws must be an int64 CUDA tensor or None, got {type(ws).__name__}')
     if ws is None or ws.numel() * 8 < nbytes or ws.device != device:
         ws = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
     return ws
 
 
-def _mask_u8(mask):
-    """A bool or uint8 mask, contiguous, as the uint8 the library reads."""
-    m = mask.contiguous()
-    return m.view(torch.uint8) if m.dtype == torch.bool else m
+def _ws_args(who, ws):
+    """The (pointer, bytes) of a workspace in a library call; whether it is the one the count made is the library's to judge, by its bytes."""
+    if not torch.is_tensor(ws):
+        raise _lib.PerfError(f'{who}: ws must be the int64 CUDA workspace of the count, got {type(ws).__name__}')
+    return _p(ws), ws.numel() * 8
+
+
+def _mask_u8(who, name, mask, shape, device=None):
+    """A bool or uint8 mask of shape as the contiguous uint8 the library reads; a strided one is copied."""
+    if torch.is_tensor(mask):
+        mask = mask.contiguous()
+    return _dev_tensor(who, name, mask, (torch.bool, torch.uint8), shape, device).view(torch.uint8)
 
 
 def _box3(who, lo, hi):
@@ -782,9 +830,75 @@ def _box3(who, lo, hi):
     return (ctypes.c_float * 3)(*lo3), (ctypes.c_float * 3)(*hi3)
 
 
+def _faces(who, faces, n_vertices, device=None):
+    """faces int32 [F, 3] over n_vertices vertices, as many as the library takes -> (n_vertices, F)."""
+    faces = _dev_tensor(who, 'faces', faces, torch.int32, ('F', 3), device)
+    n = int(n_vertices)
+    if n < 0 or n > _lib.MESHCC_MAX_VERTICES:
+        raise _lib.PerfError(f'{who}: {n} vertices are outside 0 .. 2^30')
+    return n, int(faces.shape[0])
+
+
+def _mesh_head(who, vertices, faces, max_faces=None):
+    """The head of a mesh: vertices fp32 [V, 3] and faces int32 [F, 3] on one device, at most max_faces of them -> (vertices, V, F, the
+    (vertices, V, faces, F) a library call begins with)."""
+    vertices = _dev_tensor(who, 'vertices', vertices, torch.float32, ('V', 3))
+    nv, f = _faces(who, faces, vertices.shape[0], vertices.device)
+    if max_faces is not None and f > max_faces:
+        raise _lib.PerfError(f'{who}: {f} faces are more than {"2^31 - 1" if max_faces == (1 << 31) - 1 else max_faces}')
+    return vertices, nv, f, (_pn(vertices), nv, _pn(faces), f)
+
+
+def _labelled_faces(who, faces, labels, name):
+    """faces int32 [F, 3] and the vertices' labels int32 [V], on one device -> (V, F)."""
+    labels = _dev_tensor(who, name, labels, torch.int32, ('V',))
+    return _faces(who, faces, labels.numel(), labels.device)
+
+
+def _centres(who, centres):
+    """The views' centres fp32 [K, 3] -> (centres, K).  With no view they are not read: any [0, 3] tensor serves, on the host as well."""
+    if not (torch.is_tensor(centres) and tuple(centres.shape) == (0, 3)):
+        centres = _dev_tensor(who, 'centres', centres, torch.float32, ('K', 3))
+    return centres, int(centres.shape[0])
+
+
+def _views_table(who, views, sizes, device):
+    """The views of meshvis_views against their host sizes -> the (views, sizes, K) of a library call.  With no view the table is not
+    read and may be on the host."""
+    k = len(sizes)
+    views = _dev_tensor(who, 'views', views, torch.int32, (k, 16), device if k else _ANYWHERE)
+    return _pn(views), (ctypes.c_int32 * (2 * k))(*[v for hw in sizes for v in hw]) if k else None, k
+
+
+def _blend_args(who, n, device, views, sizes, map_pointers, tol, facing, power, select, fallback, fill):
+    """The views' side of the blend of include/perf_hip_meshcolor.h over n vertices on device, checked -> its arguments in a library
+    call, from the views to the fill."""
+    table, flat, k = _views_table(who, views, sizes, device)
+    map_pointers = _dev_tensor(who, 'map_pointers', map_pointers, torch.int64, (k,), device if k else _ANYWHERE)
+    if select not in _lib.MESHCOLOR_SELECT:
+        raise _lib.PerfError(f"{who}: select is 'blend' or 'best', got {select!r}")
+    fallback = _dev_tensor(who, "the vertices' fallback", fallback, torch.float32, (n, 3), device)          # (named with the vertices, like their normals: a
+    # row count that disagrees is refused here whichever of the two is wrong)
+    fill3 = [float(v) for v in fill]
+    if len(fill3) != 3:
+        raise _lib.PerfError(f'{who}: fill holds three values')
+    return (table, _pn(map_pointers), flat, k, float(tol), int(bool(facing)), int(power), _lib.MESHCOLOR_SELECT[select], _pn(fallback),
+            (ctypes.c_float * 3)(*fill3))
+
+
+def _filtered(vertices, n_vertices_kept, n_faces_kept, device):
+    """What a filter writes -> ((kept vertices or None without vertices, kept faces, kept_vertex_index), the tail of its library call)."""
+    nv, nf = int(n_vertices_kept), int(n_faces_kept)
+    vertices_out = torch.empty(nv, 3, dtype=torch.float32, device=device) if vertices is not None else None
+    index = torch.empty(nv, dtype=torch.int32, device=device)
+    faces_out = torch.empty(nf, 3, dtype=torch.int32, device=device)
+    return (vertices_out, faces_out, index), (_pn(vertices_out), _pn(index), nv, _pn(faces_out), nf)
+
+
 # ---- surface nets on a dense lattice (include/perf_hip_mesh.h) -------------------------------------------------------------------------
 def _mesh_cells(who, field):
-    if field.dim() != 3 or min(field.shape) < 2:
+    field = _dev_tensor(who, 'field', field, torch.float32, ('nx+1', 'ny+1', 'nz+1'))
+    if min(field.shape) < 2:
         raise _lib.PerfError(f'{who}: the field must be [nx+1, ny+1, nz+1] corner values with at least one cell per axis, got {tuple(field.shape)}')
     return tuple(int(s) - 1 for s in field.shape)
 
@@ -795,7 +909,7 @@ def mesh_count(field, thr, ws=None):
     nx, ny, nz = _mesh_cells('mesh_count', field)
     ws = _mesh_ws('perf_mesh_workspace_bytes', (nx, ny, nz), ws, field.device)
     counts = torch.empty(2, dtype=torch.int64, device=field.device)
-    _call('perf_mesh_count', _p(_f32(field, 'field')), nx, ny, nz, float(thr), _p(ws), ws.numel() * 8, _p(counts), _stream())
+    _call('perf_mesh_count', _p(field), nx, ny, nz, float(thr), *_ws_args('mesh_count', ws), _p(counts), _stream())
     return counts, ws
 
 
@@ -807,8 +921,7 @@ def mesh_write(field, thr, lo, hi, ws, n_vertices, n_faces):
     lo3, hi3 = _box3('mesh_write', lo, hi)
     vertices = torch.empty(int(n_vertices), 3, dtype=torch.float32, device=field.device)
     faces = torch.empty(int(n_faces), 3, dtype=torch.int32, device=field.device)
-    _call('perf_mesh_write', _p(_f32(field, 'field')), nx, ny, nz, float(thr), lo3, hi3, _p(ws),
-          ws.numel() * 8, _p(vertices) if n_vertices else None, int(n_vertices), _p(faces) if n_faces else None, int(n_faces), _stream())
+    _call('perf_mesh_write', _p(field), nx, ny, nz, float(thr), lo3, hi3, *_ws_args('mesh_write', ws), _pn(vertices), int(n_vertices), _pn(faces), int(n_faces), _stream())
     return vertices, faces
 
 
@@ -820,45 +933,31 @@ def _brick_shape(who, shape):
     return n
 
 
-def _brick_dev(who, **tensors):
-    for name, t in tensors.items():
-        if not t.is_cuda:
-            raise _lib.PerfError(f'{who}: {name} must be a CUDA tensor (there is no CPU path)')
-
-
-def _brick_i32(t, name):
-    if t.dtype != torch.int32 or not t.is_contiguous():
-        raise _lib.PerfError(f'{name} must be a contiguous int32 tensor')
-    return t
-
-
 def _brick_occ(who, binaries):
     """binaries: bool or uint8 [..., R, R, R] -> (uint8 view, R)."""
-    if binaries.dtype not in (torch.bool, torch.uint8) or binaries.dim() < 3 or len(set(binaries.shape[-3:])) != 1 or binaries.numel() != binaries.shape[-1] ** 3:
-        raise _lib.PerfError(f'{who}: binaries must be bool or uint8 [R, R, R], got {binaries.dtype} {tuple(binaries.shape)}')
-    return _mask_u8(binaries), int(binaries.shape[-1])
+    if not torch.is_tensor(binaries) or binaries.dim() < 3 or len(set(binaries.shape[-3:])) != 1 or binaries.numel() != binaries.shape[-1] ** 3:
+        got = f'{binaries.dtype} {tuple(binaries.shape)}' if torch.is_tensor(binaries) else type(binaries).__name__
+        raise _lib.PerfError(f'{who}: binaries must be bool or uint8 [R, R, R], got {got}')
+    return _mask_u8(who, 'binaries', binaries, tuple(binaries.shape)), int(binaries.shape[-1])
 
 
 def brickmesh_select(binaries, shape, ws=None):
     """Which 8^3 bricks of a lattice of `shape` cells touch a set cell of the occupancy grid (perf_brickmesh_select) -> (table int32
     [Bx, By, Bz]: slot or -1, n_live: int64 [1] ON THE DEVICE)."""
     n = _brick_shape('brickmesh_select', shape)
-    _brick_dev('brickmesh_select', binaries=binaries)
     occ, res = _brick_occ('brickmesh_select', binaries)
     ws = _mesh_ws('perf_brickmesh_workspace_bytes', (*n, 0), ws, occ.device)
     table = torch.empty(tuple(v // 8 for v in n), dtype=torch.int32, device=occ.device)
     n_live = torch.empty(1, dtype=torch.int64, device=occ.device)
-    _call('perf_brickmesh_select', _p(occ), res, *n, _p(table), _p(n_live), _p(ws), ws.numel() * 8, _stream())
+    _call('perf_brickmesh_select', _p(occ), res, *n, _p(table), _p(n_live), *_ws_args('brickmesh_select', ws), _stream())
     return table, n_live
 
 
 def brickmesh_list(table, n_bricks):
     """The ascending linear indices int32 [n_bricks] of the bricks a table holds (perf_brickmesh_list)."""
-    _brick_dev('brickmesh_list', table=table)
-    if table.dim() != 3:
-        raise _lib.PerfError(f'brickmesh_list: the table must be [Bx, By, Bz], got {tuple(table.shape)}')
+    table = _dev_tensor('brickmesh_list', 'table', table, torch.int32, ('Bx', 'By', 'Bz'))
     ids = torch.empty(int(n_bricks), dtype=torch.int32, device=table.device)
-    _call('perf_brickmesh_list', _p(_brick_i32(table, 'table')), *(8 * int(s) for s in table.shape), _p(ids) if n_bricks else None, int(n_bricks), _stream())
+    _call('perf_brickmesh_list', _p(table), *(8 * int(s) for s in table.shape), _pn(ids), int(n_bricks), _stream())
     return ids
 
 
@@ -866,158 +965,99 @@ def brickmesh_corners(ids, first, m, shape, binaries):
     """The stored corners of the slots first .. first + m - 1 (perf_brickmesh_corners) -> (x01 fp32 [m * 512, 3], sel uint8 [m * 512]:
     strictly inside the box AND in a set occupancy cell, interior uint8 [m * 512]: strictly inside the box)."""
     n = _brick_shape('brickmesh_corners', shape)
-    _brick_dev('brickmesh_corners', ids=ids, binaries=binaries)
+    ids = _dev_tensor('brickmesh_corners', 'ids', ids, torch.int32, None, any_dtype_if_empty=True)
     occ, res = _brick_occ('brickmesh_corners', binaries)
     m = int(m)
     x01 = torch.empty(max(m, 0) * 512, 3, dtype=torch.float32, device=ids.device)
     sel = torch.empty(max(m, 0) * 512, dtype=torch.uint8, device=ids.device)
     interior = torch.empty_like(sel)
-    _call('perf_brickmesh_corners', _p(_brick_i32(ids, 'ids')) if ids.numel() else None, ids.numel(), int(first), m, *n, _p(occ), res, _p(x01) if m > 0 else None,
-          _p(sel) if m > 0 else None, _p(interior) if m > 0 else None, _stream())
+    _call('perf_brickmesh_corners', _pn(ids), ids.numel(), int(first), m, *n, _p(occ), res, _pn(x01), _pn(sel), _pn(interior), _stream())
     return x01, sel, interior
 
 
 def _brick_set(who, values, ids, table, shape):
+    """The stored corners, the ids and the table of a set of bricks -> (the lattice's cells, M, the (values, ids, table, M) of a library call)."""
     n = _brick_shape(who, shape)
-    _brick_dev(who, values=values, ids=ids, table=table)
+    values = _dev_tensor(who, 'values', values, torch.float32, None, any_dtype_if_empty=True)
+    ids = _dev_tensor(who, 'ids', ids, torch.int32, None, any_dtype_if_empty=True)
+    table = _dev_tensor(who, 'table', table, torch.int32, None)
     m = int(ids.numel())
     if values.numel() != m * 512 or tuple(table.shape) != tuple(v // 8 for v in n):
         raise _lib.PerfError(f'{who}: values {tuple(values.shape)}, ids {tuple(ids.shape)} and table {tuple(table.shape)} do not describe bricks of a lattice of {n} cells')
-    return n, m
+    return n, m, (_pn(values), _pn(ids), _p(table), m)
 
 
 def brickmesh_count(values, ids, table, shape, thr, fill, ws=None):
     """Classify the cells of the live bricks (perf_brickmesh_count) -> (counts, ws): counts = int64 [3] ON THE DEVICE (vertices, triangles,
     violations of the closure rule), ws = the int64 workspace brickmesh_write needs."""
-    n, m = _brick_set('brickmesh_count', values, ids, table, shape)
+    n, m, bricks = _brick_set('brickmesh_count', values, ids, table, shape)
     ws = _mesh_ws('perf_brickmesh_workspace_bytes', (*n, m), ws, table.device)
     counts = torch.empty(3, dtype=torch.int64, device=table.device)
-    _call('perf_brickmesh_count', _p(_f32(values, 'values')) if m else None, _p(_brick_i32(ids, 'ids')) if m else None, _p(_brick_i32(table, 'table')), m, *n, float(thr),
-          float(fill), _p(ws), ws.numel() * 8, _p(counts), _stream())
+    _call('perf_brickmesh_count', *bricks, *n, float(thr), float(fill), *_ws_args('brickmesh_count', ws), _p(counts), _stream())
     return counts, ws
 
 
 def brickmesh_write(values, ids, table, shape, thr, fill, lo, hi, ws, n_vertices, n_faces):
     """The vertices [n_vertices, 3] fp32, faces [n_faces, 3] int32 and cells [n_vertices] int64 (each vertex's linear cell of the virtual
     lattice) of what brickmesh_count classified into ws (perf_brickmesh_write).  Counts below the counted totals are refused."""
-    n, m = _brick_set('brickmesh_write', values, ids, table, shape)
+    n, m, bricks = _brick_set('brickmesh_write', values, ids, table, shape)
     lo3, hi3 = _box3('brickmesh_write', lo, hi)
     nv, nf = int(n_vertices), int(n_faces)
     vertices = torch.empty(nv, 3, dtype=torch.float32, device=table.device)
     faces = torch.empty(nf, 3, dtype=torch.int32, device=table.device)
     cells = torch.empty(nv, dtype=torch.int64, device=table.device)
-    _call('perf_brickmesh_write', _p(_f32(values, 'values')) if m else None, _p(_brick_i32(ids, 'ids')) if m else None, _p(_brick_i32(table, 'table')), m, *n, float(thr),
-          float(fill), lo3, hi3, _p(ws), ws.numel() * 8, _p(vertices) if nv else None, nv, _p(faces) if nf else None, nf,
-          _p(cells) if nv else None, _stream())
+    _call('perf_brickmesh_write', *bricks, *n, float(thr), float(fill), lo3, hi3, *_ws_args('brickmesh_write', ws), _pn(vertices), nv, _pn(faces), nf, _pn(cells), _stream())
     return vertices, faces, cells
 
 
 # ---- connected components of a triangle mesh (include/perf_hip_meshcc.h) ---------------------------------------------------------------
-def _cc_faces(who, faces, n_vertices):
-    if not faces.is_cuda:
-        raise _lib.PerfError(f'{who}: faces must be a CUDA tensor (there is no CPU path)')
-    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
-        raise _lib.PerfError(f'{who}: faces must be a contiguous int32 [F, 3] tensor, got {faces.dtype} {tuple(faces.shape)}')
-    n = int(n_vertices)
-    if n < 0 or n > _lib.MESHCC_MAX_VERTICES:
-        raise _lib.PerfError(f'{who}: {n} vertices are outside 0 .. 2^30')
-    return n, int(faces.shape[0])
-
-
-def _cc_labels(who, vertex_component, n, device):
-    if not vertex_component.is_cuda or vertex_component.device != device:
-        raise _lib.PerfError(f'{who}: vertex_component must be a CUDA tensor on the faces\' device')
-    if vertex_component.dtype != torch.int32 or tuple(vertex_component.shape) != (n,) or not vertex_component.is_contiguous():
-        raise _lib.PerfError(f'{who}: vertex_component must be a contiguous int32 [{n}] tensor, got {vertex_component.dtype} {tuple(vertex_component.shape)}')
-    return vertex_component
-
-
-def _cc_vertices(who, vertices, n, device):
-    if vertices is None:
-        return None
-    if not vertices.is_cuda or vertices.device != device:
-        raise _lib.PerfError(f'{who}: vertices must be a CUDA tensor on the faces\' device')
-    if tuple(vertices.shape) != (n, 3) or not vertices.is_contiguous():
-        raise _lib.PerfError(f'{who}: vertices must be a contiguous fp32 [{n}, 3] tensor, got {tuple(vertices.shape)}')
-    return _f32(vertices, 'vertices')
-
-
 def meshcc_label(faces, n_vertices, ws=None):
     """Label the connected components of faces int32 [F, 3] over n_vertices vertices (perf_meshcc_label) -> (vertex_component int32 [V],
     counts, ws): counts = int64 [2] ON THE DEVICE (C, the first face with an index outside [0, V) or -1)."""
-    n, f = _cc_faces('meshcc_label', faces, n_vertices)
+    n, f = _faces('meshcc_label', faces, n_vertices)
     ws = _mesh_ws('perf_meshcc_workspace_bytes', (n, f), ws, faces.device)
     vertex_component = torch.empty(n, dtype=torch.int32, device=faces.device)
     counts = torch.empty(2, dtype=torch.int64, device=faces.device)
-    _call('perf_meshcc_label', _p(faces) if f else None, f, n, _p(vertex_component) if n else None, _p(counts), _p(ws), ws.numel() * 8, _stream())
+    _call('perf_meshcc_label', _pn(faces), f, n, _pn(vertex_component), _p(counts), *_ws_args('meshcc_label', ws), _stream())
     return vertex_component, counts, ws
 
 
 def meshcc_stats(faces, vertex_component, n_components, vertices=None):
     """faces int64 [C], vertices int32 [C] and, with vertices fp32 [V, 3], signed volume float64 [C] (else None) of the components
     (perf_meshcc_stats)."""
-    n = int(vertex_component.numel())
-    _, f = _cc_faces('meshcc_stats', faces, n)
-    _cc_labels('meshcc_stats', vertex_component, n, faces.device)
-    vertices = _cc_vertices('meshcc_stats', vertices, n, faces.device)
+    n, f = _labelled_faces('meshcc_stats', faces, vertex_component, 'vertex_component')
+    vertices = _dev_tensor('meshcc_stats', 'vertices', vertices, torch.float32, (n, 3), faces.device)
     c = int(n_components)
     faces_per = torch.empty(c, dtype=torch.int64, device=faces.device)
     vertices_per = torch.empty(c, dtype=torch.int32, device=faces.device)
     volume = torch.empty(c, dtype=torch.float64, device=faces.device) if vertices is not None else None
-    _call('perf_meshcc_stats', _p(faces) if f else None, f, _p(vertices) if vertices is not None and n else None, n, _p(vertex_component) if n else None, c,
-          _p(faces_per) if c else None, _p(vertices_per) if c else None, _p(volume) if volume is not None and c else None, _stream())
+    _call('perf_meshcc_stats', _pn(faces), f, _pn(vertices), n, _pn(vertex_component), c, _pn(faces_per), _pn(vertices_per), _pn(volume), _stream())
     return faces_per, vertices_per, volume
-
-
-def _cc_keep(who, keep, device):
-    if not keep.is_cuda or keep.device != device:
-        raise _lib.PerfError(f'{who}: keep must be a CUDA tensor on the faces\' device')
-    if keep.dtype not in (torch.bool, torch.uint8) or keep.dim() != 1:
-        raise _lib.PerfError(f'{who}: keep must be bool or uint8 [C], got {keep.dtype} {tuple(keep.shape)}')
-    return _mask_u8(keep)
 
 
 def meshcc_filter_count(faces, vertex_component, keep, ws=None):
     """Rank the vertices and faces of the components keep [C] selects (perf_meshcc_filter_count) -> (counts, ws): counts = int64 [2] ON
     THE DEVICE (kept vertices, kept faces), ws = the workspace meshcc_filter_write needs."""
-    n = int(vertex_component.numel())
-    _, f = _cc_faces('meshcc_filter_count', faces, n)
-    _cc_labels('meshcc_filter_count', vertex_component, n, faces.device)
-    k = _cc_keep('meshcc_filter_count', keep, faces.device)
+    n, f = _labelled_faces('meshcc_filter_count', faces, vertex_component, 'vertex_component')
+    k = _mask_u8('meshcc_filter_count', 'keep', keep, ('C',), faces.device)
     ws = _mesh_ws('perf_meshcc_workspace_bytes', (n, f), ws, faces.device)
     counts = torch.empty(2, dtype=torch.int64, device=faces.device)
-    _call('perf_meshcc_filter_count', _p(faces) if f else None, f, _p(vertex_component) if n else None, n, _p(k) if k.numel() else None, k.numel(), _p(ws),
-          ws.numel() * 8, _p(counts), _stream())
+    _call('perf_meshcc_filter_count', _pn(faces), f, _pn(vertex_component), n, _pn(k), k.numel(), *_ws_args('meshcc_filter_count', ws), _p(counts), _stream())
     return counts, ws
 
 
 def meshcc_filter_write(faces, vertex_component, keep, ws, n_vertices_kept, n_faces_kept, vertices=None):
     """The kept faces int32 [F', 3] re-indexed, kept_vertex_index int32 [V'] and, with vertices, the kept vertices fp32 [V', 3] (else
     None) of what meshcc_filter_count ranked into ws (perf_meshcc_filter_write).  Counts below the counted totals are refused."""
-    n = int(vertex_component.numel())
-    _, f = _cc_faces('meshcc_filter_write', faces, n)
-    _cc_labels('meshcc_filter_write', vertex_component, n, faces.device)
-    k = _cc_keep('meshcc_filter_write', keep, faces.device)
-    vertices = _cc_vertices('meshcc_filter_write', vertices, n, faces.device)
-    nv, nf = int(n_vertices_kept), int(n_faces_kept)
-    vertices_out = torch.empty(nv, 3, dtype=torch.float32, device=faces.device) if vertices is not None else None
-    index = torch.empty(nv, dtype=torch.int32, device=faces.device)
-    faces_out = torch.empty(nf, 3, dtype=torch.int32, device=faces.device)
-    _call('perf_meshcc_filter_write', _p(faces) if f else None, f, _p(vertex_component) if n else None, n, _p(k) if k.numel() else None, k.numel(),
-          _p(vertices) if vertices is not None and n else None, _p(ws), ws.numel() * 8, _p(vertices_out) if vertices_out is not None and nv else None,
-          _p(index) if nv else None, nv, _p(faces_out) if nf else None, nf, _stream())
-    return vertices_out, faces_out, index
+    n, f = _labelled_faces('meshcc_filter_write', faces, vertex_component, 'vertex_component')
+    k = _mask_u8('meshcc_filter_write', 'keep', keep, ('C',), faces.device)
+    vertices = _dev_tensor('meshcc_filter_write', 'vertices', vertices, torch.float32, (n, 3), faces.device)
+    out, tail = _filtered(vertices, n_vertices_kept, n_faces_kept, faces.device)
+    _call('perf_meshcc_filter_write', _pn(faces), f, _pn(vertex_component), n, _pn(k), k.numel(), _pn(vertices), *_ws_args('meshcc_filter_write', ws), *tail, _stream())
+    return out
 
 
 # ---- cull the faces no registered panorama saw (include/perf_hip_meshvis.h) ------------------------------------------------------------
-def _vis_bits(who, name, bits, n, device):
-    if not bits.is_cuda or bits.device != device:
-        raise _lib.PerfError(f'{who}: {name} must be a CUDA tensor on the mesh\'s device')
-    if bits.dtype != torch.int64 or tuple(bits.shape) != (n,) or not bits.is_contiguous():
-        raise _lib.PerfError(f'{who}: {name} must be a contiguous int64 [{n}] tensor, got {bits.dtype} {tuple(bits.shape)}')
-    return bits
-
-
 def meshvis_views(poses, maps):
     """The device array of perf_meshvis_view of K panoramas -> (views int32 [K, 16] on the device, centres fp32 [K, 3], sizes: the host
     (height, width) pairs, maps: the tensors the descriptors point into, to be kept alive with them).  poses: K [4, 4] or [3, 4]
@@ -1052,85 +1092,53 @@ def meshvis_views(poses, maps):
 def meshvis_vertex_bits(vertices, views, sizes, tol, free_tol):
     """visible_bits, free_bits int64 [V] of vertices fp32 [V, 3] against the views of meshvis_views: ONE launch for all of them
     (perf_meshvis_vertex_bits)."""
-    if not vertices.is_cuda:
-        raise _lib.PerfError('meshvis_vertex_bits: vertices must be a CUDA tensor (there is no CPU path)')
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
-        raise _lib.PerfError(f'meshvis_vertex_bits: vertices must be a contiguous fp32 [V, 3] tensor, got {tuple(vertices.shape)}')
-    n, k = int(vertices.shape[0]), len(sizes)
-    if tuple(views.shape) != (k, 16) or views.dtype != torch.int32 or (k and views.device != vertices.device) or not views.is_contiguous():
-        raise _lib.PerfError(f'meshvis_vertex_bits: views must be the contiguous int32 [{k}, 16] tensor of meshvis_views on the vertices\' device')
+    vertices = _dev_tensor('meshvis_vertex_bits', 'vertices', vertices, torch.float32, ('V', 3), any_dtype_if_empty=True)
+    n = int(vertices.shape[0])
+    table = _views_table('meshvis_vertex_bits', views, sizes, vertices.device)
     visible = torch.empty(n, dtype=torch.int64, device=vertices.device)
     free = torch.empty(n, dtype=torch.int64, device=vertices.device)
-    flat = (ctypes.c_int32 * (2 * k))(*[v for hw in sizes for v in hw]) if k else None
-    _call('perf_meshvis_vertex_bits', _p(_f32(vertices, 'vertices')) if n else None, n, _p(views) if k else None, flat, k, float(tol), float(free_tol),
-          _p(visible) if n else None, _p(free) if n else None, _stream())
+    _call('perf_meshvis_vertex_bits', _pn(vertices), n, *table, float(tol), float(free_tol), _pn(visible), _pn(free), _stream())
     return visible, free
 
 
 def meshvis_face_keep(faces, vertices, visible_bits, free_bits, centres, facing=True, min_views=1, carve=False, flag=None):
     """face_keep uint8 [F] by the face rule of include/perf_hip_meshvis.h (perf_meshvis_face_keep) -> (face_keep, flag): flag = int64 [1]
     ON THE DEVICE, the smallest index of a face with an index outside [0, V) or -1 (an int64 [1] view to write it into may be passed)."""
-    n = int(vertices.shape[0])
-    _, f = _cc_faces('meshvis_face_keep', faces, n)
-    vertices = _cc_vertices('meshvis_face_keep', vertices, n, faces.device)
-    _vis_bits('meshvis_face_keep', 'visible_bits', visible_bits, n, faces.device)
-    _vis_bits('meshvis_face_keep', 'free_bits', free_bits, n, faces.device)
-    k = int(centres.shape[0])
-    if tuple(centres.shape) != (k, 3) or not centres.is_contiguous() or (k and not centres.is_cuda):
-        raise _lib.PerfError(f'meshvis_face_keep: centres must be a contiguous CUDA fp32 [K, 3] tensor, got {tuple(centres.shape)}')
+    vertices, n, f, _ = _mesh_head('meshvis_face_keep', vertices, faces)
+    visible_bits = _dev_tensor('meshvis_face_keep', 'visible_bits', visible_bits, torch.int64, (n,), faces.device)
+    free_bits = _dev_tensor('meshvis_face_keep', 'free_bits', free_bits, torch.int64, (n,), faces.device)
+    centres, k = _centres('meshvis_face_keep', centres)
     keep = torch.empty(f, dtype=torch.uint8, device=faces.device)
-    if flag is None:
-        flag = torch.empty(1, dtype=torch.int64, device=faces.device)
-    _call('perf_meshvis_face_keep', _p(faces) if f else None, f, _p(vertices) if n else None, n, _p(visible_bits) if n else None, _p(free_bits) if n else None,
-          _p(_f32(centres, 'centres')) if k else None, k, int(bool(facing)), int(min_views), int(bool(carve)), _p(keep) if f else None, _p(flag), _stream())
+    flag = _flag('meshvis_face_keep', 'flag', flag, 1, faces.device)
+    _call('perf_meshvis_face_keep', _pn(faces), f, _pn(vertices), n, _pn(visible_bits), _pn(free_bits), _pn(centres), k, int(bool(facing)), int(min_views),
+          int(bool(carve)), _pn(keep), _p(flag), _stream())
     return keep, flag
-
-
-def _vis_keep(who, face_keep, f, device):
-    if not face_keep.is_cuda or face_keep.device != device:
-        raise _lib.PerfError(f'{who}: face_keep must be a CUDA tensor on the faces\' device')
-    if face_keep.dtype not in (torch.bool, torch.uint8) or tuple(face_keep.shape) != (f,):
-        raise _lib.PerfError(f'{who}: face_keep must be bool or uint8 [{f}], got {face_keep.dtype} {tuple(face_keep.shape)}')
-    return _mask_u8(face_keep)
 
 
 def meshvis_filter_count(faces, n_vertices, face_keep, ws=None, counts=None):
     """Rank the faces face_keep [F] selects and the vertices they name (perf_meshvis_filter_count) -> (counts, ws): counts = int64 [2] ON
     THE DEVICE (kept vertices, kept faces; an int64 [2] view to write them into may be passed), ws = the workspace meshvis_filter_write
     needs."""
-    n, f = _cc_faces('meshvis_filter_count', faces, n_vertices)
-    k = _vis_keep('meshvis_filter_count', face_keep, f, faces.device)
+    n, f = _faces('meshvis_filter_count', faces, n_vertices)
+    k = _mask_u8('meshvis_filter_count', 'face_keep', face_keep, (f,), faces.device)
     ws = _mesh_ws('perf_meshvis_workspace_bytes', (n, f), ws, faces.device)
-    if counts is None:
-        counts = torch.empty(2, dtype=torch.int64, device=faces.device)
-    _call('perf_meshvis_filter_count', _p(faces) if f else None, f, n, _p(k) if f else None, _p(ws), ws.numel() * 8, _p(counts), _stream())
+    counts = _flag('meshvis_filter_count', 'counts', counts, 2, faces.device)
+    _call('perf_meshvis_filter_count', _pn(faces), f, n, _pn(k), *_ws_args('meshvis_filter_count', ws), _p(counts), _stream())
     return counts, ws
 
 
 def meshvis_filter_write(faces, n_vertices, face_keep, ws, n_vertices_kept, n_faces_kept, vertices=None):
     """The kept faces int32 [F', 3] re-indexed, kept_vertex_index int32 [V'] and, with vertices, the kept vertices fp32 [V', 3] (else
     None) of what meshvis_filter_count ranked into ws (perf_meshvis_filter_write).  Counts below the counted totals are refused."""
-    n, f = _cc_faces('meshvis_filter_write', faces, n_vertices)
-    k = _vis_keep('meshvis_filter_write', face_keep, f, faces.device)
-    vertices = _cc_vertices('meshvis_filter_write', vertices, n, faces.device)
-    nv, nf = int(n_vertices_kept), int(n_faces_kept)
-    vertices_out = torch.empty(nv, 3, dtype=torch.float32, device=faces.device) if vertices is not None else None
-    index = torch.empty(nv, dtype=torch.int32, device=faces.device)
-    faces_out = torch.empty(nf, 3, dtype=torch.int32, device=faces.device)
-    _call('perf_meshvis_filter_write', _p(faces) if f else None, f, n, _p(k) if f else None, _p(vertices) if vertices is not None and n else None, _p(ws),
-          ws.numel() * 8, _p(vertices_out) if vertices_out is not None and nv else None, _p(index) if nv else None, nv, _p(faces_out) if nf else None, nf, _stream())
-    return vertices_out, faces_out, index
+    n, f = _faces('meshvis_filter_write', faces, n_vertices)
+    k = _mask_u8('meshvis_filter_write', 'face_keep', face_keep, (f,), faces.device)
+    vertices = _dev_tensor('meshvis_filter_write', 'vertices', vertices, torch.float32, (n, 3), faces.device)
+    out, tail = _filtered(vertices, n_vertices_kept, n_faces_kept, faces.device)
+    _call('perf_meshvis_filter_write', _pn(faces), f, n, _pn(k), _pn(vertices), *_ws_args('meshvis_filter_write', ws), *tail, _stream())
+    return out
 
 
 # ---- simplify a mesh by vertex clustering (include/perf_hip_meshsimp.h) -----------------------------------------------------------------
-def _simp_vertices(who, vertices):
-    if not torch.is_tensor(vertices) or not vertices.is_cuda:
-        raise _lib.PerfError(f'{who}: vertices must be a CUDA tensor (there is no CPU path)')
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
-        raise _lib.PerfError(f'{who}: vertices must be a contiguous fp32 [V, 3] tensor, got {tuple(vertices.shape)}')
-    return _f32(vertices, 'vertices'), int(vertices.shape[0])
-
-
 def _simp_grid(who, lo, h, n):
     lo3, n3 = [float(v) for v in lo], [int(v) for v in n]
     if len(lo3) != 3 or len(n3) != 3:
@@ -1143,9 +1151,9 @@ def _simp_grid(who, lo, h, n):
 def meshsimp_bounds(vertices):
     """fp32 [6] ON THE DEVICE: the smallest x, y, z and the largest x, y, z among the finite coordinates of vertices fp32 [V, 3]
     (perf_meshsimp_bounds); (+inf x 3, -inf x 3) when there is none."""
-    vertices, n = _simp_vertices('meshsimp_bounds', vertices)
+    vertices = _dev_tensor('meshsimp_bounds', 'vertices', vertices, torch.float32, ('V', 3))
     bounds = torch.empty(6, dtype=torch.float32, device=vertices.device)
-    _call('perf_meshsimp_bounds', _p(vertices) if n else None, n, _p(bounds), _stream())
+    _call('perf_meshsimp_bounds', _pn(vertices), vertices.shape[0], _p(bounds), _stream())
     return bounds
 
 
@@ -1154,31 +1162,31 @@ def meshsimp_cluster(vertices, lo, h, n, n_faces=0, ws=None, counts=None):
     include/perf_hip_meshsimp.h (perf_meshsimp_cluster) -> (vertex_cluster int32 [V], counts, ws): counts = int64 [2] ON THE DEVICE (C, the
     first vertex with a coordinate that is not finite or -1; an int64 [2] view to write them into may be passed).  n_faces: the faces the
     workspace is to serve as well (meshsimp_faces)."""
-    vertices, nv = _simp_vertices('meshsimp_cluster', vertices)
+    vertices = _dev_tensor('meshsimp_cluster', 'vertices', vertices, torch.float32, ('V', 3))
+    nv = int(vertices.shape[0])
     lo3, h, n3 = _simp_grid('meshsimp_cluster', lo, h, n)
     ws = _mesh_ws('perf_meshsimp_workspace_bytes', (nv, int(n_faces)), ws, vertices.device)
     vertex_cluster = torch.empty(nv, dtype=torch.int32, device=vertices.device)
-    if counts is None:
-        counts = torch.empty(2, dtype=torch.int64, device=vertices.device)
-    _call('perf_meshsimp_cluster', _p(vertices) if nv else None, nv, int(n_faces), lo3, h, *n3, _p(vertex_cluster) if nv else None, _p(counts), _p(ws), ws.numel() * 8,
-          _stream())
+    counts = _flag('meshsimp_cluster', 'counts', counts, 2, vertices.device)
+    _call('perf_meshsimp_cluster', _pn(vertices), nv, int(n_faces), lo3, h, *n3, _pn(vertex_cluster), _p(counts), *_ws_args('meshsimp_cluster', ws), _stream())
     return vertex_cluster, counts, ws
 
 
 def meshsimp_place(vertices, lo, h, n, vertex_cluster, n_clusters, placement='mean'):
     """(cluster_vertices fp32 [C, 3], representative int32 [C]) of the labelling meshsimp_cluster made of the SAME vertices and grid
     (perf_meshsimp_place).  placement: 'mean' or 'member'."""
-    vertices, nv = _simp_vertices('meshsimp_place', vertices)
+    vertices = _dev_tensor('meshsimp_place', 'vertices', vertices, torch.float32, ('V', 3))
+    nv = int(vertices.shape[0])
     lo3, h, n3 = _simp_grid('meshsimp_place', lo, h, n)
-    _cc_labels('meshsimp_place', vertex_cluster, nv, vertices.device)
+    vertex_cluster = _dev_tensor('meshsimp_place', 'vertex_cluster', vertex_cluster, torch.int32, (nv,), vertices.device)
     if placement not in _lib.MESHSIMP_PLACEMENT:
         raise _lib.PerfError(f"meshsimp_place: placement is 'mean' or 'member', got {placement!r}")
     c = int(n_clusters)
     out = torch.empty(c, 3, dtype=torch.float32, device=vertices.device)
     representative = torch.empty(c, dtype=torch.int32, device=vertices.device)
     scratch = torch.empty(c * (_lib.MESHSIMP_SCRATCH_BYTES // 8), dtype=torch.int64, device=vertices.device)
-    _call('perf_meshsimp_place', _p(vertices) if nv else None, nv, lo3, h, *n3, _p(vertex_cluster) if nv else None, c, _lib.MESHSIMP_PLACEMENT[placement],
-          _p(out) if c else None, _p(representative) if c else None, _p(scratch) if c else None, scratch.numel() * 8, _stream())
+    _call('perf_meshsimp_place', _pn(vertices), nv, lo3, h, *n3, _pn(vertex_cluster), c, _lib.MESHSIMP_PLACEMENT[placement], _pn(out), _pn(representative),
+          _pn(scratch), scratch.numel() * 8, _stream())
     return out, representative
 
 
@@ -1187,9 +1195,7 @@ def meshsimp_faces(faces, vertex_cluster, dedupe='oriented', ws=None, flag=None)
     a face is kept unless two of its cluster ids are equal or (dedupe 'oriented' / 'unoriented') a face with a smaller index has its
     triple up to rotation / as a set; flag = int64 [1] ON THE DEVICE, the smallest index of a face with an index outside [0, V) or -1 (an
     int64 [1] view to write it into may be passed)."""
-    nv = int(vertex_cluster.numel()) if torch.is_tensor(vertex_cluster) else 0
-    _, f = _cc_faces('meshsimp_faces', faces, nv)
-    _cc_labels('meshsimp_faces', vertex_cluster, nv, faces.device)
+    nv, f = _labelled_faces('meshsimp_faces', faces, vertex_cluster, 'vertex_cluster')
     if dedupe not in _lib.MESHSIMP_DEDUPE:
         raise _lib.PerfError(f"meshsimp_faces: dedupe is 'oriented', 'unoriented' or None, got {dedupe!r}")
     if f > _lib.MESHSIMP_MAX_FACES:
@@ -1197,44 +1203,28 @@ def meshsimp_faces(faces, vertex_cluster, dedupe='oriented', ws=None, flag=None)
     ws = _mesh_ws('perf_meshsimp_workspace_bytes', (nv, f), ws, faces.device)
     remapped = torch.empty(f, 3, dtype=torch.int32, device=faces.device)
     keep = torch.empty(f, dtype=torch.uint8, device=faces.device)
-    if flag is None:
-        flag = torch.empty(1, dtype=torch.int64, device=faces.device)
-    _call('perf_meshsimp_faces', _p(faces) if f else None, f, _p(vertex_cluster) if nv else None, nv, _lib.MESHSIMP_DEDUPE[dedupe], _p(remapped) if f else None,
-          _p(keep) if f else None, _p(flag), _p(ws), ws.numel() * 8, _stream())
+    flag = _flag('meshsimp_faces', 'flag', flag, 1, faces.device)
+    _call('perf_meshsimp_faces', _pn(faces), f, _pn(vertex_cluster), nv, _lib.MESHSIMP_DEDUPE[dedupe], _pn(remapped), _pn(keep), _p(flag), *_ws_args('meshsimp_faces', ws),
+          _stream())
     return remapped, keep, flag
 
 
 # ---- quadric error placement of the clusters' vertices (include/perf_hip_meshquadric.h) ------------------------------------------------
-def _quadric_rows(who, t, name, dtype, shape, device):
-    if not torch.is_tensor(t) or not t.is_cuda or t.device != device:
-        raise _lib.PerfError(f'{who}: {name} must be a CUDA tensor on the vertices\' device (there is no CPU path)')
-    if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-        raise _lib.PerfError(f'{who}: {name} must be a contiguous {dtype} {list(shape)} tensor, got {t.dtype} {tuple(t.shape)}')
-    return t
-
-
 def meshquadric_sums(vertices, faces, lo, h, n, vertex_cluster, n_clusters, flags=None):
     """Stage A of include/perf_hip_meshquadric.h (perf_meshquadric_sums) -> (acc int64 [C, 9], flags): per cluster the int64 fixed-point
     sums (2^-40) of its members' quadrics, qA xx, xy, xz, yy, yz, zz then qb x, y, z, by integer atomics: exact in any order.  flags =
     int64 [2] ON THE DEVICE: the smallest index of a face with an index outside [0, V) or -1, then the smallest index of a face the
     2^60 rule skipped or -1 (an int64 [2] view to write them into may be passed)."""
-    vertices, nv = _simp_vertices('meshquadric_sums', vertices)
-    _, f = _cc_faces('meshquadric_sums', faces, nv)
-    if faces.device != vertices.device:
-        raise _lib.PerfError('meshquadric_sums: faces must be on the vertices\' device')
-    if f > _lib.MESHQUADRIC_MAX_FACES:
-        raise _lib.PerfError(f'meshquadric_sums: {f} faces are more than 2^31 - 1')
+    vertices, nv, f, mesh = _mesh_head('meshquadric_sums', vertices, faces, _lib.MESHQUADRIC_MAX_FACES)
     lo3, h, n3 = _simp_grid('meshquadric_sums', lo, h, n)
-    _cc_labels('meshquadric_sums', vertex_cluster, nv, vertices.device)
+    vertex_cluster = _dev_tensor('meshquadric_sums', 'vertex_cluster', vertex_cluster, torch.int32, (nv,), vertices.device)
     c = int(n_clusters)
     if c < 0 or c > nv:
         raise _lib.PerfError(f'meshquadric_sums: {c} clusters, the mesh has {nv} vertices')
     acc = torch.empty(c, _lib.MESHQUADRIC_TERMS, dtype=torch.int64, device=vertices.device)
-    if flags is None:
-        flags = torch.empty(2, dtype=torch.int64, device=vertices.device)
-    _quadric_rows('meshquadric_sums', flags, 'flags', torch.int64, (2,), vertices.device)
-    _call('perf_meshquadric_sums', _p(vertices) if nv else None, nv, _p(faces) if f else None, f, lo3, h, *n3, _p(vertex_cluster) if nv else None, c,
-          _p(acc) if c else None, ctypes.c_void_p(flags.data_ptr()), ctypes.c_void_p(flags.data_ptr() + 8), _stream())
+    flags = _flag('meshquadric_sums', 'flags', _dev_tensor('meshquadric_sums', 'flags', flags, torch.int64, (2,), vertices.device), 2, vertices.device)
+    _call('perf_meshquadric_sums', *mesh, lo3, h, *n3, _pn(vertex_cluster), c, _pn(acc), ctypes.c_void_p(flags.data_ptr()), ctypes.c_void_p(flags.data_ptr() + 8),
+          _stream())
     return acc, flags
 
 
@@ -1242,18 +1232,17 @@ def meshquadric_place(vertices, lo, h, n, anchor, representative, acc):
     """Stage B of include/perf_hip_meshquadric.h (perf_meshquadric_place) -> cluster vertices fp32 [C, 3]: the minimiser of the cluster's
     summed quadric, regularised towards anchor fp32 [C, 3] (the 'mean' placement) and clamped to the cell of vertices[representative];
     anchor's row, bit for bit, where the cluster has no face or no solve."""
-    vertices, nv = _simp_vertices('meshquadric_place', vertices)
+    vertices = _dev_tensor('meshquadric_place', 'vertices', vertices, torch.float32, ('V', 3))
+    nv, dev = int(vertices.shape[0]), vertices.device
     lo3, h, n3 = _simp_grid('meshquadric_place', lo, h, n)
-    c = int(acc.shape[0]) if torch.is_tensor(acc) and acc.dim() == 2 else -1
-    if c < 0 or c > nv:
+    acc = _dev_tensor('meshquadric_place', 'acc', acc, torch.int64, ('C', _lib.MESHQUADRIC_TERMS), dev)
+    c = int(acc.shape[0])
+    if c > nv:
         raise _lib.PerfError(f'meshquadric_place: acc must be an int64 [C, {_lib.MESHQUADRIC_TERMS}] tensor with C <= {nv} vertices')
-    dev = vertices.device
-    _quadric_rows('meshquadric_place', acc, 'acc', torch.int64, (c, _lib.MESHQUADRIC_TERMS), dev)
-    _quadric_rows('meshquadric_place', anchor, 'anchor', torch.float32, (c, 3), dev)
-    _quadric_rows('meshquadric_place', representative, 'representative', torch.int32, (c,), dev)
+    anchor = _dev_tensor('meshquadric_place', 'anchor', anchor, torch.float32, (c, 3), dev)
+    representative = _dev_tensor('meshquadric_place', 'representative', representative, torch.int32, (c,), dev)
     out = torch.empty(c, 3, dtype=torch.float32, device=dev)
-    _call('perf_meshquadric_place', _p(vertices) if nv else None, nv, lo3, h, *n3, _p(anchor) if c else None, _p(representative) if c else None,
-          _p(acc) if c else None, c, _p(out) if c else None, _stream())
+    _call('perf_meshquadric_place', _pn(vertices), nv, lo3, h, *n3, _pn(anchor), _pn(representative), _pn(acc), c, _pn(out), _stream())
     return out
 
 
@@ -1262,28 +1251,19 @@ def meshcolor_normal_sums(vertices, faces, scale_log2, flag=None):
     """The faces' area-weighted normals (double, times 2^scale_log2, rounded to int64) summed at their vertices by integer atomics
     (perf_meshcolor_normal_sums) -> (acc int64 [V, 3], flag): flag = int64 [1] ON THE DEVICE, the smallest index of a face with an index
     outside [0, V) or -1 (an int64 [1] view to write it into may be passed)."""
-    vertices, nv = _simp_vertices('meshcolor_normal_sums', vertices)
-    _, f = _cc_faces('meshcolor_normal_sums', faces, nv)
-    if faces.device != vertices.device:
-        raise _lib.PerfError('meshcolor_normal_sums: faces must be on the vertices\' device')
-    if f > _lib.MESHCOLOR_MAX_FACES:
-        raise _lib.PerfError(f'meshcolor_normal_sums: {f} faces are more than 2^31 - 1')
+    vertices, nv, f, mesh = _mesh_head('meshcolor_normal_sums', vertices, faces, _lib.MESHCOLOR_MAX_FACES)
     acc = torch.empty(nv, 3, dtype=torch.int64, device=vertices.device)
-    if flag is None:
-        flag = torch.empty(1, dtype=torch.int64, device=vertices.device)
-    _call('perf_meshcolor_normal_sums', _p(vertices) if nv else None, nv, _p(faces) if f else None, f, int(scale_log2), _p(acc) if nv else None, _p(flag), _stream())
+    flag = _flag('meshcolor_normal_sums', 'flag', flag, 1, vertices.device)
+    _call('perf_meshcolor_normal_sums', *mesh, int(scale_log2), _pn(acc), _p(flag), _stream())
     return acc, flag
 
 
 def meshcolor_normals(acc):
     """Unit normals fp32 [V, 3] of the sums of meshcolor_normal_sums, exactly 0 where a sum is (perf_meshcolor_normals)."""
-    if not torch.is_tensor(acc) or not acc.is_cuda:
-        raise _lib.PerfError('meshcolor_normals: acc must be a CUDA tensor (there is no CPU path)')
-    if acc.dtype != torch.int64 or acc.dim() != 2 or acc.shape[1] != 3 or not acc.is_contiguous():
-        raise _lib.PerfError(f'meshcolor_normals: acc must be a contiguous int64 [V, 3] tensor, got {acc.dtype} {tuple(acc.shape)}')
+    acc = _dev_tensor('meshcolor_normals', 'acc', acc, torch.int64, ('V', 3))
     n = int(acc.shape[0])
     normals = torch.empty(n, 3, dtype=torch.float32, device=acc.device)
-    _call('perf_meshcolor_normals', _p(acc) if n else None, n, _p(normals) if n else None, _stream())
+    _call('perf_meshcolor_normals', _pn(acc), n, _pn(normals), _stream())
     return normals
 
 
@@ -1308,30 +1288,17 @@ def meshcolor_blend(vertices, normals, views, sizes, map_pointers, tol, facing=T
     """(colors fp32 [V, 3], weight fp32 [V], used_bits int64 [V], best_view int8 [V]) of vertices fp32 [V, 3] against the views of
     meshvis_views and the colour maps of meshcolor_maps by the rule of include/perf_hip_meshcolor.h: ONE launch for all views
     (perf_meshcolor_blend).  normals fp32 [V, 3] are read only with facing; fallback fp32 [V, 3] or None."""
-    vertices, n = _simp_vertices('meshcolor_blend', vertices)
-    dev, k = vertices.device, len(sizes)
-    if tuple(views.shape) != (k, 16) or views.dtype != torch.int32 or (k and views.device != dev) or not views.is_contiguous():
-        raise _lib.PerfError(f'meshcolor_blend: views must be the contiguous int32 [{k}, 16] tensor of meshvis_views on the vertices\' device')
-    if tuple(map_pointers.shape) != (k,) or map_pointers.dtype != torch.int64 or (k and map_pointers.device != dev):
-        raise _lib.PerfError(f'meshcolor_blend: map_pointers must be the int64 [{k}] tensor of meshcolor_maps on the vertices\' device')
-    if select not in _lib.MESHCOLOR_SELECT:
-        raise _lib.PerfError(f"meshcolor_blend: select is 'blend' or 'best', got {select!r}")
+    vertices = _dev_tensor('meshcolor_blend', 'vertices', vertices, torch.float32, ('V', 3))
+    n, dev = int(vertices.shape[0]), vertices.device
     if facing and normals is None:
         raise _lib.PerfError('meshcolor_blend: facing needs normals')
-    normals = _cc_vertices('meshcolor_blend', normals, n, dev) if facing else None
-    fallback = _cc_vertices('meshcolor_blend', fallback, n, dev)
-    fill3 = [float(v) for v in fill]
-    if len(fill3) != 3:
-        raise _lib.PerfError('meshcolor_blend: fill holds three values')
+    normals = _dev_tensor('meshcolor_blend', "the vertices' normals", normals, torch.float32, (n, 3), dev) if facing else None
+    blend = _blend_args('meshcolor_blend', n, dev, views, sizes, map_pointers, tol, facing, power, select, fallback, fill)
     colors = torch.empty(n, 3, dtype=torch.float32, device=dev)
     weight = torch.empty(n, dtype=torch.float32, device=dev)
     used = torch.empty(n, dtype=torch.int64, device=dev)
     best = torch.empty(n, dtype=torch.int8, device=dev)
-    flat = (ctypes.c_int32 * (2 * k))(*[v for hw in sizes for v in hw]) if k else None
-    _call('perf_meshcolor_blend', _p(vertices) if n else None, _p(normals) if normals is not None and n else None, n, _p(views) if k else None,
-          _p(map_pointers) if k else None, flat, k, float(tol), int(bool(facing)), int(power), _lib.MESHCOLOR_SELECT[select],
-          _p(fallback) if fallback is not None and n else None, (ctypes.c_float * 3)(*fill3), _p(colors) if n else None, _p(weight) if n else None,
-          _p(used) if n else None, _p(best) if n else None, _stream())
+    _call('perf_meshcolor_blend', _pn(vertices), _pn(normals), n, *blend, _pn(colors), _pn(weight), _pn(used), _pn(best), _stream())
     return colors, weight, used, best
 
 
@@ -1348,13 +1315,11 @@ def _tex_layout(who, n_faces, size, tile):
 
 
 def _tex_mesh(who, vertices, normals, faces, size, tile):
-    vertices, nv = _simp_vertices(who, vertices)
-    _, f = _cc_faces(who, faces, nv)
-    if faces.device != vertices.device:
-        raise _lib.PerfError(f'{who}: faces must be on the vertices\' device')
+    """The head of a mesh in an atlas -> (vertices, V, S, the (vertices, V, normals, faces, F, S, T) a library call begins with)."""
+    vertices, nv, f, (pv, _, pf, _) = _mesh_head(who, vertices, faces)
     s, t = _tex_layout(who, f, size, tile)
-    normals = _cc_vertices(who, normals, nv, vertices.device)
-    return vertices, nv, f, s, t, (_p(vertices) if nv else None, nv, _p(normals) if normals is not None and nv else None, _p(faces) if f else None, f, s, t)
+    normals = _dev_tensor(who, "the vertices' normals", normals, torch.float32, (nv, 3), vertices.device)
+    return vertices, nv, s, (pv, nv, _pn(normals), pf, f, s, t)
 
 
 def meshtex_uv(n_faces, size, tile, device='cuda'):
@@ -1364,7 +1329,7 @@ def meshtex_uv(n_faces, size, tile, device='cuda'):
     if torch.device(device).type != 'cuda':
         raise _lib.PerfError('meshtex_uv: device must be a CUDA device (there is no CPU path)')
     uv = torch.empty(f, 3, 2, dtype=torch.float32, device=device)
-    _call('perf_meshtex_uv', f, s, t, _p(uv) if f else None, _stream())
+    _call('perf_meshtex_uv', f, s, t, _pn(uv), _stream())
     return uv
 
 
@@ -1372,14 +1337,13 @@ def meshtex_points(vertices, faces, size, tile, normals=None, flag=None):
     """The texels' points of the atlas (perf_meshtex_points) -> (points fp32 [S * S, 3], point_normals fp32 [S * S, 3], face_of int32
     [S * S], coverage uint8 [S * S], flag): normals fp32 [V, 3] are interpolated, None takes the faces' own; flag = int64 [1] ON THE DEVICE,
     the smallest index of a face with an index outside [0, V) or -1 (an int64 [1] view to write it into may be passed)."""
-    vertices, nv, f, s, t, head = _tex_mesh('meshtex_points', vertices, normals, faces, size, tile)
+    vertices, nv, s, head = _tex_mesh('meshtex_points', vertices, normals, faces, size, tile)
     dev = vertices.device
     points = torch.empty(s * s, 3, dtype=torch.float32, device=dev)
     point_normals = torch.empty(s * s, 3, dtype=torch.float32, device=dev)
     face_of = torch.empty(s * s, dtype=torch.int32, device=dev)
     coverage = torch.empty(s * s, dtype=torch.uint8, device=dev)
-    if flag is None:
-        flag = torch.empty(1, dtype=torch.int64, device=dev)
+    flag = _flag('meshtex_points', 'flag', flag, 1, dev)
     _call('perf_meshtex_points', *head, _p(points), _p(point_normals), _p(face_of), _p(coverage), _p(flag), _stream())
     return points, point_normals, face_of, coverage, flag
 
@@ -1389,42 +1353,19 @@ def meshtex_bake(vertices, faces, size, tile, views, sizes, map_pointers, tol, n
     """The fused bake (perf_meshtex_bake): the texels' points through the blend of include/perf_hip_meshcolor.h in ONE launch -> (image fp32
     [S, S, 3], weight fp32 [S, S], used_bits int64 [S, S], coverage uint8 [S, S], flag).  views, sizes, map_pointers: of meshvis_views and
     meshcolor_maps; normals, fallback: fp32 [V, 3] or None."""
-    vertices, nv, f, s, t, head = _tex_mesh('meshtex_bake', vertices, normals, faces, size, tile)
-    dev, k = vertices.device, len(sizes)
-    if tuple(views.shape) != (k, 16) or views.dtype != torch.int32 or (k and views.device != dev) or not views.is_contiguous():
-        raise _lib.PerfError(f'meshtex_bake: views must be the contiguous int32 [{k}, 16] tensor of meshvis_views on the vertices\' device')
-    if tuple(map_pointers.shape) != (k,) or map_pointers.dtype != torch.int64 or (k and map_pointers.device != dev):
-        raise _lib.PerfError(f'meshtex_bake: map_pointers must be the int64 [{k}] tensor of meshcolor_maps on the vertices\' device')
-    if select not in _lib.MESHCOLOR_SELECT:
-        raise _lib.PerfError(f"meshtex_bake: select is 'blend' or 'best', got {select!r}")
-    fallback = _cc_vertices('meshtex_bake', fallback, nv, dev)
-    fill3 = [float(v) for v in fill]
-    if len(fill3) != 3:
-        raise _lib.PerfError('meshtex_bake: fill holds three values')
+    vertices, nv, s, head = _tex_mesh('meshtex_bake', vertices, normals, faces, size, tile)
+    dev = vertices.device
+    blend = _blend_args('meshtex_bake', nv, dev, views, sizes, map_pointers, tol, facing, power, select, fallback, fill)
     image = torch.empty(s, s, 3, dtype=torch.float32, device=dev)
     weight = torch.empty(s, s, dtype=torch.float32, device=dev)
     used = torch.empty(s, s, dtype=torch.int64, device=dev)
     coverage = torch.empty(s, s, dtype=torch.uint8, device=dev)
-    if flag is None:
-        flag = torch.empty(1, dtype=torch.int64, device=dev)
-    flat = (ctypes.c_int32 * (2 * k))(*[v for hw in sizes for v in hw]) if k else None
-    _call('perf_meshtex_bake', *head, _p(views) if k else None, _p(map_pointers) if k else None, flat, k, float(tol), int(bool(facing)), int(power),
-          _lib.MESHCOLOR_SELECT[select], _p(fallback) if fallback is not None and nv else None, (ctypes.c_float * 3)(*fill3), _p(image), _p(weight), _p(used),
-          _p(coverage), _p(flag), _stream())
+    flag = _flag('meshtex_bake', 'flag', flag, 1, dev)
+    _call('perf_meshtex_bake', *head, *blend, _p(image), _p(weight), _p(used), _p(coverage), _p(flag), _stream())
     return image, weight, used, coverage, flag
 
 
 # ---- rays against a mesh on a uniform grid: closest hit, any hit, segment occlusion (include/perf_hip_meshray.h) -------------------------
-def _ray_mesh(who, vertices, faces):
-    vertices, nv = _simp_vertices(who, vertices)
-    _, f = _cc_faces(who, faces, nv)
-    if faces.device != vertices.device:
-        raise _lib.PerfError(f'{who}: faces must be on the vertices\' device')
-    if f > _lib.MESHRAY_MAX_FACES:
-        raise _lib.PerfError(f'{who}: {f} faces are more than 2^31 - 1')
-    return vertices, nv, f, (_p(vertices) if nv else None, nv, _p(faces) if f else None, f)
-
-
 def _ray_box(who, origin, cell, dims):
     """(origin fp32 [3], cell fp32, dims int32 [3]) as the library takes them, and the number of cells."""
     o3, d3 = [float(v) for v in origin], [int(v) for v in dims]
@@ -1435,25 +1376,24 @@ def _ray_box(who, origin, cell, dims):
     return ((ctypes.c_float * 3)(*o3), float(cell), (ctypes.c_int32 * 3)(*d3)), d3[0] * d3[1] * d3[2]
 
 
-def _ray_lists(who, offsets, refs, n_cells, device):
-    for name, t, n in (('offsets', offsets, n_cells), ('refs', refs, None)):
-        if not torch.is_tensor(t) or not t.is_cuda or t.device != device:
-            raise _lib.PerfError(f'{who}: {name} must be a CUDA tensor on the mesh\'s device')
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or (n is not None and t.numel() != n):
-            raise _lib.PerfError(f'{who}: {name} must be a contiguous int32 [{n if n is not None else "R"}] tensor, got {t.dtype} {tuple(t.shape)}')
-    r = int(refs.numel())
-    return _p(offsets), _p(refs) if r else None, r
+def _ray_grid(who, vertices, faces, origin, cell, dims, offsets, refs):
+    """A mesh in its grid of face lists -> (vertices, V, the arguments a library call begins with, from the vertices to the number of
+    references)."""
+    vertices, nv, f, mesh = _mesh_head(who, vertices, faces, _lib.MESHRAY_MAX_FACES)
+    box, n_cells = _ray_box(who, origin, cell, dims)
+    offsets = _dev_tensor(who, 'offsets', offsets, torch.int32, (n_cells,), vertices.device)
+    refs = _dev_tensor(who, 'refs', refs, torch.int32, ('R',), vertices.device)
+    return vertices, nv, (*mesh, *box, _p(offsets), _pn(refs), int(refs.numel()))
 
 
 def meshray_grid_count(vertices, faces, origin, cell, dims, flag=None):
     """How many faces each cell of the grid (origin [3], cell edge, dims [3]) lists, by the range rule of include/perf_hip_meshray.h
     (perf_meshray_grid_count) -> (counts int32 [nx * ny * nz], flag): flag = int64 [1] ON THE DEVICE, the smallest index of a face with an
     index outside [0, V) or a vertex that is not finite, or -1 (an int64 [1] view to write it into may be passed)."""
-    vertices, nv, f, mesh = _ray_mesh('meshray_grid_count', vertices, faces)
+    vertices, nv, f, mesh = _mesh_head('meshray_grid_count', vertices, faces, _lib.MESHRAY_MAX_FACES)
     box, n_cells = _ray_box('meshray_grid_count', origin, cell, dims)
     counts = torch.empty(n_cells, dtype=torch.int32, device=vertices.device)
-    if flag is None:
-        flag = torch.empty(1, dtype=torch.int64, device=vertices.device)
+    flag = _flag('meshray_grid_count', 'flag', flag, 1, vertices.device)
     _call('perf_meshray_grid_count', *mesh, *box, _p(counts), _p(flag), _stream())
     return counts, flag
 
@@ -1461,35 +1401,24 @@ def meshray_grid_count(vertices, faces, origin, cell, dims, flag=None):
 def meshray_grid_write(vertices, faces, origin, cell, dims, counts, offsets, n_refs):
     """refs int32 [n_refs]: the faces of every cell, cell c's at offsets[c] .. offsets[c] + its count, in no particular order
     (perf_meshray_grid_write).  counts: what meshray_grid_count returned, left 0; offsets: their exclusive scan; n_refs: its total."""
-    vertices, nv, f, mesh = _ray_mesh('meshray_grid_write', vertices, faces)
+    vertices, nv, f, mesh = _mesh_head('meshray_grid_write', vertices, faces, _lib.MESHRAY_MAX_FACES)
     box, n_cells = _ray_box('meshray_grid_write', origin, cell, dims)
-    for name, t in (('counts', counts), ('offsets', offsets)):
-        if not torch.is_tensor(t) or not t.is_cuda or t.device != vertices.device or t.dtype != torch.int32 or tuple(t.shape) != (n_cells,) or not t.is_contiguous():
-            raise _lib.PerfError(f'meshray_grid_write: {name} must be a contiguous CUDA int32 [{n_cells}] tensor on the mesh\'s device')
+    counts = _dev_tensor('meshray_grid_write', 'counts', counts, torch.int32, (n_cells,), vertices.device)
+    offsets = _dev_tensor('meshray_grid_write', 'offsets', offsets, torch.int32, (n_cells,), vertices.device)
     r = int(n_refs)
     refs = torch.empty(max(r, 0), dtype=torch.int32, device=vertices.device)
-    _call('perf_meshray_grid_write', *mesh, *box, _p(counts), _p(offsets), r, _p(refs) if r > 0 else None, int(refs.numel()), _stream())
+    _call('perf_meshray_grid_write', *mesh, *box, _p(counts), _p(offsets), r, _pn(refs), int(refs.numel()), _stream())
     return refs
-
-
-def _rays(who, name, t, device, n=None):
-    if not torch.is_tensor(t) or not t.is_cuda or t.device != device:
-        raise _lib.PerfError(f'{who}: {name} must be a CUDA tensor on the mesh\'s device (there is no CPU path)')
-    if t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous() or (n is not None and t.shape[0] != n):
-        raise _lib.PerfError(f'{who}: {name} must be a contiguous fp32 [{"N" if n is None else n}, 3] tensor, got {tuple(t.shape)}')
-    return _f32(t, name)
 
 
 def meshray_cast(vertices, faces, origin, cell, dims, offsets, refs, rays_o, rays_d, t_min=0.0, t_max=float('inf'), any_hit=False, uv=True):
     """The closest hit of every ray -> (t fp32 [N], face int32 [N], u, v fp32 [N] or None without uv), or with any_hit the uint8 [N] flag
     alone, by the rule of include/perf_hip_meshray.h over the grid meshray_grid_write made of the SAME mesh (perf_meshray_cast)."""
-    vertices, nv, f, mesh = _ray_mesh('meshray_cast', vertices, faces)
-    box, n_cells = _ray_box('meshray_cast', origin, cell, dims)
-    lists = _ray_lists('meshray_cast', offsets, refs, n_cells, vertices.device)
-    rays_o = _rays('meshray_cast', 'rays_o', rays_o, vertices.device)
-    n = int(rays_o.shape[0])
-    rays_d = _rays('meshray_cast', 'rays_d', rays_d, vertices.device, n)
+    vertices, nv, grid = _ray_grid('meshray_cast', vertices, faces, origin, cell, dims, offsets, refs)
     dev = vertices.device
+    rays_o = _dev_tensor('meshray_cast', 'rays_o', rays_o, torch.float32, ('N', 3), dev)
+    n = int(rays_o.shape[0])
+    rays_d = _dev_tensor('meshray_cast', 'rays_d', rays_d, torch.float32, (n, 3), dev)
     hit = t = face = u = v = None
     if any_hit:
         hit = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -1497,26 +1426,21 @@ def meshray_cast(vertices, faces, origin, cell, dims, offsets, refs, rays_o, ray
         t, face = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
         if uv:
             u, v = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
-    ptr = lambda x: _p(x) if x is not None and n else None
-    _call('perf_meshray_cast', *mesh, *box, *lists, ptr(rays_o), ptr(rays_d), n, float(t_min), float(t_max), int(bool(any_hit)), ptr(t), ptr(face), ptr(u), ptr(v),
-          ptr(hit), _stream())
+    _call('perf_meshray_cast', *grid, _pn(rays_o), _pn(rays_d), n, float(t_min), float(t_max), int(bool(any_hit)), _pn(t), _pn(face), _pn(u), _pn(v), _pn(hit),
+          _stream())
     return hit if any_hit else (t, face, u, v)
 
 
 def meshray_occluded(vertices, faces, origin, cell, dims, offsets, refs, centres, mask_bits):
     """occluded_bits int64 [V]: bit k iff bit k of mask_bits is set and a face that does not name the vertex cuts the segment from the vertex
     to centres[k] (fp32 [K, 3], K <= 64) at a strict 0 < t < 1 (perf_meshray_occluded)."""
-    vertices, nv, f, mesh = _ray_mesh('meshray_occluded', vertices, faces)
-    box, n_cells = _ray_box('meshray_occluded', origin, cell, dims)
-    lists = _ray_lists('meshray_occluded', offsets, refs, n_cells, vertices.device)
-    if not torch.is_tensor(centres) or centres.dim() != 2 or centres.shape[1] != 3 or not centres.is_contiguous() or (centres.shape[0] and not centres.is_cuda):
-        raise _lib.PerfError('meshray_occluded: centres must be a contiguous CUDA fp32 [K, 3] tensor')
-    k = int(centres.shape[0])
+    vertices, nv, grid = _ray_grid('meshray_occluded', vertices, faces, origin, cell, dims, offsets, refs)
+    centres, k = _centres('meshray_occluded', centres)
     if k > _lib.MESHRAY_MAX_VIEWS:
         raise _lib.PerfError(f'meshray_occluded: {k} views are more than {_lib.MESHRAY_MAX_VIEWS} (a vertex has one bit per view in a 64-bit word)')
-    _vis_bits('meshray_occluded', 'mask_bits', mask_bits, nv, vertices.device)
+    mask_bits = _dev_tensor('meshray_occluded', 'mask_bits', mask_bits, torch.int64, (nv,), vertices.device)
     out = torch.empty(nv, dtype=torch.int64, device=vertices.device)
-    _call('perf_meshray_occluded', *mesh, *box, *lists, _p(_f32(centres, 'centres')) if k else None, k, _p(mask_bits) if nv else None, _p(out) if nv else None, _stream())
+    _call('perf_meshray_occluded', *grid, _pn(centres), k, _pn(mask_bits), _pn(out), _stream())
     return out
 
 

@@ -5,6 +5,7 @@ module raises.  Build the library with `python -m perf_amd.build` (or __graft_en
 """
 import ctypes
 import os
+from collections import namedtuple
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -356,28 +357,39 @@ def _expects(label):
     return label + ' version {has}, this binding expects {want}'
 
 
-# The units of the library, each versioned on its own: (signatures, version function, the version this binding was written against, what
-# a mismatch is reported as after "<library> has ", ((size function, the bytes this binding expects), ...)).  A new unit adds one entry.
+Unit = namedtuple('Unit', 'name version sigs mismatch sizes header record macro version_fn')
+
+
+def _unit(name, version, sigs, mismatch, sizes=()):
+    """One separately versioned C ABI of the library: its name, the version this binding was written against, its signatures, what a
+    mismatch is reported as after "<library> has ", ((size function, the bytes this binding expects), ...).  The header and its recorded
+    digest (both in include/), the version macro and the version function follow from the name; the core, perf_hip.h, is the one
+    exception."""
+    stem, part = ('perf_hip', '') if name == 'core' else ('perf_hip_' + name, name + '_')
+    return Unit(name, version, sigs, mismatch, sizes, stem + '.h', stem + '.abi.json', f'PERF_{part.upper()}ABI_VERSION', f'perf_{part}version')
+
+
+# The units of the library.  tools/abi_digest.py, perf_amd/build.py and tests/test_abi_units.py read this table: a new unit adds one row.
 _UNITS = (
-    (_SIGS, 'perf_version', ABI_VERSION, _expects('ABI'), ()),
-    (_SIGS_EXT, 'perf_ext_version', EXT_ABI_VERSION, _expects('extension ABI'), ()),
-    (_SIGS_SPHERE, 'perf_sphere_version', SPHERE_ABI_VERSION, _expects('sphere-field ABI'), ()),
-    (_SIGS_PAIR, 'perf_pair_version', PAIR_ABI_VERSION, _expects('pair-table ABI'), ()),
-    (_SIGS_JOINT, 'perf_joint_version', JOINT_ABI_VERSION, _expects('joint-alignment ABI'), ()),
-    (_SIGS_MESH, 'perf_mesh_version', MESH_ABI_VERSION, _expects('mesh ABI'), ()),
-    (_SIGS_BRICKMESH, 'perf_brickmesh_version', BRICKMESH_ABI_VERSION, _expects('brick-mesh ABI'), ()),
-    (_SIGS_MESHCC, 'perf_meshcc_version', MESHCC_ABI_VERSION, _expects('mesh-component ABI'), ()),
-    (_SIGS_MESHVIS, 'perf_meshvis_version', MESHVIS_ABI_VERSION,
-     'visibility-cull ABI version {has} and a view of {has_sizes[0]} bytes, this binding expects {want} and {want_sizes[0]}',
-     (('perf_meshvis_sizeof_view', MESHVIS_VIEW_BYTES),)),
-    (_SIGS_MESHSIMP, 'perf_meshsimp_version', MESHSIMP_ABI_VERSION, _expects('mesh-simplification ABI'), ()),
-    (_SIGS_MESHCOLOR, 'perf_meshcolor_version', MESHCOLOR_ABI_VERSION, _expects('mesh-colouring ABI'), ()),
-    (_SIGS_MESHRAY, 'perf_meshray_version', MESHRAY_ABI_VERSION, _expects('mesh ray-casting ABI'), ()),
-    (_SIGS_MESHTEX, 'perf_meshtex_version', MESHTEX_ABI_VERSION, _expects('texture-atlas ABI'), ()),
-    (_SIGS_MESHQUADRIC, 'perf_meshquadric_version', MESHQUADRIC_ABI_VERSION, _expects('quadric-placement ABI'), ()),
-    (_SIGS_RIDERS, 'perf_riders_version', RIDERS_ABI_VERSION, 'step-rider ABI version {has} or other argument blocks than this binding ({want})',
-     (('perf_sizeof_rider_draw', ctypes.sizeof(RiderDraw)), ('perf_sizeof_rider_count', ctypes.sizeof(RiderCount)),
-      ('perf_sizeof_rider_write', ctypes.sizeof(RiderWrite)))),
+    _unit('core', ABI_VERSION, _SIGS, _expects('ABI')),
+    _unit('ext', EXT_ABI_VERSION, _SIGS_EXT, _expects('extension ABI')),
+    _unit('sphere', SPHERE_ABI_VERSION, _SIGS_SPHERE, _expects('sphere-field ABI')),
+    _unit('pair', PAIR_ABI_VERSION, _SIGS_PAIR, _expects('pair-table ABI')),
+    _unit('joint', JOINT_ABI_VERSION, _SIGS_JOINT, _expects('joint-alignment ABI')),
+    _unit('mesh', MESH_ABI_VERSION, _SIGS_MESH, _expects('mesh ABI')),
+    _unit('brickmesh', BRICKMESH_ABI_VERSION, _SIGS_BRICKMESH, _expects('brick-mesh ABI')),
+    _unit('meshcc', MESHCC_ABI_VERSION, _SIGS_MESHCC, _expects('mesh-component ABI')),
+    _unit('meshvis', MESHVIS_ABI_VERSION, _SIGS_MESHVIS,
+          'visibility-cull ABI version {has} and a view of {has_sizes[0]} bytes, this binding expects {want} and {want_sizes[0]}',
+          (('perf_meshvis_sizeof_view', MESHVIS_VIEW_BYTES),)),
+    _unit('meshsimp', MESHSIMP_ABI_VERSION, _SIGS_MESHSIMP, _expects('mesh-simplification ABI')),
+    _unit('meshcolor', MESHCOLOR_ABI_VERSION, _SIGS_MESHCOLOR, _expects('mesh-colouring ABI')),
+    _unit('meshray', MESHRAY_ABI_VERSION, _SIGS_MESHRAY, _expects('mesh ray-casting ABI')),
+    _unit('meshtex', MESHTEX_ABI_VERSION, _SIGS_MESHTEX, _expects('texture-atlas ABI')),
+    _unit('meshquadric', MESHQUADRIC_ABI_VERSION, _SIGS_MESHQUADRIC, _expects('quadric-placement ABI')),
+    _unit('riders', RIDERS_ABI_VERSION, _SIGS_RIDERS, 'step-rider ABI version {has} or other argument blocks than this binding ({want})',
+          (('perf_sizeof_rider_draw', ctypes.sizeof(RiderDraw)), ('perf_sizeof_rider_count', ctypes.sizeof(RiderCount)),
+           ('perf_sizeof_rider_write', ctypes.sizeof(RiderWrite)))),
 )
 
 _lib = None
@@ -395,18 +407,19 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for sigs, *_ in _UNITS:
-        for name, (res, args) in sigs.items():
+    for unit in _UNITS:
+        for name, (res, args) in unit.sigs.items():
             fn = getattr(lib, name, None)
             if fn is None:
                 raise PerfError(f'{LIB_PATH} does not export {name}: rebuild with `python -m perf_amd.build --force`')
             fn.restype = res
             fn.argtypes = args
     # the binding and the library must agree on every unit's ABI version and on the layout of the POD descriptors
-    for _, version, want, text, sizes in _UNITS:
-        has, has_sizes, want_sizes = getattr(lib, version)(), [getattr(lib, fn)() for fn, _ in sizes], [n for _, n in sizes]
+    for unit in _UNITS:
+        has, want = getattr(lib, unit.version_fn)(), unit.version
+        has_sizes, want_sizes = [getattr(lib, fn)() for fn, _ in unit.sizes], [n for _, n in unit.sizes]
         if has != want or has_sizes != want_sizes:
-            raise PerfError(f'{LIB_PATH} has ' + text.format(has=has, want=want, has_sizes=has_sizes, want_sizes=want_sizes)
+            raise PerfError(f'{LIB_PATH} has ' + unit.mismatch.format(has=has, want=want, has_sizes=has_sizes, want_sizes=want_sizes)
                             + ': rebuild with `python -m perf_amd.build --force`')
     if (lib.perf_sizeof_grid_desc() != ctypes.sizeof(GridDesc) or lib.perf_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc)
             or lib.perf_sizeof_step_book() != ctypes.sizeof(StepBook)):

@@ -6,6 +6,8 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from ._lib import _UNITS
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libperf_hip.so')
@@ -31,11 +33,15 @@ def _includes(path):
     return {path}.union(*(_includes(os.path.normpath(os.path.join(os.path.dirname(path), n))) for n in names))
 
 
+def deps():
+    """what the library as a whole is rebuilt for: the sources, the device headers and the public header of every unit of _lib's table"""
+    return ([os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, h) for h in HEADERS]
+            + [os.path.join(HERE, '..', 'include', u.header) for u in _UNITS])
+
+
 def build(force=False, verbose=False):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(HERE, '..', 'include', h) for h in ('perf_hip.h', 'perf_hip_ext.h', 'perf_hip_sphere.h', 'perf_hip_pair.h', 'perf_hip_joint.h', 'perf_hip_mesh.h', 'perf_hip_brickmesh.h', 'perf_hip_meshcc.h', 'perf_hip_meshvis.h', 'perf_hip_meshsimp.h', 'perf_hip_meshcolor.h', 'perf_hip_meshray.h', 'perf_hip_meshtex.h', 'perf_hip_meshquadric.h', 'perf_hip_riders.h')]
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + hdrs
-    if not force and _newer(LIB, deps):
+    if not force and _newer(LIB, deps()):
         return LIB
     objdir = os.path.join(HERE, 'build')
     os.makedirs(objdir, exist_ok=True)

@@ -1,30 +1,18 @@
-"""Surface nets on the live bricks of a lattice (include/perf_hip_brickmesh.h, perf_amd/mesh.py) checked without a GPU: the seventh
-header, its binding table, its recorded digest and the library agree and the six older ABIs are untouched; every refusal happens before
-a launch with a message that names its reason (the fake pointers are never dereferenced); the workspace has the documented size; the
+"""Surface nets on the live bricks of a lattice (include/perf_hip_brickmesh.h, perf_amd/mesh.py) checked without a GPU: the header's constants
+and parameter types are the binding's (that header, binding, record and library agree is tests/test_abi_units.py's); every refusal happens
+before a launch with a message that names its reason (the fake pointers are never dereferenced); the workspace has the documented size; the
 Python surface has the documented signatures and refuses CPU tensors."""
 import ctypes
 import inspect
-import json
-import os
-import re
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID, refused as _call
+
 FAKE = ctypes.c_void_p(64)   # never dereferenced: every call of this file is refused before a launch
-NAMES = ['perf_brickmesh_corners', 'perf_brickmesh_count', 'perf_brickmesh_list', 'perf_brickmesh_select', 'perf_brickmesh_version', 'perf_brickmesh_workspace_bytes',
-         'perf_brickmesh_write']
 F3 = ctypes.c_float * 3
 BIG = 1 << 40
-
-
-def _call(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
 
 
 def _select(**kw):
@@ -66,38 +54,15 @@ WITH_BRICKS = (_list, _corners, _count, _write)
 
 
 def test_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is [brickmesh] of tests/test_abi_units.py; this is what is particular to this header)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header = open(os.path.join(ROOT, 'include', 'perf_hip_brickmesh.h')).read()
-    version = int(re.search(r'#define\s+PERF_BRICKMESH_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_brickmesh.abi.json')))
-    now = abi_digest.digest(abi_digest.BRICKMESH_HEADER, 'PERF_BRICKMESH_ABI_VERSION')
-    lib = _lib.load()
-    assert version == 1 and _lib.BRICKMESH_ABI_VERSION == 1 and record['version'] == 1 and lib.perf_brickmesh_version() == 1
-    assert now == record, 'include/perf_hip_brickmesh.h changed: bump PERF_BRICKMESH_ABI_VERSION, then `python tools/abi_digest.py --brickmesh --write`'
-    assert list(inspect.signature(abi_digest.digest).parameters) == ['path', 'macro']
-    const = lambda name: int(re.search(r'#define\s+' + name + r'\s+(\d+)', header).group(1))
+    header, _ = abi_units.header('brickmesh')
+    const = lambda name: abi_units.const(header, name)
+    assert const('PERF_BRICKMESH_ABI_VERSION') == _lib.BRICKMESH_ABI_VERSION == 1
+    assert list(inspect.signature(abi_units.abi_digest().digest).parameters) == ['path', 'macro']
     assert const('PERF_BRICKMESH_EDGE') == _lib.BRICKMESH_EDGE == 8
     assert const('PERF_BRICKMESH_MAX_DIM') == _lib.BRICKMESH_MAX_DIM == 4096
     assert const('PERF_BRICKMESH_MAX_BRICKS') == _lib.BRICKMESH_MAX_BRICKS == 1 << 21
-    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_BRICKMESH) == NAMES
-    for name, (_, args) in _lib._SIGS_BRICKMESH.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args), name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
-    # the six older ABIs are what they were, and the seven name sets are disjoint
-    for macro, hdr, rec, ver in (('PERF_ABI_VERSION', abi_digest.HEADER, abi_digest.RECORD, 16), ('PERF_EXT_ABI_VERSION', abi_digest.EXT_HEADER, abi_digest.EXT_RECORD, 1),
-                                 ('PERF_SPHERE_ABI_VERSION', abi_digest.SPHERE_HEADER, abi_digest.SPHERE_RECORD, 1),
-                                 ('PERF_PAIR_ABI_VERSION', abi_digest.PAIR_HEADER, abi_digest.PAIR_RECORD, 1),
-                                 ('PERF_JOINT_ABI_VERSION', abi_digest.JOINT_HEADER, abi_digest.JOINT_RECORD, 1),
-                                 ('PERF_MESH_ABI_VERSION', abi_digest.MESH_HEADER, abi_digest.MESH_RECORD, 1)):
-        old = json.load(open(rec))
-        assert old['version'] == ver and abi_digest.digest(hdr, macro) == old, macro
-    sets = [set(_lib._SIGS), set(_lib._SIGS_EXT), set(_lib._SIGS_SPHERE), set(_lib._SIGS_PAIR), set(_lib._SIGS_JOINT), set(_lib._SIGS_MESH), set(_lib._SIGS_BRICKMESH)]
-    assert sum(len(s) for s in sets) == len(set().union(*sets))
 
 
 def test_refuses_null_pointers():
@@ -167,20 +132,10 @@ def test_refuses_threshold_fill_and_box():
         assert rc == PERF_E_INVALID and 'hi > lo' in msg, (list(lo), list(hi), msg)
 
 
-def _levels(n):
-    """L(n) of the header: the words of the scan's levels of 256 above n words, down to the level of one word."""
-    words = 0
-    while True:
-        n = -(-n // 256)
-        words += n
-        if n <= 1:
-            return words
-
-
 def _words(nx, ny, nz, m):
     groups = -(-(nx // 8) * (ny // 8) * (nz // 8) // 256)
-    select = groups + _levels(groups)
-    count = 3 * 8 * m + 2 * _levels(8 * m) + 4 if m else 4
+    select = groups + abi_units.levels(groups)
+    count = 3 * 8 * m + 2 * abi_units.levels(8 * m) + 4 if m else 4
     return max(select, count)
 
 

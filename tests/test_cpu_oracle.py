@@ -113,7 +113,7 @@ def test_abi_version_is_bumped_with_every_signature_change():
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import abi_digest
     now = abi_digest.digest()
-    rec = json.load(open(abi_digest.RECORD))
+    rec = json.load(open(abi_digest.record_path('core')))
     if now['digest'] != rec['digest']:
         assert now['version'] > rec['version'], ('include/perf_hip.h changed but PERF_ABI_VERSION is still '
                                                  f"{rec['version']}: bump it, then `python tools/abi_digest.py --write`")

@@ -1,23 +1,13 @@
-"""The density-gradient entry points (ABI 16: perf_field_grad_x, perf_normal_composite) and their Python surface, checked without a
-GPU: header, binding and recorded digest agree on the version, the symbols are exported, and every refusal happens before a launch
-with a message that names its reason."""
+"""The density-gradient entry points (ABI 16: perf_field_grad_x, perf_normal_composite) and their Python surface, checked without a GPU: the
+symbols are exported and declared in the header, and every refusal happens before a launch with a message that names its reason."""
 import ctypes
 import inspect
-import json
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
-
-
-def _call(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID, refused as _call
 
 
 def _descs(n_levels=16, n_hidden=1, **grid_kw):
@@ -35,11 +25,9 @@ def _grad_x(gd, md, grad, sigma=None, n=64, x01=ctypes.c_void_p(16), table=ctype
 
 def test_abi_16_header_binding_and_record_agree():
     from perf_amd import _lib
-    header = open(os.path.join(ROOT, 'include', 'perf_hip.h')).read()
-    version = int(re.search(r'#define\s+PERF_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip.abi.json')))
+    header, _ = abi_units.header('core')
     lib = _lib.load()
-    assert version == 16 and _lib.ABI_VERSION == 16 and record['version'] == 16 and lib.perf_version() == 16
+    assert abi_units.const(header, 'PERF_ABI_VERSION') == _lib.ABI_VERSION == 16          # (the record and the library: tests/test_abi_units.py)
     for name in ('perf_field_grad_x', 'perf_normal_composite'):
         assert name in _lib.exported_symbols() and hasattr(lib, name)
         assert re.search(r'\bint\s+%s\s*\(' % name, header), name

@@ -1,26 +1,17 @@
-"""The backward of the density gradient (include/perf_hip_ext.h: perf_field_grad_x_bwd) and its Python surface, checked without a GPU:
-the extension header, its binding table, its recorded digest and the library agree; the core ABI is untouched; every refusal happens
-before a launch with a message that names its reason; the geometry step leaves the fused path only when a normal loss is asked for."""
+"""The backward of the density gradient (include/perf_hip_ext.h: perf_field_grad_x_bwd) and its Python surface, checked without a GPU: the
+header's constants and parameter types are the binding's (that header, binding, record and library agree is tests/test_abi_units.py's);
+every refusal happens before a launch with a message that names its reason; the geometry step leaves the fused path only when a normal loss
+is asked for."""
 import ctypes
 import inspect
-import json
-import os
-import re
-import sys
 from types import SimpleNamespace
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID, refused as _call
+
 FAKE = ctypes.c_void_p(16)   # never dereferenced: every call of this file is refused -- or is an empty call -- before a launch
-
-
-def _call(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
 
 
 def _descs(n_levels=16, n_hidden=1, **grid_kw):
@@ -39,27 +30,11 @@ def _bwd(gd, md, n=64, dtype=0, **kw):
 
 
 def test_extension_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is tests/test_abi_units.py's, [ext]; this is what is the extension's own)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header = open(os.path.join(ROOT, 'include', 'perf_hip_ext.h')).read()
-    version = int(re.search(r'#define\s+PERF_EXT_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_ext.abi.json')))
-    now = abi_digest.digest(abi_digest.EXT_HEADER, 'PERF_EXT_ABI_VERSION')
-    lib = _lib.load()
-    assert version == 1 and _lib.EXT_ABI_VERSION == 1 and record['version'] == 1 and lib.perf_ext_version() == 1
-    assert now == record, 'include/perf_hip_ext.h changed: bump PERF_EXT_ABI_VERSION, then `python tools/abi_digest.py --ext --write`'
-    # declarations == binding table, name for name and parameter count for parameter count
-    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_EXT) == ['perf_ext_version', 'perf_field_grad_x_bwd', 'perf_field_grad_x_bwd_workspace_bytes']
-    for name, (_, args) in _lib._SIGS_EXT.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args), name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
-    # the core ABI is what it was: version 16, its own record, and the extension's names are not in its table
-    core = json.load(open(os.path.join(ROOT, 'include', 'perf_hip.abi.json')))
-    assert _lib.ABI_VERSION == 16 and lib.perf_version() == 16 and core['version'] == 16 and abi_digest.digest() == core
+    header, _ = abi_units.header('ext')
+    assert abi_units.const(header, 'PERF_EXT_ABI_VERSION') == _lib.EXT_ABI_VERSION == 1
+    # the extension's names are not in the core's frozen table
     assert not set(_lib._SIGS_EXT) & set(_lib.exported_symbols())
 
 

@@ -1,32 +1,23 @@
-"""The joint predictor's alignment step (include/perf_hip_joint.h, perf_amd/joint_align.py) checked without a GPU: the fifth header, its
-binding table, its recorded digest and the library agree and the four older ABIs are untouched; every refusal happens before a launch
-with a message that names its reason; the Python surface has the reference's signatures and defaults; install_joint_predictor_shim
-rebinds one method on a decoy tree and nothing is rebound without the call; the torch restatement of the iteration agrees with itself
-across precisions; the restated panorama look-up coordinates and perspective views reproduce the reference's recorded outputs
-(tests/golden/make_joint_fixture.py), and the view set has the properties the loop relies on."""
+"""The joint predictor's alignment step (include/perf_hip_joint.h, perf_amd/joint_align.py) checked without a GPU: the header's constants and
+parameter types are the binding's (that header, binding, record and library agree is tests/test_abi_units.py's); every refusal happens
+before a launch with a message that names its reason; the Python surface has the reference's signatures and defaults;
+install_joint_predictor_shim rebinds one method on a decoy tree and nothing is rebound without the call; the torch restatement of the
+iteration agrees with itself across precisions; the restated panorama look-up coordinates and perspective views reproduce the reference's
+recorded outputs (tests/golden/make_joint_fixture.py), and the view set has the properties the loop relies on."""
 import ctypes
 import importlib
 import inspect
-import json
 import os
-import re
 import sys
 import textwrap
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID, refused as _call
+
 FAKE = ctypes.c_void_p(16)   # never dereferenced: every call of this file is refused before a launch
-NAMES = ['perf_joint_loss', 'perf_joint_loss_workspace_bytes', 'perf_joint_sample', 'perf_joint_tv', 'perf_joint_tv_workspace_bytes', 'perf_joint_version']
-
-
-def _call(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
 
 
 def _sample(**kw):
@@ -51,34 +42,14 @@ def _tv(**kw):
 
 
 def test_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is [joint] of tests/test_abi_units.py; this is what is particular to this header)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header = open(os.path.join(ROOT, 'include', 'perf_hip_joint.h')).read()
-    version = int(re.search(r'#define\s+PERF_JOINT_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_joint.abi.json')))
-    now = abi_digest.digest(abi_digest.JOINT_HEADER, 'PERF_JOINT_ABI_VERSION')
-    lib = _lib.load()
-    assert version == 1 and _lib.JOINT_ABI_VERSION == 1 and record['version'] == 1 and lib.perf_joint_version() == 1
-    assert now == record, 'include/perf_hip_joint.h changed: bump PERF_JOINT_ABI_VERSION, then `python tools/abi_digest.py --joint --write`'
-    assert list(inspect.signature(abi_digest.digest).parameters) == ['path', 'macro']
-    assert int(re.search(r'#define\s+PERF_JOINT_RECORD\s+(\d+)', header).group(1)) == _lib.JOINT_RECORD == 12
-    assert int(re.search(r'#define\s+PERF_JOINT_LOSSES\s+(\d+)', header).group(1)) == _lib.JOINT_LOSSES == 8
-    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_JOINT) == NAMES
-    for name, (_, args) in _lib._SIGS_JOINT.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args), name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
-    # the four older ABIs are what they were, and the five name sets are disjoint
-    for macro, hdr, rec, ver in (('PERF_ABI_VERSION', abi_digest.HEADER, abi_digest.RECORD, 16), ('PERF_EXT_ABI_VERSION', abi_digest.EXT_HEADER, abi_digest.EXT_RECORD, 1),
-                                 ('PERF_SPHERE_ABI_VERSION', abi_digest.SPHERE_HEADER, abi_digest.SPHERE_RECORD, 1),
-                                 ('PERF_PAIR_ABI_VERSION', abi_digest.PAIR_HEADER, abi_digest.PAIR_RECORD, 1)):
-        old = json.load(open(rec))
-        assert old['version'] == ver and abi_digest.digest(hdr, macro) == old, macro
-    sets = [set(_lib._SIGS), set(_lib._SIGS_EXT), set(_lib._SIGS_SPHERE), set(_lib._SIGS_PAIR), set(_lib._SIGS_JOINT)]
-    assert sum(len(s) for s in sets) == len(set().union(*sets))
+    header, _ = abi_units.header('joint')
+    const = lambda name: abi_units.const(header, name)
+    assert const('PERF_JOINT_ABI_VERSION') == _lib.JOINT_ABI_VERSION == 1
+    assert list(inspect.signature(abi_units.abi_digest().digest).parameters) == ['path', 'macro']
+    assert const('PERF_JOINT_RECORD') == _lib.JOINT_RECORD == 12
+    assert const('PERF_JOINT_LOSSES') == _lib.JOINT_LOSSES == 8
 
 
 def test_refuses_null_pointers_and_counts():

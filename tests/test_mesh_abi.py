@@ -1,29 +1,18 @@
-"""Surface nets on a dense lattice (include/perf_hip_mesh.h, perf_amd/mesh.py) checked without a GPU: the sixth header, its binding
-table, its recorded digest and the library agree and the five older ABIs are untouched; every refusal happens before a launch with a
-message that names its reason (the fake pointers are never dereferenced); the workspace has the documented size; write_ply's files
+"""Surface nets on a dense lattice (include/perf_hip_mesh.h, perf_amd/mesh.py) checked without a GPU: the header's constants and parameter
+types are the binding's (that header, binding, record and library agree is tests/test_abi_units.py's); every refusal happens before a launch
+with a message that names its reason (the fake pointers are never dereferenced); the workspace has the documented size; write_ply's files
 read back."""
 import ctypes
 import inspect
-import json
-import os
-import re
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID, refused as _call
+
 FAKE = ctypes.c_void_p(64)   # never dereferenced: every call of this file is refused before a launch
-NAMES = ['perf_mesh_count', 'perf_mesh_version', 'perf_mesh_workspace_bytes', 'perf_mesh_write']
 F3 = ctypes.c_float * 3
-
-
-def _call(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
 
 
 def _count(**kw):
@@ -41,34 +30,13 @@ def _write(**kw):
 
 
 def test_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is [mesh] of tests/test_abi_units.py; this is what is particular to this header)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header = open(os.path.join(ROOT, 'include', 'perf_hip_mesh.h')).read()
-    version = int(re.search(r'#define\s+PERF_MESH_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_mesh.abi.json')))
-    now = abi_digest.digest(abi_digest.MESH_HEADER, 'PERF_MESH_ABI_VERSION')
-    lib = _lib.load()
-    assert version == 1 and _lib.MESH_ABI_VERSION == 1 and record['version'] == 1 and lib.perf_mesh_version() == 1
-    assert now == record, 'include/perf_hip_mesh.h changed: bump PERF_MESH_ABI_VERSION, then `python tools/abi_digest.py --mesh --write`'
-    assert list(inspect.signature(abi_digest.digest).parameters) == ['path', 'macro']
-    assert int(re.search(r'#define\s+PERF_MESH_MAX_CELLS\s+(\d+)', header).group(1)) == _lib.MESH_MAX_CELLS == 1 << 30
-    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_MESH) == NAMES
-    for name, (_, args) in _lib._SIGS_MESH.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args), name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
-    # the five older ABIs are what they were, and the six name sets are disjoint
-    for macro, hdr, rec, ver in (('PERF_ABI_VERSION', abi_digest.HEADER, abi_digest.RECORD, 16), ('PERF_EXT_ABI_VERSION', abi_digest.EXT_HEADER, abi_digest.EXT_RECORD, 1),
-                                 ('PERF_SPHERE_ABI_VERSION', abi_digest.SPHERE_HEADER, abi_digest.SPHERE_RECORD, 1),
-                                 ('PERF_PAIR_ABI_VERSION', abi_digest.PAIR_HEADER, abi_digest.PAIR_RECORD, 1),
-                                 ('PERF_JOINT_ABI_VERSION', abi_digest.JOINT_HEADER, abi_digest.JOINT_RECORD, 1)):
-        old = json.load(open(rec))
-        assert old['version'] == ver and abi_digest.digest(hdr, macro) == old, macro
-    sets = [set(_lib._SIGS), set(_lib._SIGS_EXT), set(_lib._SIGS_SPHERE), set(_lib._SIGS_PAIR), set(_lib._SIGS_JOINT), set(_lib._SIGS_MESH)]
-    assert sum(len(s) for s in sets) == len(set().union(*sets))
+    header, _ = abi_units.header('mesh')
+    const = lambda name: abi_units.const(header, name)
+    assert const('PERF_MESH_ABI_VERSION') == _lib.MESH_ABI_VERSION == 1
+    assert list(inspect.signature(abi_units.abi_digest().digest).parameters) == ['path', 'macro']
+    assert const('PERF_MESH_MAX_CELLS') == _lib.MESH_MAX_CELLS == 1 << 30
 
 
 def test_refuses_null_pointers():

@@ -1,28 +1,20 @@
-"""The connected components of a triangle mesh (include/perf_hip_meshcc.h, perf_amd/mesh.py) checked without a GPU: the eighth header,
-its binding table, its recorded digest and the library agree and the seven older ABIs are untouched; every refusal happens before a
-launch with a message that names its reason (the fake pointers are never dereferenced); the workspace has the documented size; the
+"""The connected components of a triangle mesh (include/perf_hip_meshcc.h, perf_amd/mesh.py) checked without a GPU: the header's constants and
+parameter types are the binding's (that header, binding, record and library agree is tests/test_abi_units.py's); every refusal happens
+before a launch with a message that names its reason (the fake pointers are never dereferenced); the workspace has the documented size; the
 Python surface has the documented signatures and refuses CPU tensors."""
 import ctypes
 import inspect
-import json
 import os
 import re
-import sys
 
 import pytest
 
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID, refused as _call
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
 FAKE = ctypes.c_void_p(64)   # never dereferenced: every call of this file is refused before a launch
-NAMES = ['perf_meshcc_filter_count', 'perf_meshcc_filter_write', 'perf_meshcc_label', 'perf_meshcc_stats', 'perf_meshcc_version', 'perf_meshcc_workspace_bytes']
 BIG = 1 << 40
-
-
-def _call(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
 
 
 def _label(**kw):
@@ -57,43 +49,18 @@ WITH_WORKSPACE = (_label, _filter_count, _filter_write)
 
 
 def test_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is [meshcc] of tests/test_abi_units.py; this is what is particular to this header)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header = open(os.path.join(ROOT, 'include', 'perf_hip_meshcc.h')).read()
-    version = int(re.search(r'#define\s+PERF_MESHCC_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_meshcc.abi.json')))
-    now = abi_digest.digest(abi_digest.MESHCC_HEADER, 'PERF_MESHCC_ABI_VERSION')
-    lib = _lib.load()
-    assert version == 1 and _lib.MESHCC_ABI_VERSION == 1 and record['version'] == 1 and lib.perf_meshcc_version() == 1
-    assert now == record, 'include/perf_hip_meshcc.h changed: bump PERF_MESHCC_ABI_VERSION, then `python tools/abi_digest.py --meshcc --write`'
-    assert list(inspect.signature(abi_digest.digest).parameters) == ['path', 'macro']
-    const = lambda name: int(re.search(r'#define\s+' + name + r'\s+(\d+)', header).group(1))
+    header, plain = abi_units.header('meshcc')
+    const = lambda name: abi_units.const(header, name)
+    assert const('PERF_MESHCC_ABI_VERSION') == _lib.MESHCC_ABI_VERSION == 1
+    assert list(inspect.signature(abi_units.abi_digest().digest).parameters) == ['path', 'macro']
     assert const('PERF_MESHCC_MAX_VERTICES') == _lib.MESHCC_MAX_VERTICES == _lib.MESH_MAX_CELLS == 1 << 30          # the mesh ABI's ceiling
     assert const('PERF_MESHCC_MAX_FACES') == _lib.MESHCC_MAX_FACES == 1 << 38 and _lib.MESHCC_MAX_FACES > 1 << 31
-    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_MESHCC) == NAMES
-    for name, (_, args) in _lib._SIGS_MESHCC.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args), name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
     # face counts and offsets are 64-bit at the boundary
     for name in ('perf_meshcc_label', 'perf_meshcc_stats', 'perf_meshcc_filter_count', 'perf_meshcc_filter_write'):
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1)
+        params = abi_units.params(plain, name)
         assert 'int64_t n_faces' in params and 'int64_t n_vertices' in params, name
-    # the seven older ABIs are what they were, and the eight name sets are disjoint
-    for macro, hdr, rec, ver in (('PERF_ABI_VERSION', abi_digest.HEADER, abi_digest.RECORD, 16), ('PERF_EXT_ABI_VERSION', abi_digest.EXT_HEADER, abi_digest.EXT_RECORD, 1),
-                                 ('PERF_SPHERE_ABI_VERSION', abi_digest.SPHERE_HEADER, abi_digest.SPHERE_RECORD, 1),
-                                 ('PERF_PAIR_ABI_VERSION', abi_digest.PAIR_HEADER, abi_digest.PAIR_RECORD, 1),
-                                 ('PERF_JOINT_ABI_VERSION', abi_digest.JOINT_HEADER, abi_digest.JOINT_RECORD, 1),
-                                 ('PERF_MESH_ABI_VERSION', abi_digest.MESH_HEADER, abi_digest.MESH_RECORD, 1),
-                                 ('PERF_BRICKMESH_ABI_VERSION', abi_digest.BRICKMESH_HEADER, abi_digest.BRICKMESH_RECORD, 1)):
-        old = json.load(open(rec))
-        assert old['version'] == ver and abi_digest.digest(hdr, macro) == old, macro
-    sets = [set(_lib._SIGS), set(_lib._SIGS_EXT), set(_lib._SIGS_SPHERE), set(_lib._SIGS_PAIR), set(_lib._SIGS_JOINT), set(_lib._SIGS_MESH), set(_lib._SIGS_BRICKMESH),
-            set(_lib._SIGS_MESHCC)]
-    assert sum(len(s) for s in sets) == len(set().union(*sets))
 
 
 def test_the_header_states_the_termination_argument():
@@ -145,27 +112,12 @@ def test_refuses_counts():
     assert lib.perf_meshcc_workspace_bytes(1 << 30, 1 << 38) > 0
 
 
-def _levels(n):
-    """L(n) of the header: the words of the scan's levels of 256 above n words, down to the level of one word."""
-    words = 0
-    while True:
-        n = -(-n // 256)
-        words += n
-        if n <= 1:
-            return words
-
-
-def _group_words(n):
-    """S(n) of the header."""
-    return 0 if n == 0 else -(-n // 256) + _levels(-(-n // 256))
-
-
 def test_refuses_a_bad_workspace_and_sizes_it_as_documented():
     from perf_amd import _lib
     lib = _lib.load()
     for V, F in ((0, 0), (5, 0), (0, 7), (1, 1), (256, 256), (257, 65537), (65536, 65536), (65537, 131070), (3_700_000, 7_400_000), (14_700_000, 29_400_000),
                  (1 << 30, 1 << 31), (1 << 30, (1 << 31) + 12345), (1 << 30, 1 << 38)):
-        words = V + _group_words(V) + _group_words(F) + 4
+        words = V + abi_units.group_words(V) + abi_units.group_words(F) + 4
         need = lib.perf_meshcc_workspace_bytes(V, F)
         assert need == 8 * (words + words % 2) and need % 16 == 0, (V, F)
     assert lib.perf_meshcc_workspace_bytes(14_700_000, 29_400_000) < 8.1 * 14_700_000          # 8 bytes per vertex, 1/32 byte per face, and the levels

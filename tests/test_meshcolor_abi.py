@@ -1,27 +1,19 @@
-"""The colouring from the registered panoramas (include/perf_hip_meshcolor.h, perf_amd/mesh.py) checked without a GPU: the eleventh
-header, its binding table, its recorded digest and the library agree and the ten older ABIs are untouched; every refusal happens before a
-launch with a message that names its reason (the fake pointers are never dereferenced); the Python surface has the documented signatures
-and refuses CPU tensors; the extraction tool colours after the cleaning and before the simplification."""
+"""The colouring from the registered panoramas (include/perf_hip_meshcolor.h, perf_amd/mesh.py) checked without a GPU: the header's constants
+and parameter types are the binding's (that header, binding, record and library agree is tests/test_abi_units.py's); every refusal happens
+before a launch with a message that names its reason (the fake pointers are never dereferenced); the Python surface has the documented
+signatures and refuses CPU tensors; the extraction tool colours after the cleaning and before the simplification."""
 import ctypes
 import inspect
-import json
 import os
 import re
-import sys
 
 import pytest
 
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID, refused as _call
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
 FAKE = ctypes.c_void_p(64)   # never dereferenced: every call of this file is refused before a launch
-NAMES = ['perf_meshcolor_blend', 'perf_meshcolor_normal_sums', 'perf_meshcolor_normals', 'perf_meshcolor_version']
-
-
-def _call(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
 
 
 def _sums(**kw):
@@ -47,50 +39,22 @@ def _blend(**kw):
 
 
 def test_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is [meshcolor] of tests/test_abi_units.py; this is what is particular to this header)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header = open(os.path.join(ROOT, 'include', 'perf_hip_meshcolor.h')).read()
-    version = int(re.search(r'#define\s+PERF_MESHCOLOR_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_meshcolor.abi.json')))
-    now = abi_digest.digest(abi_digest.MESHCOLOR_HEADER, 'PERF_MESHCOLOR_ABI_VERSION')
-    lib = _lib.load()
-    assert version == 1 and _lib.MESHCOLOR_ABI_VERSION == 1 and record['version'] == 1 and lib.perf_meshcolor_version() == 1
-    assert now == record, 'include/perf_hip_meshcolor.h changed: bump PERF_MESHCOLOR_ABI_VERSION, then `python tools/abi_digest.py --meshcolor --write`'
-    const = lambda name: int(re.search(r'#define\s+' + name + r'\s+(\d+)', header).group(1))
+    header, plain = abi_units.header('meshcolor')
+    const = lambda name: abi_units.const(header, name)
+    assert const('PERF_MESHCOLOR_ABI_VERSION') == _lib.MESHCOLOR_ABI_VERSION == 1
     assert const('PERF_MESHCOLOR_MAX_VIEWS') == _lib.MESHCOLOR_MAX_VIEWS == _lib.MESHVIS_MAX_VIEWS == 64
     assert const('PERF_MESHCOLOR_MAX_VERTICES') == _lib.MESHCOLOR_MAX_VERTICES == 1 << 30
     assert const('PERF_MESHCOLOR_MAX_FACES') == _lib.MESHCOLOR_MAX_FACES == (1 << 31) - 1
     assert const('PERF_MESHCOLOR_MAX_POWER') == _lib.MESHCOLOR_MAX_POWER == 8
     assert {k: const('PERF_MESHCOLOR_SELECT_' + k.upper()) for k in ('blend', 'best')} == _lib.MESHCOLOR_SELECT
     assert '#include "perf_hip_meshvis.h"' in header and 'typedef struct' not in header          # the view descriptor is the cull's, unchanged
-    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_MESHCOLOR) == NAMES
-    for name, (_, args) in _lib._SIGS_MESHCOLOR.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args), name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
     # vertex and face counts are 64-bit at the boundary
-    params = re.search(r'\bperf_meshcolor_normal_sums\s*\((.*?)\)\s*;', plain, re.S).group(1)
+    params = abi_units.params(plain, 'perf_meshcolor_normal_sums')
     assert 'int64_t n_faces' in params and 'int64_t n_vertices' in params
     for name in ('perf_meshcolor_normals', 'perf_meshcolor_blend'):
-        assert 'int64_t n_vertices' in re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1), name
-    # the ten older ABIs are what they were, and the eleven name sets are disjoint
-    for macro, hdr, rec, ver in (('PERF_ABI_VERSION', abi_digest.HEADER, abi_digest.RECORD, 16), ('PERF_EXT_ABI_VERSION', abi_digest.EXT_HEADER, abi_digest.EXT_RECORD, 1),
-                                 ('PERF_SPHERE_ABI_VERSION', abi_digest.SPHERE_HEADER, abi_digest.SPHERE_RECORD, 1),
-                                 ('PERF_PAIR_ABI_VERSION', abi_digest.PAIR_HEADER, abi_digest.PAIR_RECORD, 1),
-                                 ('PERF_JOINT_ABI_VERSION', abi_digest.JOINT_HEADER, abi_digest.JOINT_RECORD, 1),
-                                 ('PERF_MESH_ABI_VERSION', abi_digest.MESH_HEADER, abi_digest.MESH_RECORD, 1),
-                                 ('PERF_BRICKMESH_ABI_VERSION', abi_digest.BRICKMESH_HEADER, abi_digest.BRICKMESH_RECORD, 1),
-                                 ('PERF_MESHCC_ABI_VERSION', abi_digest.MESHCC_HEADER, abi_digest.MESHCC_RECORD, 1),
-                                 ('PERF_MESHVIS_ABI_VERSION', abi_digest.MESHVIS_HEADER, abi_digest.MESHVIS_RECORD, 1),
-                                 ('PERF_MESHSIMP_ABI_VERSION', abi_digest.MESHSIMP_HEADER, abi_digest.MESHSIMP_RECORD, 1)):
-        old = json.load(open(rec))
-        assert old['version'] == ver and abi_digest.digest(hdr, macro) == old, macro
-    sets = [set(_lib._SIGS), set(_lib._SIGS_EXT), set(_lib._SIGS_SPHERE), set(_lib._SIGS_PAIR), set(_lib._SIGS_JOINT), set(_lib._SIGS_MESH), set(_lib._SIGS_BRICKMESH),
-            set(_lib._SIGS_MESHCC), set(_lib._SIGS_MESHVIS), set(_lib._SIGS_MESHSIMP), set(_lib._SIGS_MESHCOLOR)]
-    assert len(sets) == 11 and sum(len(s) for s in sets) == len(set().union(*sets))
+        assert 'int64_t n_vertices' in abi_units.params(plain, name), name
 
 
 def test_the_header_states_the_rule_and_what_it_does_not_do():
@@ -112,8 +76,7 @@ def test_the_header_states_the_rule_and_what_it_does_not_do():
 def test_the_unit_is_built_with_its_own_header():
     from perf_amd import build
     assert 'meshcolor.hip' in build.SOURCES and len(set(build.SOURCES)) == len(build.SOURCES)
-    text = open(os.path.join(ROOT, 'perf_amd', 'build.py')).read()
-    assert "'perf_hip_meshcolor.h'" in text.split('hdrs =')[1].split('\n')[0]
+    assert os.path.join(ROOT, 'include', 'perf_hip_meshcolor.h') in abi_units.build_deps()
     users = [s for s in build.SOURCES if any(p.endswith(os.sep + 'perf_hip_meshcolor.h') for p in build._includes(os.path.join(build.CSRC, s)))]
     assert users == ['meshcolor.hip'], users          # the units that include the header, by their #include lines, are the ones rebuilt for it
     unit = open(os.path.join(ROOT, 'perf_amd', 'csrc', 'meshcolor.hip')).read()

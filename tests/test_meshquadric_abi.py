@@ -1,28 +1,22 @@
-"""The quadric error placement (include/perf_hip_meshquadric.h, perf_amd/mesh.py) checked without a GPU: the fourteenth header, its
-binding table, its recorded digest and the library agree and the thirteen older ABIs are untouched; the header states the rule; the unit
-lives where the older ABI tests need it; every refusal happens before a launch with a message that names its reason (the fake pointers
-are never dereferenced); the Python surface has the documented signatures and refuses CPU tensors; the extraction tool offers 'quadric'."""
+"""The quadric error placement (include/perf_hip_meshquadric.h, perf_amd/mesh.py) checked without a GPU: the header's constants and parameter
+types are the binding's (that header, binding, record and library agree is tests/test_abi_units.py's); the header states the rule; the unit
+lives where the build and the other units' tests need it; every refusal happens before a launch with a message that names its reason (the
+fake pointers are never dereferenced); the Python surface has the documented signatures and refuses CPU tensors; the extraction tool offers
+'quadric'."""
 import ctypes
 import inspect
-import json
 import os
 import re
-import sys
 
 import pytest
 
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID, refused as _call
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
 FAKE = ctypes.c_void_p(64)   # never dereferenced: every call of this file is refused before a launch
 NAMES = ['perf_meshquadric_place', 'perf_meshquadric_sums', 'perf_meshquadric_version']
 ARITY = {'perf_meshquadric_version': 0, 'perf_meshquadric_sums': 15, 'perf_meshquadric_place': 13}
-
-
-def _call(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
 
 
 def _lo(values):
@@ -45,17 +39,11 @@ ALL = (_sums, _place)
 
 
 def test_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is [meshquadric] of tests/test_abi_units.py; this is what is particular to this header)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header = open(os.path.join(ROOT, 'include', 'perf_hip_meshquadric.h')).read()
-    version = int(re.search(r'#define\s+PERF_MESHQUADRIC_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_meshquadric.abi.json')))
-    now = abi_digest.digest(abi_digest.MESHQUADRIC_HEADER, 'PERF_MESHQUADRIC_ABI_VERSION')
-    lib = _lib.load()
-    assert version == 1 and _lib.MESHQUADRIC_ABI_VERSION == 1 and record['version'] == 1 and lib.perf_meshquadric_version() == 1
-    assert now == record, 'include/perf_hip_meshquadric.h changed: bump PERF_MESHQUADRIC_ABI_VERSION, then `python tools/abi_digest.py --meshquadric --write`'
-    const = lambda name: int(re.search(r'#define\s+' + name + r'\s+(\d+)', header).group(1))
+    header, plain = abi_units.header('meshquadric')
+    const = lambda name: abi_units.const(header, name)
+    assert const('PERF_MESHQUADRIC_ABI_VERSION') == _lib.MESHQUADRIC_ABI_VERSION == 1
     assert const('PERF_MESHQUADRIC_MAX_VERTICES') == _lib.MESHQUADRIC_MAX_VERTICES == _lib.MESHSIMP_MAX_VERTICES == 1 << 30
     assert const('PERF_MESHQUADRIC_MAX_FACES') == _lib.MESHQUADRIC_MAX_FACES == _lib.MESHSIMP_MAX_FACES == (1 << 31) - 1
     assert const('PERF_MESHQUADRIC_MAX_CELLS') == _lib.MESHQUADRIC_MAX_CELLS == _lib.MESHSIMP_MAX_CELLS == 1 << 21
@@ -65,35 +53,10 @@ def test_header_binding_record_and_library_agree():
     assert const('PERF_MESHQUADRIC_REGULARISER_BITS') == _lib.MESHQUADRIC_REGULARISER_BITS == 10
     # the header stands alone
     assert '#include "perf_hip' not in header and 'typedef struct' not in header and '#include <stdint.h>' in header
-    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_MESHQUADRIC) == NAMES
-    for name, (_, args) in _lib._SIGS_MESHQUADRIC.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args) == ARITY[name], name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
+    assert {name: len(args) for name, (_, args) in _lib._SIGS_MESHQUADRIC.items()} == ARITY
     for name in NAMES[:2]:
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1)
+        params = abi_units.params(plain, name)
         assert 'int64_t n_vertices' in params and 'const float* lo' in params and 'float h' in params and 'int64_t n_clusters' in params and 'void* stream' in params, name
-    # the thirteen older ABIs are what they were, and the fourteen name sets are disjoint
-    older = (('PERF_ABI_VERSION', abi_digest.HEADER, abi_digest.RECORD, 16), ('PERF_EXT_ABI_VERSION', abi_digest.EXT_HEADER, abi_digest.EXT_RECORD, 1),
-             ('PERF_SPHERE_ABI_VERSION', abi_digest.SPHERE_HEADER, abi_digest.SPHERE_RECORD, 1), ('PERF_PAIR_ABI_VERSION', abi_digest.PAIR_HEADER, abi_digest.PAIR_RECORD, 1),
-             ('PERF_JOINT_ABI_VERSION', abi_digest.JOINT_HEADER, abi_digest.JOINT_RECORD, 1), ('PERF_MESH_ABI_VERSION', abi_digest.MESH_HEADER, abi_digest.MESH_RECORD, 1),
-             ('PERF_BRICKMESH_ABI_VERSION', abi_digest.BRICKMESH_HEADER, abi_digest.BRICKMESH_RECORD, 1),
-             ('PERF_MESHCC_ABI_VERSION', abi_digest.MESHCC_HEADER, abi_digest.MESHCC_RECORD, 1), ('PERF_MESHVIS_ABI_VERSION', abi_digest.MESHVIS_HEADER, abi_digest.MESHVIS_RECORD, 1),
-             ('PERF_MESHSIMP_ABI_VERSION', abi_digest.MESHSIMP_HEADER, abi_digest.MESHSIMP_RECORD, 1),
-             ('PERF_MESHCOLOR_ABI_VERSION', abi_digest.MESHCOLOR_HEADER, abi_digest.MESHCOLOR_RECORD, 1),
-             ('PERF_MESHRAY_ABI_VERSION', abi_digest.MESHRAY_HEADER, abi_digest.MESHRAY_RECORD, 1),
-             ('PERF_MESHTEX_ABI_VERSION', abi_digest.MESHTEX_HEADER, abi_digest.MESHTEX_RECORD, 1))
-    assert len(older) == 13
-    for macro, hdr, rec, ver in older:
-        old = json.load(open(rec))
-        assert old['version'] == ver and abi_digest.digest(hdr, macro) == old, macro
-    sets = [set(_lib._SIGS), set(_lib._SIGS_EXT), set(_lib._SIGS_SPHERE), set(_lib._SIGS_PAIR), set(_lib._SIGS_JOINT), set(_lib._SIGS_MESH), set(_lib._SIGS_BRICKMESH),
-            set(_lib._SIGS_MESHCC), set(_lib._SIGS_MESHVIS), set(_lib._SIGS_MESHSIMP), set(_lib._SIGS_MESHCOLOR), set(_lib._SIGS_MESHRAY), set(_lib._SIGS_MESHTEX),
-            set(_lib._SIGS_MESHQUADRIC)]
-    assert len(sets) == 14 and sum(len(s) for s in sets) == len(set().union(*sets))
-    assert any(sigs is _lib._SIGS_MESHQUADRIC and version == 'perf_meshquadric_version' for sigs, version, *_ in _lib._UNITS)
     # 'quadric' is the wrapper's: the clustering unit's placements are what they were
     assert _lib.MESHSIMP_PLACEMENT == {'mean': 0, 'member': 1}
 
@@ -126,8 +89,7 @@ def test_the_code_lives_where_the_older_abi_tests_need_it():
     includes = lambda name: build._includes(os.path.join(build.CSRC, name))
     reaches = lambda name, header: any(p.endswith(os.sep + header) for p in includes(name))
     assert build.SOURCES.count('meshquadric.hip') == 1 and len(set(build.SOURCES)) == len(build.SOURCES)
-    text = open(os.path.join(ROOT, 'perf_amd', 'build.py')).read()
-    assert "'perf_hip_meshquadric.h'" in text.split('hdrs =')[1].split('\n')[0]
+    assert os.path.join(ROOT, 'include', 'perf_hip_meshquadric.h') in abi_units.build_deps()
     assert [s for s in build.SOURCES if reaches(s, 'perf_hip_meshquadric.h')] == ['meshquadric.hip']
     assert [s for s in build.SOURCES if reaches(s, 'perf_hip_meshsimp.h')] == ['meshsimp.hip']
     for header in ('perf_hip_meshsimp.h', 'perf_hip_meshvis.h', 'perf_hip_meshcolor.h', 'perf_hip_meshray.h', 'perf_hip_meshtex.h', 'meshtex_device.hpp'):

@@ -1,28 +1,21 @@
-"""Rays against a mesh on a uniform grid (include/perf_hip_meshray.h, perf_amd/mesh.py) checked without a GPU: the twelfth header, its
-binding table, its recorded digest and the library agree and the eleven older ABIs are untouched; every refusal happens before a launch
-with a message that names its reason (the fake pointers are never dereferenced); the header states the rule; the Python surface has the
-documented signatures and refuses CPU tensors; the extraction tool takes --occlusion."""
+"""Rays against a mesh on a uniform grid (include/perf_hip_meshray.h, perf_amd/mesh.py) checked without a GPU: the header's constants and
+parameter types are the binding's (that header, binding, record and library agree is tests/test_abi_units.py's); every refusal happens
+before a launch with a message that names its reason (the fake pointers are never dereferenced); the header states the rule; the Python
+surface has the documented signatures and refuses CPU tensors; the extraction tool takes --occlusion."""
 import ctypes
 import inspect
-import json
 import os
 import re
-import sys
 
 import pytest
 
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID, refused as _call
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
 FAKE = ctypes.c_void_p(64)   # never dereferenced: every call of this file is refused before a launch
 NAMES = ['perf_meshray_cast', 'perf_meshray_grid_count', 'perf_meshray_grid_write', 'perf_meshray_occluded', 'perf_meshray_version']
 ARITY = {'perf_meshray_version': 0, 'perf_meshray_grid_count': 10, 'perf_meshray_grid_write': 13, 'perf_meshray_cast': 22, 'perf_meshray_occluded': 15}
-
-
-def _call(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
 
 
 def _box(a):
@@ -63,49 +56,22 @@ ALL = (_count, _write, _cast, _occluded)
 
 
 def test_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is [meshray] of tests/test_abi_units.py; this is what is particular to this header)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header = open(os.path.join(ROOT, 'include', 'perf_hip_meshray.h')).read()
-    version = int(re.search(r'#define\s+PERF_MESHRAY_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_meshray.abi.json')))
-    now = abi_digest.digest(abi_digest.MESHRAY_HEADER, 'PERF_MESHRAY_ABI_VERSION')
-    lib = _lib.load()
-    assert version == 1 and _lib.MESHRAY_ABI_VERSION == 1 and record['version'] == 1 and lib.perf_meshray_version() == 1
-    assert now == record, 'include/perf_hip_meshray.h changed: bump PERF_MESHRAY_ABI_VERSION, then `python tools/abi_digest.py --meshray --write`'
-    const = lambda name: int(re.search(r'#define\s+' + name + r'\s+(\d+)', header).group(1))
+    header, plain = abi_units.header('meshray')
+    const = lambda name: abi_units.const(header, name)
+    assert const('PERF_MESHRAY_ABI_VERSION') == _lib.MESHRAY_ABI_VERSION == 1
     assert const('PERF_MESHRAY_MAX_CELLS') == _lib.MESHRAY_MAX_CELLS == 1 << 24
     assert const('PERF_MESHRAY_MAX_VIEWS') == _lib.MESHRAY_MAX_VIEWS == _lib.MESHVIS_MAX_VIEWS == 64
     assert const('PERF_MESHRAY_MAX_VERTICES') == _lib.MESHRAY_MAX_VERTICES == 1 << 30
     assert const('PERF_MESHRAY_MAX_FACES') == _lib.MESHRAY_MAX_FACES == (1 << 31) - 1
-    assert '#include "perf_hip' not in header and 'typedef struct' not in header          # it stands alone: the eleven other headers do not change
-    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_MESHRAY) == NAMES
-    for name, (_, args) in _lib._SIGS_MESHRAY.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args) == ARITY[name], name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
+    assert '#include "perf_hip' not in header and 'typedef struct' not in header          # it stands alone: the other headers do not change
+    assert {name: len(args) for name, (_, args) in _lib._SIGS_MESHRAY.items()} == ARITY
     # counts are 64-bit at the boundary
     for name in NAMES[:4]:
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1)
+        params = abi_units.params(plain, name)
         assert 'int64_t n_vertices' in params and 'int64_t n_faces' in params and 'void* stream' in params, name
     assert 'int64_t n_rays' in plain and 'int64_t n_refs' in plain and 'int64_t ref_capacity' in plain and 'int64_t n_refs_counted' in plain
-    # the eleven older ABIs are what they were, and the twelve name sets are disjoint
-    older = (('PERF_ABI_VERSION', abi_digest.HEADER, abi_digest.RECORD, 16), ('PERF_EXT_ABI_VERSION', abi_digest.EXT_HEADER, abi_digest.EXT_RECORD, 1),
-             ('PERF_SPHERE_ABI_VERSION', abi_digest.SPHERE_HEADER, abi_digest.SPHERE_RECORD, 1), ('PERF_PAIR_ABI_VERSION', abi_digest.PAIR_HEADER, abi_digest.PAIR_RECORD, 1),
-             ('PERF_JOINT_ABI_VERSION', abi_digest.JOINT_HEADER, abi_digest.JOINT_RECORD, 1), ('PERF_MESH_ABI_VERSION', abi_digest.MESH_HEADER, abi_digest.MESH_RECORD, 1),
-             ('PERF_BRICKMESH_ABI_VERSION', abi_digest.BRICKMESH_HEADER, abi_digest.BRICKMESH_RECORD, 1),
-             ('PERF_MESHCC_ABI_VERSION', abi_digest.MESHCC_HEADER, abi_digest.MESHCC_RECORD, 1), ('PERF_MESHVIS_ABI_VERSION', abi_digest.MESHVIS_HEADER, abi_digest.MESHVIS_RECORD, 1),
-             ('PERF_MESHSIMP_ABI_VERSION', abi_digest.MESHSIMP_HEADER, abi_digest.MESHSIMP_RECORD, 1),
-             ('PERF_MESHCOLOR_ABI_VERSION', abi_digest.MESHCOLOR_HEADER, abi_digest.MESHCOLOR_RECORD, 1))
-    assert len(older) == 11
-    for macro, hdr, rec, ver in older:
-        old = json.load(open(rec))
-        assert old['version'] == ver and abi_digest.digest(hdr, macro) == old, macro
-    sets = [set(_lib._SIGS), set(_lib._SIGS_EXT), set(_lib._SIGS_SPHERE), set(_lib._SIGS_PAIR), set(_lib._SIGS_JOINT), set(_lib._SIGS_MESH), set(_lib._SIGS_BRICKMESH),
-            set(_lib._SIGS_MESHCC), set(_lib._SIGS_MESHVIS), set(_lib._SIGS_MESHSIMP), set(_lib._SIGS_MESHCOLOR), set(_lib._SIGS_MESHRAY)]
-    assert len(sets) == 12 and sum(len(s) for s in sets) == len(set().union(*sets))
 
 
 def test_the_header_states_the_rule_and_what_it_does_not_do():
@@ -128,8 +94,8 @@ def test_the_header_states_the_rule_and_what_it_does_not_do():
 def test_the_unit_is_built_with_its_own_header():
     from perf_amd import build
     assert 'meshray.hip' in build.SOURCES and len(set(build.SOURCES)) == len(build.SOURCES)
+    assert os.path.join(ROOT, 'include', 'perf_hip_meshray.h') in abi_units.build_deps()
     text = open(os.path.join(ROOT, 'perf_amd', 'build.py')).read()
-    assert "'perf_hip_meshray.h'" in text.split('hdrs =')[1].split('\n')[0]
     users = [s for s in build.SOURCES if any(p.endswith(os.sep + 'perf_hip_meshray.h') for p in build._includes(os.path.join(build.CSRC, s)))]
     assert users == ['meshray.hip'], users          # the units that include the header, by their #include lines, are the ones rebuilt for it
     assert "'-ffp-contract=off'" in text

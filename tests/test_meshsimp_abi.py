@@ -1,29 +1,20 @@
-"""The simplification by vertex clustering (include/perf_hip_meshsimp.h, perf_amd/mesh.py) checked without a GPU: the tenth header, its
-binding table, its recorded digest and the library agree and the nine older ABIs are untouched; every refusal happens before a launch
-with a message that names its reason (the fake pointers are never dereferenced); the workspace has the documented size; the Python
-surface has the documented signatures and refuses CPU tensors; the extraction tool simplifies after the component cleaning."""
+"""The simplification by vertex clustering (include/perf_hip_meshsimp.h, perf_amd/mesh.py) checked without a GPU: the header's constants and
+parameter types are the binding's (that header, binding, record and library agree is tests/test_abi_units.py's); every refusal happens
+before a launch with a message that names its reason (the fake pointers are never dereferenced); the workspace has the documented size; the
+Python surface has the documented signatures and refuses CPU tensors; the extraction tool simplifies after the component cleaning."""
 import ctypes
 import inspect
-import json
 import os
 import re
-import sys
 
 import pytest
 
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID, refused as _call
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
 FAKE = ctypes.c_void_p(64)   # never dereferenced: every call of this file is refused before a launch
-NAMES = ['perf_meshsimp_bounds', 'perf_meshsimp_cluster', 'perf_meshsimp_faces', 'perf_meshsimp_place', 'perf_meshsimp_table_slots', 'perf_meshsimp_version',
-         'perf_meshsimp_workspace_bytes']
 BIG = 1 << 40
-
-
-def _call(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
 
 
 def _lo(*values):
@@ -61,48 +52,21 @@ WITH_WORKSPACE = (_cluster, _faces)
 
 
 def test_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is [meshsimp] of tests/test_abi_units.py; this is what is particular to this header)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header = open(os.path.join(ROOT, 'include', 'perf_hip_meshsimp.h')).read()
-    version = int(re.search(r'#define\s+PERF_MESHSIMP_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_meshsimp.abi.json')))
-    now = abi_digest.digest(abi_digest.MESHSIMP_HEADER, 'PERF_MESHSIMP_ABI_VERSION')
-    lib = _lib.load()
-    assert version == 1 and _lib.MESHSIMP_ABI_VERSION == 1 and record['version'] == 1 and lib.perf_meshsimp_version() == 1
-    assert now == record, 'include/perf_hip_meshsimp.h changed: bump PERF_MESHSIMP_ABI_VERSION, then `python tools/abi_digest.py --meshsimp --write`'
-    const = lambda name: int(re.search(r'#define\s+' + name + r'\s+(\d+)', header).group(1))
+    header, plain = abi_units.header('meshsimp')
+    const = lambda name: abi_units.const(header, name)
+    assert const('PERF_MESHSIMP_ABI_VERSION') == _lib.MESHSIMP_ABI_VERSION == 1
     assert const('PERF_MESHSIMP_MAX_VERTICES') == _lib.MESHSIMP_MAX_VERTICES == 1 << 30
     assert const('PERF_MESHSIMP_MAX_FACES') == _lib.MESHSIMP_MAX_FACES == (1 << 31) - 1
     assert const('PERF_MESHSIMP_MAX_CELLS') == _lib.MESHSIMP_MAX_CELLS == 1 << 21
     assert {k: const('PERF_MESHSIMP_PLACE_' + k.upper()) for k in ('mean', 'member')} == _lib.MESHSIMP_PLACEMENT
     assert {None if k == 'NONE' else k.lower(): const('PERF_MESHSIMP_DEDUPE_' + k) for k in ('NONE', 'ORIENTED', 'UNORIENTED')} == _lib.MESHSIMP_DEDUPE
-    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_MESHSIMP) == NAMES
-    for name, (_, args) in _lib._SIGS_MESHSIMP.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args), name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
     # vertex and face counts are 64-bit at the boundary
     for name in ('perf_meshsimp_cluster', 'perf_meshsimp_faces'):
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1)
+        params = abi_units.params(plain, name)
         assert 'int64_t n_faces' in params and 'int64_t n_vertices' in params, name
-    assert 'int64_t n_vertices' in re.search(r'\bperf_meshsimp_place\s*\((.*?)\)\s*;', plain, re.S).group(1)
-    # the nine older ABIs are what they were, and the ten name sets are disjoint
-    for macro, hdr, rec, ver in (('PERF_ABI_VERSION', abi_digest.HEADER, abi_digest.RECORD, 16), ('PERF_EXT_ABI_VERSION', abi_digest.EXT_HEADER, abi_digest.EXT_RECORD, 1),
-                                 ('PERF_SPHERE_ABI_VERSION', abi_digest.SPHERE_HEADER, abi_digest.SPHERE_RECORD, 1),
-                                 ('PERF_PAIR_ABI_VERSION', abi_digest.PAIR_HEADER, abi_digest.PAIR_RECORD, 1),
-                                 ('PERF_JOINT_ABI_VERSION', abi_digest.JOINT_HEADER, abi_digest.JOINT_RECORD, 1),
-                                 ('PERF_MESH_ABI_VERSION', abi_digest.MESH_HEADER, abi_digest.MESH_RECORD, 1),
-                                 ('PERF_BRICKMESH_ABI_VERSION', abi_digest.BRICKMESH_HEADER, abi_digest.BRICKMESH_RECORD, 1),
-                                 ('PERF_MESHCC_ABI_VERSION', abi_digest.MESHCC_HEADER, abi_digest.MESHCC_RECORD, 1),
-                                 ('PERF_MESHVIS_ABI_VERSION', abi_digest.MESHVIS_HEADER, abi_digest.MESHVIS_RECORD, 1)):
-        old = json.load(open(rec))
-        assert old['version'] == ver and abi_digest.digest(hdr, macro) == old, macro
-    sets = [set(_lib._SIGS), set(_lib._SIGS_EXT), set(_lib._SIGS_SPHERE), set(_lib._SIGS_PAIR), set(_lib._SIGS_JOINT), set(_lib._SIGS_MESH), set(_lib._SIGS_BRICKMESH),
-            set(_lib._SIGS_MESHCC), set(_lib._SIGS_MESHVIS), set(_lib._SIGS_MESHSIMP)]
-    assert len(sets) == 10 and sum(len(s) for s in sets) == len(set().union(*sets))
+    assert 'int64_t n_vertices' in abi_units.params(plain, 'perf_meshsimp_place')
 
 
 def test_the_header_states_the_rule_and_what_it_does_not_do():
@@ -119,8 +83,7 @@ def test_the_header_states_the_rule_and_what_it_does_not_do():
 def test_the_unit_is_built_with_its_own_header_only():
     from perf_amd import build
     assert 'meshsimp.hip' in build.SOURCES and len(set(build.SOURCES)) == len(build.SOURCES)
-    text = open(os.path.join(ROOT, 'perf_amd', 'build.py')).read()
-    assert "'perf_hip_meshsimp.h'" in text.split('hdrs =')[1].split('\n')[0]
+    assert os.path.join(ROOT, 'include', 'perf_hip_meshsimp.h') in abi_units.build_deps()
     users = [s for s in build.SOURCES if any(p.endswith(os.sep + 'perf_hip_meshsimp.h') for p in build._includes(os.path.join(build.CSRC, s)))]
     assert users == ['meshsimp.hip'], users          # the units that include the header, by their #include lines, are the ones rebuilt for it
 
@@ -179,37 +142,14 @@ def test_refuses_counts_and_grids():
     assert lib.perf_meshsimp_table_slots(-1) == -1 and lib.perf_meshsimp_table_slots(1 << 31) == -1
 
 
-def _levels(n):
-    """L(n) of the header: the words of the scan's levels of 256 above n words, down to the level of one word."""
-    words = 0
-    while True:
-        n = -(-n // 256)
-        words += n
-        if n <= 1:
-            return words
-
-
-def _group_words(n):
-    """S(n) of the header."""
-    return 0 if n == 0 else -(-n // 256) + _levels(-(-n // 256))
-
-
-def _slots(n):
-    """T(n) of the header."""
-    t = 256
-    while t < 2 * n:
-        t *= 2
-    return t
-
-
 def test_refuses_a_bad_workspace_and_sizes_it_as_documented():
     from perf_amd import _lib
     lib = _lib.load()
     for n in (0, 1, 127, 128, 129, 4096, 4097, 65536, 65537, 14_700_000, 1 << 30, (1 << 31) - 1):
-        assert lib.perf_meshsimp_table_slots(n) == _slots(n) >= 2 * n
+        assert lib.perf_meshsimp_table_slots(n) == abi_units.slots(n) >= 2 * n
     for V, F in ((0, 0), (5, 0), (0, 7), (1, 1), (256, 256), (257, 65537), (65536, 65536), (65537, 131070), (3_700_000, 7_400_000), (14_700_000, 29_400_000),
                  (1 << 30, 1 << 30), (1 << 30, (1 << 31) - 1)):
-        need = 16 * V + 4 * _slots(V) + 4 * (F + F % 2) + 4 * _slots(F) + 8 * _group_words(V) + 32
+        need = 16 * V + 4 * abi_units.slots(V) + 4 * (F + F % 2) + 4 * abi_units.slots(F) + 8 * abi_units.group_words(V) + 32
         assert lib.perf_meshsimp_workspace_bytes(V, F) == -(-need // 16) * 16, (V, F)
     assert 24 * 14_700_000 < lib.perf_meshsimp_workspace_bytes(14_700_000, 0) < 32.1 * 14_700_000          # 24 to 32 bytes per vertex, and the levels
     assert 12 * 29_400_000 < lib.perf_meshsimp_workspace_bytes(0, 29_400_000) < 20.1 * 29_400_000          # 12 to 20 bytes per face

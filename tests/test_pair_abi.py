@@ -1,44 +1,18 @@
-"""The pair table's header (include/perf_hip_pair.h) checked without a GPU: the fourth header, its binding table, its recorded digest and
-the library agree; the three older ABIs are untouched and the four name sets are disjoint; refusals happen before a launch."""
+"""The pair table's header (include/perf_hip_pair.h) checked without a GPU: the header's constants and parameter types are the binding's (that
+header, binding, record and library agree is tests/test_abi_units.py's); refusals happen before a launch."""
 import ctypes
-import json
-import os
-import re
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID
+
 FAKE = ctypes.c_void_p(64)   # never dereferenced: every call of this file is refused before a launch
-NAMES = ['perf_adam_step_dev_pair', 'perf_hashgrid_fwd_pair', 'perf_mlp_fwd_rows', 'perf_pair_fill', 'perf_pair_version']
 
 
 def test_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is [pair] of tests/test_abi_units.py; this is what is particular to this header)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header = open(os.path.join(ROOT, 'include', 'perf_hip_pair.h')).read()
-    version = int(re.search(r'#define\s+PERF_PAIR_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_pair.abi.json')))
-    now = abi_digest.digest(abi_digest.PAIR_HEADER, 'PERF_PAIR_ABI_VERSION')
-    lib = _lib.load()
-    assert version == 1 and _lib.PAIR_ABI_VERSION == 1 and record['version'] == 1 and lib.perf_pair_version() == 1
-    assert now == record, 'include/perf_hip_pair.h changed: bump PERF_PAIR_ABI_VERSION, then `python tools/abi_digest.py --pair --write`'
-    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_PAIR) == NAMES
-    for name, (_, args) in _lib._SIGS_PAIR.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args), name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
-    # the three older ABIs are what they were, and the four name sets are disjoint
-    for rec, hdr, macro, ver in (('perf_hip.abi.json', abi_digest.HEADER, 'PERF_ABI_VERSION', 16),
-                                 ('perf_hip_ext.abi.json', abi_digest.EXT_HEADER, 'PERF_EXT_ABI_VERSION', 1),
-                                 ('perf_hip_sphere.abi.json', abi_digest.SPHERE_HEADER, 'PERF_SPHERE_ABI_VERSION', 1)):
-        old = json.load(open(os.path.join(ROOT, 'include', rec)))
-        assert old['version'] == ver and abi_digest.digest(hdr, macro) == old, rec
-    assert lib.perf_version() == 16 and lib.perf_ext_version() == 1 and lib.perf_sphere_version() == 1
-    sets = [set(_lib._SIGS), set(_lib._SIGS_EXT), set(_lib._SIGS_SPHERE), set(_lib._SIGS_PAIR)]
-    assert all(not (a & b) for i, a in enumerate(sets) for b in sets[i + 1:])
+    header, _ = abi_units.header('pair')
+    assert abi_units.const(header, 'PERF_PAIR_ABI_VERSION') == _lib.PAIR_ABI_VERSION == 1
     assert _lib.exported_symbols() == sorted(_lib._SIGS)
 
 

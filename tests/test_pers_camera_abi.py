@@ -7,14 +7,7 @@ import inspect
 import numpy as np
 import pytest
 
-PERF_E_INVALID = -1          # include/perf_hip.h
-
-
-def _refused(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
+from tests.abi_units import PERF_E_INVALID, refused as _refused
 
 
 def test_pers_raygen_refuses_bad_fovy_and_null_pointers():

@@ -1,29 +1,21 @@
-"""The sphere distance field (include/perf_hip_sphere.h, perf_amd/sphere_field.py) checked without a GPU: the third header, its binding
-table, its recorded digest and the library agree; the two older ABIs are untouched; every refusal happens before a launch with a message
-that names its reason; the MLP half is pinned on the reference's VanillaMLP; install_shims(sphere_field=True) rebinds one global."""
+"""The sphere distance field (include/perf_hip_sphere.h, perf_amd/sphere_field.py) checked without a GPU: the header's constants and parameter
+types are the binding's (that header, binding, record and library agree is tests/test_abi_units.py's); every refusal happens before a launch
+with a message that names its reason; the MLP half is pinned on the reference's VanillaMLP; install_shims(sphere_field=True) rebinds one
+global."""
 import ctypes
 import importlib
 import inspect
-import json
 import os
-import re
 import sys
 import textwrap
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PERF_E_INVALID = -1          # include/perf_hip.h
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID, refused as _call
+
 FAKE = ctypes.c_void_p(16)   # never dereferenced: every call of this file is refused before a launch
-NAMES = ['perf_sphere_field_bwd', 'perf_sphere_field_bwd_workspace_bytes', 'perf_sphere_field_fwd', 'perf_sphere_version']
-
-
-def _call(name, *args):
-    from perf_amd import _lib
-    lib = _lib.load()
-    rc = getattr(lib, name)(*args)
-    return rc, (lib.perf_last_error() or b'').decode()
 
 
 def _desc(n_levels=16, interpolation='Smoothstep', **kw):
@@ -45,32 +37,11 @@ def _bwd(gd, n=64, **kw):
 
 
 def test_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is [sphere] of tests/test_abi_units.py; this is what is particular to this header)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header = open(os.path.join(ROOT, 'include', 'perf_hip_sphere.h')).read()
-    version = int(re.search(r'#define\s+PERF_SPHERE_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_sphere.abi.json')))
-    now = abi_digest.digest(abi_digest.SPHERE_HEADER, 'PERF_SPHERE_ABI_VERSION')
-    lib = _lib.load()
-    assert version == 1 and _lib.SPHERE_ABI_VERSION == 1 and record['version'] == 1 and lib.perf_sphere_version() == 1
-    assert now == record, 'include/perf_hip_sphere.h changed: bump PERF_SPHERE_ABI_VERSION, then `python tools/abi_digest.py --sphere --write`'
-    assert list(inspect.signature(abi_digest.digest).parameters) == ['path', 'macro']
-    plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_SPHERE) == NAMES
-    for name, (_, args) in _lib._SIGS_SPHERE.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args), name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
-    # the two older ABIs are what they were, and the three name sets are disjoint
-    core = json.load(open(os.path.join(ROOT, 'include', 'perf_hip.abi.json')))
-    ext = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_ext.abi.json')))
-    assert _lib.ABI_VERSION == 16 and lib.perf_version() == 16 and core['version'] == 16 and abi_digest.digest() == core
-    assert _lib.EXT_ABI_VERSION == 1 and lib.perf_ext_version() == 1 and ext['version'] == 1
-    assert abi_digest.digest(abi_digest.EXT_HEADER, 'PERF_EXT_ABI_VERSION') == ext
-    a, b, c = set(_lib._SIGS), set(_lib._SIGS_EXT), set(_lib._SIGS_SPHERE)
-    assert not (a & b or a & c or b & c)
+    header, _ = abi_units.header('sphere')
+    assert abi_units.const(header, 'PERF_SPHERE_ABI_VERSION') == _lib.SPHERE_ABI_VERSION == 1
+    assert list(inspect.signature(abi_units.abi_digest().digest).parameters) == ['path', 'macro']
 
 
 def test_refuses_null_pointers_and_counts():

@@ -1,46 +1,25 @@
-"""The step riders' header (include/perf_hip_riders.h) checked without a GPU: header, binding table, recorded digest and library agree;
-every argument block has the fields of its ctypes mirror, in order, with matching sizes; the block-index split of every host launch
-(rider workgroups first, rays per rider workgroup) is the header's constants in the host code, the kernels and the binding; refusals
-happen before a launch."""
+"""The step riders' header (include/perf_hip_riders.h) checked without a GPU: the header's constants and parameter types are the binding's
+(that header, binding, record and library agree is tests/test_abi_units.py's); every argument block has the fields of its ctypes mirror, in
+order, with matching sizes; the block-index split of every host launch (rider workgroups first, rays per rider workgroup) is the header's
+constants in the host code, the kernels and the binding; refusals happen before a launch."""
 import ctypes
-import json
 import os
 import re
-import sys
+
+from tests import abi_units
+from tests.abi_units import PERF_E_INVALID
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'perf_amd', 'csrc')
-PERF_E_INVALID = -1          # include/perf_hip.h
 FAKE = ctypes.c_void_p(64)   # never dereferenced: every call of this file is refused before a launch
-NAMES = ['perf_adam_step_dev_riders', 'perf_field_bwd_riders', 'perf_riders_version', 'perf_sizeof_rider_count', 'perf_sizeof_rider_draw',
-         'perf_sizeof_rider_write']
 CTYPE_OF = {'uint64_t': ctypes.c_uint64, 'int64_t': ctypes.c_int64, 'int32_t': ctypes.c_int32, 'float': ctypes.c_float}
 
 
-def _header():
-    text = open(os.path.join(ROOT, 'include', 'perf_hip_riders.h')).read()
-    return text, re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-
-
 def test_header_binding_record_and_library_agree():
+    """(the agreement every unit owes is [riders] of tests/test_abi_units.py; this is what is particular to this header)"""
     from perf_amd import _lib
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import abi_digest
-    header, plain = _header()
-    version = int(re.search(r'#define\s+PERF_RIDERS_ABI_VERSION\s+(\d+)', header).group(1))
-    record = json.load(open(os.path.join(ROOT, 'include', 'perf_hip_riders.abi.json')))
-    now = abi_digest.digest(abi_digest.RIDERS_HEADER, 'PERF_RIDERS_ABI_VERSION')
-    lib = _lib.load()
-    assert version == _lib.RIDERS_ABI_VERSION == record['version'] == lib.perf_riders_version() == 1
-    assert now == record, 'include/perf_hip_riders.h changed: bump PERF_RIDERS_ABI_VERSION, then `python tools/abi_digest.py --riders --write`'
-    declared = sorted(set(re.findall(r'\b(perf_[a-z0-9_]+)\s*\(', plain)))
-    assert declared == sorted(_lib._SIGS_RIDERS) == NAMES
-    for name, (_, args) in _lib._SIGS_RIDERS.items():
-        params = re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', plain, re.S).group(1).strip()
-        assert (0 if params in ('', 'void') else len(params.split(','))) == len(args), name
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes or []) == len(args)
-    others = [_lib._SIGS, _lib._SIGS_EXT, _lib._SIGS_SPHERE, _lib._SIGS_PAIR, _lib._SIGS_JOINT, _lib._SIGS_MESH]
-    assert all(not (set(_lib._SIGS_RIDERS) & set(o)) for o in others)
+    header, _ = abi_units.header('riders')
+    assert abi_units.const(header, 'PERF_RIDERS_ABI_VERSION') == _lib.RIDERS_ABI_VERSION == 1
 
 
 def _fields_of(plain, struct):
@@ -63,7 +42,7 @@ def _fields_of(plain, struct):
 
 def test_argument_blocks_are_their_ctypes_mirrors_field_for_field():
     from perf_amd import _lib
-    _, plain = _header()
+    _, plain = abi_units.header('riders')
     lib = _lib.load()
     for struct, mirror, size in (('perf_rider_draw', _lib.RiderDraw, lib.perf_sizeof_rider_draw()), ('perf_rider_count', _lib.RiderCount, lib.perf_sizeof_rider_count()),
                                  ('perf_rider_write', _lib.RiderWrite, lib.perf_sizeof_rider_write())):
@@ -79,7 +58,7 @@ def test_argument_blocks_are_their_ctypes_mirrors_field_for_field():
 
 def test_block_index_split_is_the_headers_constants_everywhere():
     from perf_amd import _lib
-    header, _ = _header()
+    header, _ = abi_units.header('riders')
     const = {k: int(v) for k, v in re.findall(r'#define\s+(PERF_RIDER_[A-Z_]+)\s+(\d+)', header)}
     assert const == {'PERF_RIDER_THREADS': 256, 'PERF_RIDER_DRAW_RAYS': 256, 'PERF_RIDER_MARCH_RAYS': 4, 'PERF_RIDER_MAX_RAYS': 65536}
     assert (_lib.RIDER_THREADS, _lib.RIDER_DRAW_RAYS, _lib.RIDER_MARCH_RAYS, _lib.RIDER_MAX_RAYS) == (256, 256, 4, 65536)

@@ -25,6 +25,7 @@ MESHCOLOR_ABI_VERSION = 1    # PERF_MESHCOLOR_ABI_VERSION of include/perf_hip_me
 MESHRAY_ABI_VERSION = 1      # PERF_MESHRAY_ABI_VERSION of include/perf_hip_meshray.h (rays against a mesh on a uniform grid: closest hit, any hit, occlusion)
 MESHTEX_ABI_VERSION = 1      # PERF_MESHTEX_ABI_VERSION of include/perf_hip_meshtex.h (a texture atlas for a mesh, baked from the registered panoramas)
 MESHQUADRIC_ABI_VERSION = 1  # PERF_MESHQUADRIC_ABI_VERSION of include/perf_hip_meshquadric.h (quadric error placement of a simplified mesh's vertices, sums in fixed point)
+MESHNEAR_ABI_VERSION = 1     # PERF_MESHNEAR_ABI_VERSION of include/staged/perf_hip_meshnear.h (the closest point of a mesh to each query point; a staged unit)
 RIDERS_ABI_VERSION = 1       # PERF_RIDERS_ABI_VERSION of include/perf_hip_riders.h (the next batch's front end riding in the backward's launches)
 MAX_LEVELS = 24
 DTYPE_BF16, DTYPE_FP16 = 0, 1
@@ -352,6 +353,16 @@ _SIGS_RIDERS = {
     'perf_adam_step_dev_riders': (c_int, [P, P, P, P, P, c_int64, c_int, P, P, P, c_float, c_float, c_float, c_int, P, P, c_int, c_int64, POINTER(RiderWrite), P]),
 }
 
+# include/staged/perf_hip_meshnear.h: the closest point of a triangle mesh to each query point, on the grid of perf_hip_meshray.h
+# (perf_meshnear_version)
+MESHNEAR_MAX_CELLS = 1 << 24         # PERF_MESHNEAR_MAX_CELLS
+MESHNEAR_MAX_VERTICES = 1 << 30      # PERF_MESHNEAR_MAX_VERTICES
+MESHNEAR_MAX_FACES = (1 << 31) - 1   # PERF_MESHNEAR_MAX_FACES
+_SIGS_MESHNEAR = {
+    'perf_meshnear_version': (c_int, []),
+    'perf_meshnear_query': (c_int, _RAY_MESH + _RAY_BOX + [P, P, c_int64, P, c_int64, c_float, P, P, P, P, P]),
+}
+
 
 def _expects(label):
     return label + ' version {has}, this binding expects {want}'
@@ -360,12 +371,12 @@ def _expects(label):
 Unit = namedtuple('Unit', 'name version sigs mismatch sizes header record macro version_fn')
 
 
-def _unit(name, version, sigs, mismatch, sizes=()):
+def _unit(name, version, sigs, mismatch, sizes=(), folder=''):
     """One separately versioned C ABI of the library: its name, the version this binding was written against, its signatures, what a
     mismatch is reported as after "<library> has ", ((size function, the bytes this binding expects), ...).  The header and its recorded
-    digest (both in include/), the version macro and the version function follow from the name; the core, perf_hip.h, is the one
-    exception."""
-    stem, part = ('perf_hip', '') if name == 'core' else ('perf_hip_' + name, name + '_')
+    digest (both in include/, below folder when one is given), the version macro and the version function follow from the name; the
+    core, perf_hip.h, is the one exception."""
+    stem, part = ('perf_hip', '') if name == 'core' else (folder + 'perf_hip_' + name, name + '_')
     return Unit(name, version, sigs, mismatch, sizes, stem + '.h', stem + '.abi.json', f'PERF_{part.upper()}ABI_VERSION', f'perf_{part}version')
 
 
@@ -392,6 +403,12 @@ _UNITS = (
            ('perf_sizeof_rider_write', ctypes.sizeof(RiderWrite)))),
 )
 
+# The staged units: bound, version-checked, digested and built exactly like the rows above, with header and record in include/staged/.
+# A unit waits here until the pinned table of tests/test_abi_units.py is next open, and then moves up with one pin.
+_STAGED_UNITS = (
+    _unit('meshnear', MESHNEAR_ABI_VERSION, _SIGS_MESHNEAR, _expects('closest-point ABI'), folder='staged/'),
+)
+
 _lib = None
 
 
@@ -407,7 +424,7 @@ def load():
         raise PerfError(f'{LIB_PATH} not found: build it with `python -m perf_amd.build` '
                         '(there is no CPU fallback for the HIP path)')
     lib = ctypes.CDLL(LIB_PATH)
-    for unit in _UNITS:
+    for unit in _UNITS + _STAGED_UNITS:
         for name, (res, args) in unit.sigs.items():
             fn = getattr(lib, name, None)
             if fn is None:
@@ -415,7 +432,7 @@ def load():
             fn.restype = res
             fn.argtypes = args
     # the binding and the library must agree on every unit's ABI version and on the layout of the POD descriptors
-    for unit in _UNITS:
+    for unit in _UNITS + _STAGED_UNITS:
         has, want = getattr(lib, unit.version_fn)(), unit.version
         has_sizes, want_sizes = [getattr(lib, fn)() for fn, _ in unit.sizes], [n for _, n in unit.sizes]
         if has != want or has_sizes != want_sizes:

@@ -1,4 +1,4 @@
-"""Build libperf_hip.so (gfx950) in-tree with hipcc: one object per unit of SOURCES (meshquadric.hip, the quadric error placement, is the newest), rebuilt
+"""Build libperf_hip.so (gfx950) in-tree with hipcc: one object per unit of SOURCES (meshnear.hip, the closest point of a mesh, is the newest), rebuilt
 when a file it includes changed.  `python -m perf_amd.build [--force]`."""
 import os
 import re
@@ -6,14 +6,14 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-from ._lib import _UNITS
+from ._lib import _STAGED_UNITS, _UNITS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libperf_hip.so')
 # (the MLP kernels are instantiated in six units of their own: one unit took 65 s, the longest of them now takes ~15 s)
 SOURCES = ['mlp_bwd_bf16_nh2.hip', 'mlp_bwd_fp16_nh2.hip', 'mlp_bwd_bf16_nh1.hip', 'mlp_bwd_fp16_nh1.hip', 'mlp_fwd_bf16.hip', 'mlp_fwd_fp16.hip', 'mlp_fwd_rows.hip',
-           'hashgrid_bwd.hip', 'hashgrid_bwd_lines.hip', 'hashgrid_fwd.hip', 'hashgrid_aux.hip', 'march.hip', 'misc.hip', 'composite.hip', 'mlp.hip', 'visibility.hip', 'field_normal.hip', 'field_normal_bwd.hip', 'sphere_field.hip', 'hashgrid_pair.hip', 'joint_align.hip', 'mesh.hip', 'brickmesh.hip', 'meshcc.hip', 'meshvis.hip', 'meshsimp.hip', 'meshcolor.hip', 'meshray.hip', 'meshtex.hip', 'meshquadric.hip']
+           'hashgrid_bwd.hip', 'hashgrid_bwd_lines.hip', 'hashgrid_fwd.hip', 'hashgrid_aux.hip', 'march.hip', 'misc.hip', 'composite.hip', 'mlp.hip', 'visibility.hip', 'field_normal.hip', 'field_normal_bwd.hip', 'sphere_field.hip', 'hashgrid_pair.hip', 'joint_align.hip', 'mesh.hip', 'brickmesh.hip', 'meshcc.hip', 'meshvis.hip', 'meshsimp.hip', 'meshcolor.hip', 'meshray.hip', 'meshtex.hip', 'meshquadric.hip', 'meshnear.hip']
 HEADERS = ['common.hpp', 'grid_device.hpp', 'grid_fixed_point.hpp', 'mlp_reduce_device.hpp', 'step_book_device.hpp', 'mlp_device.hpp', 'field_normal_device.hpp', 'mesh_device.hpp', 'mesh_scan_device.hpp', 'mesh_filter_device.hpp', 'mesh_check_host.hpp', 'pano_lookup_device.hpp', 'march_device.hpp', 'step_riders_device.hpp', 'composite_device.hpp', 'meshtex_device.hpp']
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs (no v_accvgpr_read per accumulator register before the epilogues)
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
@@ -34,9 +34,9 @@ def _includes(path):
 
 
 def deps():
-    """what the library as a whole is rebuilt for: the sources, the device headers and the public header of every unit of _lib's table"""
+    """what the library as a whole is rebuilt for: the sources, the device headers and the public header of every unit of _lib's two tables"""
     return ([os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, h) for h in HEADERS]
-            + [os.path.join(HERE, '..', 'include', u.header) for u in _UNITS])
+            + [os.path.join(HERE, '..', 'include', u.header) for u in _UNITS + _STAGED_UNITS])
 
 
 def build(force=False, verbose=False):

@@ -907,6 +907,189 @@ def mesh_distance(mesh, grid, rays_o, rays_d) -> torch.Tensor:
     return ops.meshray_cast(vertices, faces, grid.origin, grid.cell, grid.dims, grid.offsets, grid.refs, rays_o.contiguous(), rays_d.contiguous(), uv=False)[0]
 
 
+# ---- mesh-to-mesh deviation: the closest point of a mesh, on the rays' grid (include/staged/perf_hip_meshnear.h) -----------------------------
+class NearestHits(NamedTuple):
+    dist2: torch.Tensor                          # [N] float64: the squared distance to the closest point, +inf where there is no answer
+    distance: torch.Tensor                       # [N] fp32: dist2.sqrt().float()
+    face: torch.Tensor                           # [N] int32: the face of the closest point (the smallest index among equals), -1 where none
+    u: torch.Tensor                              # [N] fp32: the closest point is (1 - u - v) a + u b + v c; 0 where there is no answer
+    v: torch.Tensor                              # [N] fp32
+
+
+class Deviation(NamedTuple):
+    max: float                                   # the largest distance of a sample of a to b; +inf when a sample has no answer within max_distance
+    mean: float                                  # over the samples that have an answer, as rms and p90
+    rms: float
+    p90: float                                   # nearest rank: the ceil(0.9 n)-th smallest distance
+    argmax_point: tuple                          # the sample of max (the first of equals), three floats; None without samples
+    argmax_face_of_b: int                        # the face of b closest to it; -1 when it has no answer
+    n_samples: int
+    n_beyond: int = 0                            # samples with no answer within max_distance (or not finite): counted, and they make max +inf
+    a_to_b: Optional['Deviation'] = None         # symmetric: the two directions; the fields above are those of the direction with the larger
+    b_to_a: Optional['Deviation'] = None         # max (the sampled Hausdorff distance), a_to_b's when they are equal
+
+
+def closest_point(mesh, grid, points, max_distance=float('inf')) -> NearestHits:
+    """The closest point of the mesh to every point (CUDA fp32 [N, 3]) by the rule of include/staged/perf_hip_meshnear.h -- the double
+    seven-region closest point of a triangle, the lexicographic minimum of (dist2, face index) over ALL faces -> NearestHits.  grid: the
+    RayGrid of build_ray_grid; it only skips faces that cannot be the answer, so the result does not depend on its cell and is
+    bit-identical from run to run.  A point that is not finite, a mesh without a valid face and an answer beyond max_distance give +inf,
+    -1, 0, 0.  The search visits the O((d / cell)^3) cells within the answer's distance d: bound it with max_distance for points far from
+    the mesh.  No host read."""
+    vertices, faces = _check_grid('closest_point', mesh, grid)
+    if not torch.is_tensor(points) or not points.is_cuda:
+        raise _lib.PerfError('closest_point: points must be a CUDA tensor (there is no CPU path)')
+    if not float(max_distance) >= 0.0:
+        raise _lib.PerfError(f'closest_point: max_distance ({max_distance}) is NaN or negative')
+    dist2, face, u, v = ops.meshnear_query(vertices, faces, grid.origin, grid.cell, grid.dims, grid.offsets, grid.refs, points.contiguous(), max_distance)
+    return NearestHits(dist2, dist2.sqrt().float(), face, u, v)
+
+
+def _lattice(order):
+    """The barycentric lattice points (i, j, k) with i + j + k = order that are not corners, j ascending, then k ascending."""
+    return [(order - j - k, j, k) for j in range(order + 1) for k in range(order + 1 - j) if order not in (order - j - k, j, k)]
+
+
+def surface_samples(mesh, order=2):
+    """Points on the mesh -> (points fp32 [M, 3], face int32 [M]): the vertices first, with face -1; then per face, in face order, the
+    barycentric lattice points (i, j, k) / order that are not corners (j ascending, then k; order 2: the three edge midpoints), each
+    formed in float64 as ((i a + j b) + k c) / order and rounded once to fp32.  order 1: the vertices alone.  M = V + F ((order + 1)
+    (order + 2) / 2 - 3).  The samples of a face with an index outside [0, V) are NaN.  Plain torch; no host read."""
+    _check_mesh('surface_samples', mesh)
+    order = int(order)
+    if order < 1:
+        raise _lib.PerfError(f'surface_samples: order {order} is below 1')
+    vertices, faces = mesh.vertices.float(), mesh.faces
+    n_vertices, n_faces = int(vertices.shape[0]), int(faces.shape[0])
+    lattice = _lattice(order)
+    face_of = torch.full((n_vertices,), -1, dtype=torch.int32, device=vertices.device)
+    if not lattice or n_faces == 0 or n_vertices == 0:
+        return vertices.contiguous(), face_of
+    valid = ((faces >= 0) & (faces < n_vertices)).all(dim=1)
+    corners = vertices.double()[faces.clamp(0, n_vertices - 1).long()]                        # [F, 3, 3]
+    a, b, c = corners[:, 0], corners[:, 1], corners[:, 2]
+    inner = torch.stack([((i * a + j * b) + k * c) / order for i, j, k in lattice], dim=1)          # [F, L, 3]
+    inner = torch.where(valid[:, None, None], inner, torch.full_like(inner, float('nan'))).float().reshape(-1, 3)
+    ids = torch.arange(n_faces, dtype=torch.int32, device=vertices.device).repeat_interleave(len(lattice))
+    return torch.cat([vertices, inner]).contiguous(), torch.cat([face_of, ids])
+
+
+_DEVIATION_WORDS = 10          # of one direction's statistics on the device
+
+
+def _direction_stats(points, hits):
+    """float64 [10] on the device: max dist2, mean, rms, p90 dist2, the index of max, its face, the samples with an answer, its point."""
+    n = int(points.shape[0])
+    if n == 0:
+        return torch.zeros(_DEVIATION_WORDS, dtype=torch.float64, device=points.device)
+    dist2 = hits.dist2
+    within = hits.face >= 0
+    n_within = within.sum()
+    count = n_within.clamp(min=1).double()
+    zero = torch.zeros_like(dist2)
+    mean = torch.where(within, dist2.sqrt(), zero).sum() / count
+    rms = (torch.where(within, dist2, zero).sum() / count).sqrt()
+    rank = ((9 * n_within + 9) // 10 - 1).clamp(min=0)                                        # ceil(0.9 n) - 1; the samples beyond sort last (+inf)
+    p90 = dist2.sort().values[rank]
+    top = dist2.argmax()                                                                     # (the first of equal maxima)
+    return torch.cat([torch.stack([dist2[top], mean, rms, p90, top.double(), hits.face[top].double(), n_within.double()]), points[top].double()])
+
+
+def _deviation_of(words, n):
+    if n == 0:
+        return Deviation(0.0, 0.0, 0.0, 0.0, None, -1, 0)
+    max2, mean, rms, p90, _, face, n_within = words[:7]
+    return Deviation(math.sqrt(max2), mean, rms, math.sqrt(p90) if n_within else 0.0, tuple(words[7:10]), int(face), n, n - int(n_within))
+
+
+def _deviations(directions):
+    """[(samples, mesh, grid, max_distance)] -> [Deviation], with ONE host read for all of them."""
+    stats = [_direction_stats(points, closest_point(mesh, grid, points, max_distance)) for points, mesh, grid, max_distance in directions]
+    words = torch.cat(stats).tolist()                                                        # the one host read
+    return [_deviation_of(words[_DEVIATION_WORDS * i:_DEVIATION_WORDS * (i + 1)], int(d[0].shape[0])) for i, d in enumerate(directions)]
+
+
+def _symmetric(forward, backward):
+    return (forward if forward.max >= backward.max else backward)._replace(a_to_b=forward, b_to_a=backward)
+
+
+def mesh_deviation(a, b, order=2, symmetric=True, cell=None, max_distance=float('inf')) -> Deviation:
+    """How far mesh a lies from mesh b: the distances from surface_samples(a, order) to their closest points on b (closest_point), and with
+    symmetric also those from b's samples to a; the fields are then those of the direction with the larger max -- the SAMPLED Hausdorff
+    distance: a lower bound of the true one, which is attained somewhere between the samples -- with both directions in a_to_b and b_to_a.
+    The statistics are torch reductions of the float64 dist2 on the device, read back ONCE at the end (beside the grids' own reads).
+    Samples without an answer within max_distance are counted in n_beyond and make max +inf: they are not dropped from it.  cell: of
+    build_ray_grid."""
+    _check_mesh('mesh_deviation', a)
+    _check_mesh('mesh_deviation', b)
+    directions = [(surface_samples(a, order)[0], b, build_ray_grid(b, cell), max_distance)]
+    if symmetric:
+        directions.append((surface_samples(b, order)[0], a, build_ray_grid(a, cell), max_distance))
+    out = _deviations(directions)
+    return _symmetric(*out) if symmetric else out[0]
+
+
+def median_edge_length(mesh) -> float:
+    """The median length of the 3 F face edges, computed on the device in float64 (one host read); 0 for a mesh without faces."""
+    _check_mesh('median_edge_length', mesh)
+    n_vertices, n_faces = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
+    if n_faces == 0 or n_vertices == 0:
+        return 0.0
+    corners = mesh.vertices.double()[mesh.faces.clamp(0, n_vertices - 1).long()]
+    edges = (corners - corners.roll(-1, dims=1)).norm(dim=2).reshape(-1)
+    return float(edges.nan_to_num(nan=0.0, posinf=0.0).median())
+
+
+def tolerance_ladder(mesh, steps=10):
+    """The default cells of simplify_to_tolerance: 16 times the mesh's median edge length, then each 1 / sqrt(2) of the one before."""
+    first = 16.0 * median_edge_length(mesh)
+    return [first * 0.5 ** (0.5 * k) for k in range(steps)] if first > 0 else []
+
+
+def simplify_to_tolerance(mesh, tol, cells=None, placement='quadric', order=2, **kw):
+    """The coarsest simplification of the mesh that stays within tol of it -> (Mesh, cell, Deviation).  cells: the cell edges to try,
+    scanned in the order given, coarse to fine; default tolerance_ladder(mesh): at most ten, from 16 times the median edge length, each
+    1 / sqrt(2) of the one before.  The first cell whose symmetric sampled deviation (mesh_deviation, order) has max <= tol is returned.
+    No monotonicity is assumed: every cell is measured against the original.  If none passes, the finest (last) is returned with its
+    deviation and a RuntimeWarning says so.  kw: simplify_mesh's (box, dedupe), and max_distance for the deviation's searches (a limit
+    at or above tol leaves the decision as it is: a sample beyond it makes max +inf)."""
+    _check_mesh('simplify_to_tolerance', mesh)
+    tol = float(tol)
+    if not tol >= 0.0:
+        raise _lib.PerfError(f'simplify_to_tolerance: the tolerance {tol} is NaN or negative')
+    max_distance = kw.pop('max_distance', float('inf'))
+    cells = tolerance_ladder(mesh) if cells is None else [float(c) for c in cells]
+    if not cells:
+        raise _lib.PerfError('simplify_to_tolerance: no cell to try (a mesh without faces has no edge length to start from)')
+    samples, grid = surface_samples(mesh, order)[0], build_ray_grid(mesh)
+    for cell in cells:
+        small = simplify_mesh(mesh, cell, placement=placement, **kw)[0]
+        deviation = _symmetric(*_deviations([(surface_samples(small, order)[0], mesh, grid, max_distance), (samples, small, build_ray_grid(small), max_distance)]))
+        if deviation.max <= tol:
+            return small, cell, deviation
+    import warnings
+    warnings.warn(f'simplify_to_tolerance: no cell of {cells} stays within {tol}: the finest is returned with a deviation of {deviation.max}', RuntimeWarning)
+    return small, cell, deviation
+
+
+def transfer_vertex_values(src_mesh, values, hits) -> torch.Tensor:
+    """The values [V, C] of src_mesh's vertices at the closest points of hits (closest_point against src_mesh) -> [N, C] of values' dtype:
+    ((1 - u - v) val[a] + u val[b]) + v val[c] in float64, rounded once; NaN where a point has no answer.  The original's colours at a
+    simplified mesh's vertices, for one.  Plain torch; no host read."""
+    _check_mesh('transfer_vertex_values', src_mesh)
+    n_vertices = int(src_mesh.vertices.shape[0])
+    if not torch.is_tensor(values) or values.dim() != 2 or int(values.shape[0]) != n_vertices or values.device != src_mesh.vertices.device:
+        raise _lib.PerfError(f'transfer_vertex_values: values must be a [{n_vertices}, C] tensor on the mesh\'s device')
+    n = int(hits.face.shape[0])
+    if int(src_mesh.faces.shape[0]) == 0 or n_vertices == 0:
+        return torch.full((n, int(values.shape[1])), float('nan'), dtype=values.dtype, device=values.device)
+    corners = src_mesh.faces[hits.face.clamp(min=0).long()].clamp(0, n_vertices - 1).long()          # [N, 3]
+    val = values.double()
+    u, v = hits.u.double()[:, None], hits.v.double()[:, None]
+    out = (((1.0 - u) - v) * val[corners[:, 0]] + u * val[corners[:, 1]]) + v * val[corners[:, 2]]
+    return torch.where((hits.face >= 0)[:, None], out, torch.full_like(out, float('nan'))).to(values.dtype)
+
+
 def write_ply(path, mesh):
     """Binary little-endian PLY: x y z [nx ny nz] [red green blue as uchar] per vertex, a uchar-counted int list per face."""
     v = mesh.vertices.detach().cpu().numpy().astype('<f4')

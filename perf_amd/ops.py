@@ -1444,6 +1444,27 @@ def meshray_occluded(vertices, faces, origin, cell, dims, offsets, refs, centres
     return out
 
 
+# ---- the closest point of a mesh to each query point, on the same grid (include/staged/perf_hip_meshnear.h) ------------------------------
+def meshnear_query(vertices, faces, origin, cell, dims, offsets, refs, points, max_distance=float('inf'), uv=True):
+    """The closest point of the mesh to every point -> (dist2 float64 [N], face int32 [N], u, v fp32 [N] or None without uv): the
+    lexicographic minimum of (dist2, face index) over ALL faces by the rule of include/staged/perf_hip_meshnear.h, searched over the grid
+    meshray_grid_write made of the SAME mesh; +inf, -1, 0, 0 for a point that is not finite, for a mesh without a valid face and beyond
+    max_distance (perf_meshnear_query)."""
+    vertices, nv, grid = _ray_grid('meshnear_query', vertices, faces, origin, cell, dims, offsets, refs)
+    dev = vertices.device
+    points = _dev_tensor('meshnear_query', 'points', points, torch.float32, ('N', 3), dev)
+    n = int(points.shape[0])
+    limit = float(max_distance)
+    if not limit >= 0.0:
+        raise _lib.PerfError(f'meshnear_query: max_distance ({max_distance}) is NaN or negative')
+    dist2, face = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    u = v = None
+    if uv:
+        u, v = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+    _call('perf_meshnear_query', *grid, _pn(points), n, limit, _pn(dist2), _pn(face), _pn(u), _pn(v), _stream())
+    return dist2, face, u, v
+
+
 def normal_composite(weights, grad, packed):
     """normal [R,3] = unit(sum_i w_i * (-grad_i / |grad_i|)) per ray, exactly zero for rays without samples (perf_normal_composite)."""
     R = packed.shape[0]

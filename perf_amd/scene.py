@@ -1716,6 +1716,20 @@ class NeRFScene:
         from .mesh import cull_occluded
         return cull_occluded(mesh, sup_pool, **kw)
 
+    def mesh_deviation(self, a, b, **kw):
+        """How far mesh a lies from mesh b, sampled: the closest points on the device (perf_amd/mesh.py: mesh_deviation's keywords) ->
+        mesh.Deviation."""
+        from .mesh import mesh_deviation
+        return mesh_deviation(a, b, **kw)
+
+    def simplify_mesh_to_tolerance(self, mesh, tol, **kw):
+        """The coarsest clustering of the mesh, on the grid over the scene's aabb, whose sampled deviation from it stays within tol
+        (perf_amd/mesh.py: simplify_to_tolerance's keywords) -> (mesh.Mesh, cell, mesh.Deviation)."""
+        from .mesh import simplify_to_tolerance
+        aabb = [float(v) for v in self.nerf._aabb_host]
+        kw.setdefault('box', (aabb[:3], aabb[3:]))
+        return simplify_to_tolerance(mesh, tol, **kw)
+
     def render_mesh_distance(self, mesh, rays: Rays, grid=None):
         """The distance panorama of the mesh itself: the closest hit of every ray -> [..., 1], the shape of render's 'distance'.  The value
         is the ray parameter t of rays.o + t rays.d: a distance for unit directions (gen_pano_rays and gen_pers_rays give them), as

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Digest of one C ABI of the library: sha256 over the comment-free, whitespace-normalised text of every `perf_*` prototype, struct
-and #define of its header, in file order.  The units are the rows of perf_amd/_lib.py's table; a unit NAME has the header
+and #define of its header, in file order.  The units are the rows of perf_amd/_lib.py's two tables (a staged unit's header and record
+lie in include/staged/); a unit NAME has the header
 include/perf_hip_NAME.h, the version macro PERF_NAME_ABI_VERSION and the record include/perf_hip_NAME.abi.json, and the core is
 include/perf_hip.h, PERF_ABI_VERSION, include/perf_hip.abi.json.  `python tools/abi_digest.py` prints {version, digest} of the core,
 `--NAME` (`--ext` ... `--riders`) of that unit; `--write` records it.  tests/test_abi_units.py fails when the digest of a header differs
@@ -14,9 +15,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from perf_amd._lib import _UNITS  # noqa: E402
+from perf_amd._lib import _STAGED_UNITS, _UNITS  # noqa: E402
 
-UNITS = {u.name: u for u in _UNITS}
+UNITS = {u.name: u for u in _UNITS + _STAGED_UNITS}
 
 
 def header_path(name='core'):

@@ -3,7 +3,8 @@
   python tools/extract_mesh.py --out room.ply [--resolution 256] [--threshold T] [--no-occupancy] [--no-colors] [--no-normals] [--sparse]
                                [--seen-by-panoramas [--occlusion] [--visibility-tol T] [--carve] [--sup-pool pool.pt]]
                                [--min-component-faces N] [--keep-largest K] [--orientation inward|outward]
-                               [--simplify-cell H [--simplify-placement mean|member|quadric] [--simplify-dedupe oriented|unoriented|none]]
+                               [--simplify-cell H | --simplify-tolerance E] [--simplify-placement mean|member|quadric]
+                               [--simplify-dedupe oriented|unoriented|none] [--report-deviation]
                                [--colors-from-panoramas [--color-select blend|best] [--color-power N] [--sup-pool pool.pt]]
                                [--texture SIZE [--texture-source panoramas|field] [--texture-tile T]]
                                [--checkpoint scene.pt | --geo 3000 --app 1500] [--dtype fp16]
@@ -53,12 +54,20 @@ ap.add_argument('--texture', type=int, default=None, metavar='SIZE',
 ap.add_argument('--texture-source', choices=['panoramas', 'field'], default='panoramas',
                 help='with --texture: the registered panoramas blended as --colors-from-panoramas blends them at every texel, or the field\'s own colours')
 ap.add_argument('--texture-tile', type=int, default=None, help='with --texture: the tile edge in texels (default: the largest that holds the faces)')
+ap.add_argument('--simplify-tolerance', type=float, default=None, metavar='E',
+                help='instead of --simplify-cell: the coarsest cell of a ladder (from 16 median edge lengths down, each 1/sqrt(2) of the one before) whose sampled '
+                     'deviation from the cleaned mesh stays within E scene units')
+ap.add_argument('--report-deviation', action='store_true',
+                help='print the sampled deviation (max, mean, rms, p90 of the closest-point distances, both directions) of every stage\'s output from the stage '
+                     'before it: cull, cleaning, simplification')
 ap.add_argument('--checkpoint', default=None, help='a torch.save of NeRFScene.state_dict()')
 ap.add_argument('--geo', type=int, default=3000)
 ap.add_argument('--app', type=int, default=1500)
 ap.add_argument('--batch', type=int, default=4096)
 ap.add_argument('--dtype', default='fp16')
 args = ap.parse_args()
+if args.simplify_cell is not None and args.simplify_tolerance is not None:
+    ap.error('--simplify-cell and --simplify-tolerance are exclusive: the cell is given, or found for the tolerance')
 
 torch.manual_seed(0); np.random.seed(0)
 scene = NeRFScene(dtype=args.dtype)
@@ -90,19 +99,35 @@ else:
                               normals=not args.no_normals)
 torch.cuda.synchronize(); t2 = time.perf_counter()
 extracted = (len(mesh.vertices), len(mesh.faces))
+deviations = {}          # --report-deviation: stage -> the deviation of its output from its input
+
+
+def report(stage, before, after, known=None):
+    if args.report_deviation and len(before.faces) and len(after.faces):
+        d = known if known is not None else scene.mesh_deviation(after, before)
+        deviations[stage] = {k: getattr(d, k) for k in ('max', 'mean', 'rms', 'p90', 'argmax_point', 'n_samples', 'n_beyond')}
+    return after
+
+
 if args.seen_by_panoramas:          # first the faces no panorama saw, then the components of what is left
     if args.occlusion:          # (the depth test against the panoramas and the segment test against the mesh itself)
-        mesh = scene.cull_occluded_mesh(mesh, views, tol=args.visibility_tol, carve=args.carve)
+        mesh = report('cull', mesh, scene.cull_occluded_mesh(mesh, views, tol=args.visibility_tol, carve=args.carve))
     else:
-        mesh = scene.cull_unseen_mesh(mesh, views, tol=args.visibility_tol, carve=args.carve)
+        mesh = report('cull', mesh, scene.cull_unseen_mesh(mesh, views, tol=args.visibility_tol, carve=args.carve))
 seen = {'seen_vertices': len(mesh.vertices), 'seen_faces': len(mesh.faces)} if args.seen_by_panoramas else {}
 if args.min_component_faces > 0 or args.keep_largest is not None or args.orientation is not None:          # after either extraction path
-    mesh = scene.clean_mesh(mesh, min_faces=args.min_component_faces, keep_largest=args.keep_largest, orientation=args.orientation)
+    mesh = report('clean', mesh, scene.clean_mesh(mesh, min_faces=args.min_component_faces, keep_largest=args.keep_largest, orientation=args.orientation))
 if args.colors_from_panoramas:          # on the fine vertices, which lie on the surface the depth test was made for; the simplification carries the colours
     mesh = scene.color_mesh_from_panoramas(mesh, views, tol=args.visibility_tol, select=args.color_select, power=args.color_power)
-cleaned = {'cleaned_vertices': len(mesh.vertices), 'cleaned_faces': len(mesh.faces)} if args.simplify_cell is not None else {}
+cleaned = {'cleaned_vertices': len(mesh.vertices), 'cleaned_faces': len(mesh.faces)} if args.simplify_cell is not None or args.simplify_tolerance is not None else {}
 if args.simplify_cell is not None:          # last: the cull and the cleaning have seen the mesh as it was extracted
-    mesh = scene.simplify_mesh(mesh, args.simplify_cell, placement=args.simplify_placement, dedupe=None if args.simplify_dedupe == 'none' else args.simplify_dedupe)
+    mesh = report('simplify', mesh, scene.simplify_mesh(mesh, args.simplify_cell, placement=args.simplify_placement,
+                                                        dedupe=None if args.simplify_dedupe == 'none' else args.simplify_dedupe))
+elif args.simplify_tolerance is not None:          # the cell is found: the coarsest of the ladder within the tolerance
+    small, found_cell, deviation = scene.simplify_mesh_to_tolerance(mesh, args.simplify_tolerance, placement=args.simplify_placement,
+                                                                    dedupe=None if args.simplify_dedupe == 'none' else args.simplify_dedupe)
+    cleaned['simplify_cell'] = found_cell
+    mesh = report('simplify', mesh, small, deviation)
 textured = {}
 if args.texture is not None:          # after the simplification: the small mesh carries as many colour samples as the atlas has texels
     if args.texture_source == 'panoramas':
@@ -117,4 +142,4 @@ if args.texture is not None:
 else:
     write_ply(args.out, mesh)
 print(json.dumps({'out': args.out, 'vertices': len(mesh.vertices), 'faces': len(mesh.faces), 'resolution': args.resolution, 'sparse': args.sparse,
-                  'threshold': args.threshold, 'extracted_vertices': extracted[0], 'extracted_faces': extracted[1], **seen, **cleaned, **textured, 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'clean_s': t3 - t2, 'bytes': os.path.getsize(args.out)}))
+                  'threshold': args.threshold, 'extracted_vertices': extracted[0], 'extracted_faces': extracted[1], **seen, **cleaned, **textured, **({'deviation': deviations} if args.report_deviation else {}), 'prepare_s': t1 - t0, 'extract_s': t2 - t1, 'clean_s': t3 - t2, 'bytes': os.path.getsize(args.out)}))

@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256, (NH == 1 && KS == 1 && !FUSED && !ROWS) ? 5 : 
     const int64_t n_tiles = (n_live + kTile - 1) / kTile;
     struct TileIn { u32x4 b1[KS]; uint8_t sv; };
     // the layers and the store of one tile, given the packed first-layer operand
-    auto layers = [&](int64_t si, bool valid, const u32x4 (&b1)[KS], float sv) __attribute__((always_inline)) {
+    auto layers = [&](int64_t si, bool valid, const u32x4 (&b1)[KS], uint32_t sv) __attribute__((always_inline)) {
         // (the smallest net's six fragments are read per tile, as everywhere else: held in registers across the loop they cost
         // the kernel 20 registers and its fifth wave per SIMD)
         if constexpr (kSmallestPlain) asm volatile("" ::: "memory");
@@ -294,18 +294,25 @@ __global__ __launch_bounds__(256, (NH == 1 && KS == 1 && !FUSED && !ROWS) ? 5 : 
             // the activation is a kernel argument: branch on it ONCE (scalar), and stop at the last register that can hold
             // a real output row (rows of register r: d_row(r, 0) < d_row(r, 1)) -- otherwise both exponentials are
             // evaluated for all 8 registers and selected afterwards (~250 vector instructions per tile)
+            // a masked sample (sv == 0) is 0 by SELECTION, not by multiplication: its activation may be inf (an exponential that
+            // overflows), and inf * 0 is NaN.  The selection is one AND with an all-ones / zero word that takes the selector's register
+            // (any non-zero selector byte keeps the sample; a masked one is +0).
+            uint32_t keep = 0u - (sv < 1u ? sv : 1u);
+            asm("" : "+v"(keep));       // (opaque: the compiler turns the AND back into selects on a held condition -- two scalar registers
+                                        //  too many for <NH = 1, KS = 2>, which spilled them into a vector register: tests/test_mlp_fwd_resources.py)
+            auto kept = [&](float v) { return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, v) & keep); };
             auto emit = [&](auto act) {
                 if (mp.n_out == 16 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {   // registers 0..3 / 4..7 are rows 4h..4h+3 / 8+4h..: two 16-byte stores
                     float* row0 = out + si * 16 + 4 * h;
-                    *reinterpret_cast<float4*>(row0) = make_float4(act(o[0]) * sv, act(o[1]) * sv, act(o[2]) * sv, act(o[3]) * sv);
-                    *reinterpret_cast<float4*>(row0 + 8) = make_float4(act(o[4]) * sv, act(o[5]) * sv, act(o[6]) * sv, act(o[7]) * sv);
+                    *reinterpret_cast<float4*>(row0) = make_float4(kept(act(o[0])), kept(act(o[1])), kept(act(o[2])), kept(act(o[3])));
+                    *reinterpret_cast<float4*>(row0 + 8) = make_float4(kept(act(o[4])), kept(act(o[5])), kept(act(o[6])), kept(act(o[7])));
                     return;
                 }
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
                     if (d_row(r, 0) >= mp.n_out) break;
                     const int row = d_row(r, h);
-                    if (row < mp.n_out) out[si * mp.n_out + row] = act(o[r]) * sv;
+                    if (row < mp.n_out) out[si * mp.n_out + row] = kept(act(o[r]));
                 }
             };
             if (mp.out_act == PERF_ACT_SIGMOID) emit([](float y) { return 1.0f / (1.0f + expf(-y)); });
@@ -335,7 +342,7 @@ __global__ __launch_bounds__(256, (NH == 1 && KS == 1 && !FUSED && !ROWS) ? 5 : 
                     }
                     b1[s][i] = pair;
                 }
-            layers(si, valid, b1, (valid && sel) ? (float)sel[si] : 1.0f);
+            layers(si, valid, b1, (valid && sel) ? (uint32_t)sel[si] : 1u);
         }
     } else if constexpr (ROWS) {
         if (tile >= n_tiles) return;
@@ -364,7 +371,7 @@ __global__ __launch_bounds__(256, (NH == 1 && KS == 1 && !FUSED && !ROWS) ? 5 : 
             };
             auto process = [&](int64_t tl, const TileIn& t) __attribute__((always_inline)) {
                 const int64_t si = tl * kTile + c;
-                layers(si, si < n_live, t.b1, sel ? (float)t.sv : 1.0f);
+                layers(si, si < n_live, t.b1, sel ? (uint32_t)t.sv : 1u);
             };
             TileIn ta, tb;
             request(tile, row_of(tile), ta);
@@ -394,7 +401,7 @@ __global__ __launch_bounds__(256, (NH == 1 && KS == 1 && !FUSED && !ROWS) ? 5 : 
                         const int level = 8 * s + 2 * i + h;
                         b1[s][i] = (valid && level < mp.n_levels) ? feat[(int64_t)level * fz.stride + row] : 0u;
                     }
-                layers(si, valid, b1, (valid && sel) ? (float)sel[si] : 1.0f);
+                layers(si, valid, b1, (valid && sel) ? (uint32_t)sel[si] : 1u);
             }
         }
     } else if (n <= kMaxFastStride && mp.n_levels == 8 * KS) {      // (uniform) see kMaxFastStride
@@ -419,7 +426,7 @@ __global__ __launch_bounds__(256, (NH == 1 && KS == 1 && !FUSED && !ROWS) ? 5 : 
         };
         auto process = [&](int64_t tl, const TileIn& t) __attribute__((always_inline)) {
             const int64_t si = tl * kTile + c;
-            layers(si, si < n_live, t.b1, sel ? (float)t.sv : 1.0f);
+            layers(si, si < n_live, t.b1, sel ? (uint32_t)t.sv : 1u);
         };
         TileIn ta, tb;
         request(tile, ta);
@@ -445,7 +452,7 @@ __global__ __launch_bounds__(256, (NH == 1 && KS == 1 && !FUSED && !ROWS) ? 5 : 
                     const int level = 8 * s + 2 * i + h;
                     b1[s][i] = (valid && level < mp.n_levels) ? feat[(int64_t)level * n + si] : 0u;
                 }
-            layers(si, valid, b1, (valid && sel) ? (float)sel[si] : 1.0f);
+            layers(si, valid, b1, (valid && sel) ? (uint32_t)sel[si] : 1u);
         }
     }
 }

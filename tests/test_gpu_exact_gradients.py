@@ -297,130 +297,9 @@ def test_two_raw_tables_added_and_unfixed_on_a_slice(ops):
 
 
 # ---- B: exact-arithmetic cases of the MLP kernels -------------------------------------------------------------------------------
-DT = {'bf16': (torch.bfloat16, 256), 'fp16': (torch.float16, 2048)}      # integers up to this magnitude are exact in the type
-S_FEAT, S_DOUT = 0.25, 0.125                                             # powers of two: features / output gradients are integers times these
-
-
-def _sparse_int(o, i, k, mag, g):
-    """[o, i] matrix of small integers, k non-zeros per row, at most k * ceil(o / i) per column"""
-    W = torch.zeros(o, i)
-    for j in range(k):
-        perm = torch.cat([torch.randperm(i, generator=g) for _ in range(-(-o // i))])[:o]
-        W[torch.arange(o), perm] = torch.randint(1, mag + 1, (o,), generator=g).float() * (torch.randint(0, 2, (o,), generator=g) * 2 - 1).float()
-    return W
-
-
-def _exact_mlp(dt, nh, n_out, n_levels, n, seed, sel_mode, nnz=3, n_src=None):
-    from perf_amd.grid import MlpConfig
-    cfgm = MlpConfig(n_levels=n_levels, n_hidden_layers=nh, n_output_dims=n_out, output_activation='None')
-    g = torch.Generator().manual_seed(seed)
-    mag = 2 if n <= 5000 else 1                          # the value range shrinks with n: every fp32 sum over the samples stays below 2^24
-    # (every column of W1 -- padded inputs included -- and every row of W_out -- rows >= n_out included -- holds weights)
-    w = torch.cat([_sparse_int(o, i, nnz, mag, g).reshape(-1) for o, i in cfgm.shapes])
-    rows = n if n_src is None else n_src
-    feat = torch.randint(-mag, mag + 1, (n_levels, rows, 2), generator=g).float() * S_FEAT
-    dout = torch.randint(-mag, mag + 1, (n, n_out), generator=g).float() * S_DOUT
-    dout[0, 0] = S_DOUT                                  # (the first sample counts whatever the draw: batches of one, live counts of one)
-    if sel_mode == 'zeros':
-        sel = (torch.rand(n, generator=g) > 0.2).to(torch.uint8)
-        sel[0] = 1
-    else:
-        sel = torch.ones(n, dtype=torch.uint8) if sel_mode == 'ones' else None
-    return cfgm, w, feat, sel, dout
-
-
-def _exact_reference(cfgm, w, feat, sel, dout, n_live, dt, activity=True):
-    """float64 forward and autograd; asserts the conditions under which it is what the kernels must give to the bit.  activity=False:
-    the shares of active / tied / negative units are conditions on a population -- a caller that runs a few rows of one has asserted
-    them on the whole of it"""
-    tdt, cap = DT[dt]
-    n = feat.shape[1]
-    x = feat.permute(1, 0, 2).reshape(n, -1).double()
-    x = torch.cat([x, x.new_zeros(n, cfgm.n_in_pad - x.shape[1])], 1).requires_grad_(True)
-    Ws, off = [], 0
-    for o, i in cfgm.shapes:
-        Ws.append(w[off:off + o * i].view(o, i).double().requires_grad_(True))
-        off += o * i
-    h, zs, ins = x, [], []
-    for W in Ws[:-1]:
-        ins.append(h)
-        z = h @ W.t()
-        z.retain_grad()
-        zs.append(z)
-        h = torch.relu(z)
-    ins.append(h)
-    y = (h @ Ws[-1].t())[:, :cfgm.n_output_dims]
-    y.retain_grad()
-    out = y * (sel.double()[:, None] if sel is not None else 1.0)
-    (out[:n_live] * dout[:n_live].double()).sum().backward()
-
-    def exact16(t):
-        return torch.equal(t.to(tdt).double(), t)
-    # ---- the conditions (on the reference, before the GPU is touched)
-    assert exact16(w.double()) and exact16(feat.double()) and exact16(y.grad)
-    s = S_FEAT
-    for z in zs:                                         # hidden pre-activations, and their gradients dH (masked): integers the type holds
-        assert exact16(z.detach()) and float(z.detach().abs().max()) / s <= cap
-        assert exact16(z.grad) and float(z.grad.abs().max()) / S_DOUT <= cap
-        if not activity:
-            continue
-        live = z.detach()[:n_live]
-        assert float((live > 0).double().mean()) >= 0.25, 'too few active hidden units'
-        assert float((live == 0).double().mean()) >= 0.01, 'no ReLU ties'
-        assert float((live < 0).double().mean()) >= 0.01
-    # every fp32 sum: sum of |terms| below 2^24 units (forward rows, dX rows, and every dW entry summed over ALL samples)
-    unit = S_FEAT * S_DOUT
-    dzs = [z.grad for z in zs] + [torch.cat([y.grad, y.grad.new_zeros(n, 16 - y.grad.shape[1])], 1)]
-    for W, a, dz in zip(Ws, ins, dzs):
-        assert float((a.detach().abs() @ W.detach().abs().t()).max()) / S_FEAT < 2 ** 24
-        assert float((dz.abs() @ W.detach().abs()).max()) / S_DOUT < 2 ** 24
-        assert float((dz.abs().t() @ a.detach().abs()).max()) / unit < 2 ** 24
-    dw = torch.cat([W.grad.reshape(-1) for W in Ws])
-    dfeat = x.grad[:, :2 * cfgm.n_levels].reshape(n, cfgm.n_levels, 2).permute(1, 0, 2)
-    for t in (out.detach(), dw, dfeat):
-        assert torch.equal(t.float().double(), t)        # the answer itself is an fp32 number
-    assert float(dw.abs().max()) > 0 and float(dfeat.abs().max()) > 0 and float(out.detach().abs().max()) > 0
-    return out.detach().float(), dfeat.float().contiguous(), dw.float()
-
-
-def _half_maxima(dfeat, n_levels):
-    """level_absmax as mlp_bwd reports it TODAY: a lane accumulates ONE maximum over the levels of its half-wave, so level l receives
-    the maximum over the levels l' with (l' >> 1) & 1 == (l >> 1) & 1 (mlp_reduce_device.hpp:32).  The rule for it is only ">= the
-    level's own, tight overall" (_check_exact_mlp asserts no more); the end-to-end test needs the units the grid kernels derive from
-    what mlp_bwd hands them, and a change of the sharing changes this function with it."""
-    own = dfeat.abs().amax(dim=(1, 2)) if dfeat.shape[1] else torch.zeros(n_levels)
-    half = [max([float(own[k]) for k in range(n_levels) if (k >> 1) & 1 == h], default=0.0) for h in (0, 1)]
-    a = torch.zeros(24)
-    for l in range(n_levels):
-        a[l] = half[(l >> 1) & 1]
-    return a, own
-
-
-def _check_exact_mlp(ops, dt, cfgm, w, feat, sel, dout, n_live=None, index=None, activity=True):
-    tdt, _ = DT[dt]
-    n = dout.shape[0]
-    live = n if n_live is None else n_live
-    src = feat if index is None else feat[:, index.long()]
-    out_ref, dfeat_ref, dw_ref = _exact_reference(cfgm, w, src, sel, dout, live, dt, activity)
-    w16, f16 = w.to(tdt).cuda(), feat.to(tdt).cuda()
-    sel_dev = None if sel is None else sel.cuda()
-    n_dev = None if n_live is None else torch.tensor([n_live], dtype=torch.int64, device='cuda')
-    if index is None:
-        out = ops.mlp_fwd(cfgm, w16, f16, sel_dev, n_dev=n_dev).cpu()
-        assert torch.equal(out[:live], out_ref[:live])
-        fin = f16
-    else:
-        fin = ops.IndexedFeat(f16, index.cuda())
-    dfeat, dw, amax = ops.mlp_bwd(cfgm, w16, fin, dout.cuda(), sel_dev, want_absmax=True, n_dev=n_dev)
-    dfeat, dw, amax = dfeat.cpu(), dw.cpu(), amax.cpu()
-    assert torch.equal(dfeat[:, :live], dfeat_ref[:, :live]), int((dfeat[:, :live] != dfeat_ref[:, :live]).sum())
-    if not torch.equal(dw, dw_ref):
-        bad = (dw != dw_ref).nonzero()[:, 0]
-        raise AssertionError(f'dw: {len(bad)} of {dw.numel()} entries differ, first at {int(bad[0])}: kernel {float(dw[bad[0]])} reference {float(dw_ref[bad[0]])}')
-    own = dfeat_ref[:, :live].abs().amax(dim=(1, 2))                   # per level: at least its own maximum; tight overall
-    assert float(amax.max()) == float(own.max())
-    assert bool((amax[:cfgm.n_levels] >= own).all()) and float(amax[cfgm.n_levels:].abs().sum()) == 0.0
-    return dfeat_ref, dw_ref
+# (the cases' builders, the float64 reference and its conditions live in tests/mlp_range_reference.py, with the units as arguments
+#  whose defaults are this file's: features are integers times 2^-2, output gradients integers times 2^-3)
+from tests.mlp_range_reference import DT, MIN_NORMAL, S_DOUT, S_FEAT, _check_exact_mlp, _exact_mlp, _exact_reference, _half_maxima, _sparse_int  # noqa: E402,F401
 
 
 ARCHS = [(1, 1), (1, 16), (2, 3), (2, 16)]
@@ -491,12 +370,27 @@ def test_mlp_backward_through_an_index_is_exact(ops, dt, nh, n_out, n_levels):
 def test_field_backward_to_the_bit(ops, dt, nh, n_out, one_call):
     """ops.field_bwd on the exact data: the network part is the float64 reference, the grid part is the integer oracle on the reference's
     dfeat with the units the kernels derive from the reference's level maxima (closed loop, fresh state)."""
+    _field_backward_to_the_bit(ops, dt, nh, n_out, one_call, S_DOUT)
+
+
+@pytest.mark.parametrize('one_call', [True, False])
+@pytest.mark.parametrize('nh,n_out', [(1, 16), (2, 3)])
+def test_field_backward_to_the_bit_on_subnormal_output_gradients(ops, nh, n_out, one_call):
+    """the same in fp16 with output gradients of integers times 2^-24 (what a small per-sample gradient is after the loss scale): dY and
+    every dH are fp16 subnormals, and the level maxima of a dfeat of that size still drive the fixed-point units to the oracle's table"""
+    _field_backward_to_the_bit(ops, 'fp16', nh, n_out, one_call, 2.0 ** -24)
+
+
+def _field_backward_to_the_bit(ops, dt, nh, n_out, one_call, s_dout):
     tdt, _ = DT[dt]
     cfg, lv = _grid('Linear')
     L = cfg.n_levels
     n, n_live = 4003, 3990
-    cfgm, w, feat, sel, dout = _exact_mlp(dt, nh, n_out, L, n, 400 + n_out, 'zeros')
-    out_ref, dfeat_ref, dw_ref = _exact_reference(cfgm, w, feat, sel, dout, n_live, dt)
+    cfgm, w, feat, sel, dout = _exact_mlp(dt, nh, n_out, L, n, 400 + n_out, 'zeros', s_dout=s_dout)
+    info = {}
+    out_ref, dfeat_ref, dw_ref = _exact_reference(cfgm, w, feat, sel, dout, n_live, dt, s_dout=s_dout, info=info)
+    if s_dout != S_DOUT:                                 # the edge is reached: every dY and every dH is subnormal in the type
+        assert all(float(d.abs().max()) < MIN_NORMAL[dt] for d in info['dz'] + [info['dy']]) and float(dfeat_ref.abs().max()) < MIN_NORMAL[dt]
     g = torch.Generator().manual_seed(17)
     x = torch.cat([_ray_points(2000, g), torch.rand(n - 2000, 3, generator=g)])
     amax, _ = _half_maxima(dfeat_ref[:, :n_live], L)
@@ -523,6 +417,19 @@ def test_field_backward_to_the_bit(ops, dt, nh, n_out, one_call):
 @pytest.mark.parametrize('dt', ['bf16', 'fp16'])
 @pytest.mark.parametrize('nh,n_out,L', [(1, 1, 16), (2, 3, 16), (1, 16, 5), (2, 16, 8)])
 def test_field_inference_is_exact_on_exactly_representable_data(ops, dt, nh, n_out, L):
+    _field_inference_is_exact(ops, dt, nh, n_out, L, 1.0)
+
+
+@pytest.mark.parametrize('dt', ['bf16', 'fp16'])
+@pytest.mark.parametrize('nh,n_out,L', [(1, 1, 16), (2, 16, 8)])
+def test_field_inference_is_exact_on_subnormal_features(ops, dt, nh, n_out, L):
+    """the same with the table scaled by a power of two that puts every feature below the type's smallest normal: the encoding's one
+    rounding is then a rounding to the subnormals' spacing (nearest, ties to even: torch's CPU cast and the kernels' pack alike), the
+    first layer's operands and the hidden activations are subnormals"""
+    _field_inference_is_exact(ops, dt, nh, n_out, L, MIN_NORMAL[dt])
+
+
+def _field_inference_is_exact(ops, dt, nh, n_out, L, table_unit):
     """field_infer (one fused kernel up to FUSED_MAX_SAMPLES rows, encode + MLP beyond), hashgrid_fwd and mlp_fwd against a float64
     forward.  The grid doubles its resolution per level (scale = 16 * 2^l - 1, an integer) and the points are multiples of 1/16, so
     every fraction is a multiple of 1/16 and every trilinear weight a multiple of 2^-12; the table holds integers / 4.  Every
@@ -535,14 +442,14 @@ def test_field_inference_is_exact_on_exactly_representable_data(ops, dt, nh, n_o
     assert lv.total == cfg.total and all(float(cfg.scale[l]) == 16 * 2 ** l - 1 == float(lv.scale[l]) for l in range(L))
     cfgm, w, _, _, _ = _exact_mlp(dt, nh, n_out, L, 64, 500 + L + n_out, 'ones')
     g = torch.Generator().manual_seed(23)
-    table = torch.randint(-2, 3, (cfg.total, 2), generator=g).float() * 0.25
+    table = torch.randint(-2, 3, (cfg.total, 2), generator=g).float() * 0.25 * table_unit
     w16 = torch.cat([w, table.reshape(-1)]).to(tdt).cuda()
     assert torch.equal(w16.cpu().double(), torch.cat([w, table.reshape(-1)]).double())
     Ws, off = [], 0
     for o, i in cfgm.shapes:
         Ws.append(w[off:off + o * i].view(o, i).double())
         off += o * i
-    q = 2.0 ** 14                                          # everything below is an integer number of 2^-14
+    q = 2.0 ** 14 / table_unit                             # everything below is an integer number of 2^-14 table units
     for n in (1, 37, ops.FUSED_MAX_SAMPLES, ops.FUSED_MAX_SAMPLES + 817):
         x = torch.randint(0, 17, (n, 3), generator=g).float() / 16.0
         x[0] = torch.tensor([0.0, 1.0, 0.5])
@@ -550,10 +457,12 @@ def test_field_inference_is_exact_on_exactly_representable_data(ops, dt, nh, n_o
         sel[0] = 1
         # ---- the reference, and the conditions that make it THE answer
         enc64 = O.hashgrid_encode(x, table.double(), lv, 'Linear')                 # fp32 weights, float64 products and sums: exact
-        assert enc64.dtype == torch.float64 and torch.equal((enc64 * q).round(), enc64 * q) and float(enc64.abs().max()) <= 0.5
+        assert enc64.dtype == torch.float64 and torch.equal((enc64 * q).round(), enc64 * q) and float(enc64.abs().max()) <= 0.5 * table_unit
         enc = O.hashgrid_encode(x, table, lv, 'Linear', quant=dt)                  # the oracle's emulation: the same numbers in fp32
         assert torch.equal(enc.double(), enc64)
         feat_ref = enc.to(tdt)                                                     # [n, 2L]: ONE rounding to the storage type
+        if table_unit != 1.0:                                                      # the edge is reached: features subnormal, most of them non-zero
+            assert float(feat_ref.float().abs().max()) < MIN_NORMAL[dt] and float((feat_ref != 0).float().mean()) > 0.5
         h = torch.cat([feat_ref.double(), torch.zeros(n, cfgm.n_in_pad - 2 * L, dtype=torch.float64)], 1)
         for W in Ws[:-1]:
             assert float((h.abs() @ W.abs().t()).max()) * q < 2 ** 24              # every fp32 sum exact

@@ -185,6 +185,43 @@ def test_gradient_of_a_shallower_grid_and_the_plain_gradient():
     assert float(((sigma.cpu() - sq).abs() / sq.abs()).max()) < 16 * 2.0 ** -11
 
 
+@pytest.mark.parametrize('dtype', ['bf16'])
+def test_gradient_above_and_below_the_exponential_clamp(dtype):
+    """The 8-level field with its output row times -256: y spreads over about +-70, a third of the samples lie above the clamp of the
+    activation's derivative -- the gradient there is e^15 dy/dx while sigma itself is e^y, as O.trunc_exp has it -- and some below -15.
+    bf16 only: the fp16 oracle rounds its dH -- e^15 times the output row -- to fp16, where e^15 > 65504 is inf; its gradient is NaN
+    at this scale (the kernels apply the activation's derivative last, in fp32, and stay finite).
+    Same reference (autograd on the quantised oracle), same bound."""
+    from perf_amd import ops
+    from perf_amd.grid import GridConfig, MlpConfig
+    lv = O.grid_levels(n_levels=8)
+    spec = O.FieldSpec(lv, 1, 1, 'None')
+    p = O.init_field_params(spec, 7)
+    g = torch.Generator().manual_seed(2)
+    p[spec.n_net:] = (torch.rand(lv.n_params, generator=g) * 2 - 1) * 0.5
+    n1 = 64 * spec.n_in
+    p[n1:n1 + 64] *= -256.0
+    x = torch.rand(777, 3, generator=g) * 0.98 + 0.01
+    y = O.network_with_encoding(x, p.double(), spec)[:, 0]
+    above, below = float((y > 15.0).double().mean()), float((y < -15.0).double().mean())
+    print(f'[field_grad_x saturated {dtype}] y in [{float(y.min()):.1f}, {float(y.max()):.1f}], {above:.1%} above the clamp, {below:.1%} below -15')
+    assert 0.15 <= above <= 0.5 and below >= 0.02 and float(y.max()) < 85.0          # (the forward stays finite: expf overflows at 88.7)
+    gq, sq, near_zero, e_q = _oracle_noise(x, p, spec, [0., 0, 0, 1, 1, 1], dtype)
+    grid, mlp = GridConfig(n_levels=8), MlpConfig(n_levels=8, n_hidden_layers=1, n_output_dims=1, output_activation='Exponential')
+    w16 = ops.cast_params(p.cuda(), dtype)
+    sel = torch.ones(777, dtype=torch.uint8, device='cuda')
+    sigma, grad = ops.field_grad_x(grid, mlp, x.cuda(), sel, w16)
+    assert torch.isfinite(sigma).all() and torch.isfinite(grad).all()
+    nq = torch.linalg.vector_norm(gq, dim=1)
+    err = (torch.linalg.vector_norm(grad.cpu() - gq, dim=1) / nq)[~near_zero & (nq > 0)]
+    eq, ek = _stats(e_q), _stats(err)
+    print(f'[field_grad_x saturated {dtype}] e_q {eq}; kernel vs quant oracle {ek}')
+    assert ek['max'] <= 2 * eq['max'] and ek['p99'] <= 2 * eq['p99'], (ek, eq)
+    # the forward is exp(y) unclamped: where the gradient's factor stopped at e^15, sigma went on
+    top = (sq > 2.0 * float(np.exp(15.0)))
+    assert float(top.float().mean()) >= 0.1 and bool((sigma.cpu()[top] > float(np.exp(15.0))).all())
+
+
 def test_inference_only_field_gradient():
     """fields.InferenceNeRF (16-bit working copies only) takes the same kernel: its own weights, read back, are the oracle's parameters;
     its default 20-level grid is refused with the reason."""

@@ -265,6 +265,28 @@ def test_random_data_lies_within_two_noise_units_of_the_quantised_oracle(dtype, 
     _check_against_oracle(c, c['ds'], c['dg'], f'{dtype}_L{levels}')
 
 
+@pytest.mark.parametrize('dtype', ['bf16'])
+def test_random_data_above_and_below_the_exponential_clamp(dtype):
+    """The 8-level case with its output row times -256: the network output y spreads over about +-70, a third of the samples lie
+    above the clamp of the activation's derivative (a'(y) = e^15 and a''(y) = 0 there, as O.trunc_exp's backward and its derivative
+    have it) and some below -15.  The scale touches neither the first layer nor the table: the removed samples and the agreeing masks
+    are the 8-level case's.  Same reference, same bound.  bf16 only: the fp16 oracle rounds its dH -- e^15 times the output row -- to
+    fp16, where e^15 > 65504 is inf, and its gradient is NaN at this scale (the kernels apply the activation's derivatives last, in
+    fp32, and stay finite)."""
+    c = dict(_case(dtype, 8))
+    spec = c['spec']
+    n1 = 64 * spec.n_in
+    geo = c['geo'].clone()
+    geo[n1:n1 + 64] *= -256.0
+    c['geo'] = geo
+    x_in = c['x'][:c['n_in']]
+    y = O.network_with_encoding((x_in - torch.tensor(c['aabb'][:3])) / (torch.tensor(c['aabb'][3:]) - torch.tensor(c['aabb'][:3])), geo.double(), spec)[:, 0]
+    above, below = float((y > 15.0).double().mean()), float((y < -15.0).double().mean())
+    print(f'[field_grad_x_bwd saturated {dtype}] y in [{float(y.min()):.1f}, {float(y.max()):.1f}], {above:.1%} above the clamp, {below:.1%} below -15')
+    assert 0.15 <= above <= 0.5 and below >= 0.02 and float(y.max()) < 85.0          # (the forward stays finite: expf overflows at 88.7)
+    _check_against_oracle(c, c['ds'], c['dg'], f'{dtype}_L8_saturated')
+
+
 # ---- 3. variants ---------------------------------------------------------------------------------------------------------------------
 def test_one_upstream_gradient_at_a_time_and_their_sum():
     c = _case('fp16', 16)
